@@ -6,6 +6,8 @@
                                                       # N workers (one per GPU, RCCL), or run it under
                                                       # `python -m torch.distributed.run --nproc-per-node N`
     python bench.py --config C3|C3g|C4|C5             # make another BASELINE config the main line
+    python bench.py ... --dump-outputs DIR            # + the main line's last timed outputs as DIR/<key>.npy (inputs
+                                                      # are seeded: two builds compare output for output)
 
 A "step" is one render_rays-equivalent call over the rank's batch, inputs resident in HBM, outputs left on the
 device.  metric = ray-samples/s = network-evaluated samples of all ranks / wall time (max over ranks).
@@ -267,6 +269,38 @@ def errors_vs(ref, out):
     mse = float(((out[key].detach().cpu().double() - ref[key].double()) ** 2).mean())
     return {"max_rel": errs, "l2_rel": l2, "psnr_equiv_db": (-10 * np.log10(mse)) if mse > 0 else float("inf"),
             "psnr_key": key}
+
+
+DUMP_LIMIT = 64 << 20       # bytes: --dump-outputs writes at most this much in all
+DUMP_SEED = 20240917        # the fixed row sample of outputs that would exceed it
+
+
+def dump_outputs(out, dirname, limit=DUMP_LIMIT):
+    """--dump-outputs: the result dict of one render_rays call as ``dirname/<key>.npy``, float64 kept, everything else float32
+    (a lazy consensus vector is materialised first, as any caller that reads it would).  If the arrays together exceed
+    `limit` bytes, each one keeps the same fraction of its rows, chosen by a fixed seed from its shape alone -- so two builds
+    dump the same rows.  -> {key: [shape written, rows of the full output]}."""
+    import numpy as np
+    arrays = {}
+    for k in sorted(out):
+        v = out[k]
+        if v is None:
+            continue
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        if a.dtype.kind not in "biuf":
+            continue
+        arrays[k] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.uint64) else np.float32, copy=False)
+    total = sum(a.size * a.itemsize for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for k, a in arrays.items():
+        n = a.shape[0] if a.ndim else 1
+        if total > limit and a.ndim:
+            keep = max(1, n * limit // total)
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))]
+        np.save(os.path.join(dirname, "".join(c if c.isalnum() or c in "_-." else "_" for c in k) + ".npy"), a)
+        written[k] = [list(a.shape), n]
+    return written
 
 
 def traffic_of(name):
@@ -768,6 +802,10 @@ def run_config(name, a, ctx, steps, warmup, main):
         if host_ts and rank == 0:
             print("host time of each timed call's enqueue, ms:", [round((b - a) * 1e3, 3) for a, b in zip([t0] + host_ts, host_ts)],
                   "then the final synchronize: %.3f" % ((t0 + elapsed - host_ts[-1]) * 1e3), file=sys.stderr)
+        if main and rank == 0 and a.dump_outputs:
+            # what the last timed call returned (rank 0's rays at N > 1), before anything else runs on the stream
+            written = dump_outputs(out, a.dump_outputs)
+            print("dump_outputs:", a.dump_outputs, json.dumps(written), file=sys.stderr)
         # per-call device span (step_span_ms), outside the timed region: the event pairs cost ~10 us of stream time each on
         # this runtime, which is 3 % of a 0.33 ms step
         for i in range(steps):
@@ -1197,7 +1235,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true",
                     help="skip the extra fwd+bwd measurement (SURVEY.md §8d: reported separately from the graded forward)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main line's last timed step returned as DIR/<key>.npy "
+                         "(float32, float64 kept; at most 64 MB in all, a fixed row sample beyond that; rank 0 at N > 1)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and world == 1 and not os.environ.get("MF_BENCH_CHILD"):
         sys.exit(spawn_workers(a.gpus, sys.argv[1:]))      # nothing above touched the GPU (torch is not even imported)

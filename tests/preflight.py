@@ -12,9 +12,10 @@ for it before its first GPU test, so the children never share the device with a 
      first execution of that code).
 
   3. `bench.py --steps 3 --warmup 1` (main line only) with MF_BENCH_FORCE_DIST=1: a 1-rank RCCL process group around the run, stdout kept
-     apart -- RCCL's version banner goes through C stdio to stdout and must not land behind the compact JSON line.
+     apart -- RCCL's version banner goes through C stdio to stdout and must not land behind the compact JSON line; with
+     --dump-outputs, so that the arrays bench.py writes can be held to the same render in the test process.
 
-usage: preflight.py <outdir>   ->   <outdir>/{rccl.log, bench2.log, bench1d.out, bench1d.log, status.json}"""
+usage: preflight.py <outdir>   ->   <outdir>/{rccl.log, bench2.log, bench1d.out, bench1d.log, dump/*.npy, status.json}"""
 import json
 import os
 import subprocess
@@ -50,7 +51,7 @@ def main():
     with open(os.path.join(out, "bench1d.out"), "w") as fo, open(os.path.join(out, "bench1d.log"), "w") as fe:
         try:
             status["bench1d"] = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extra-legs",
-                                                "--no-cpu-baseline", "--no-train-leg"], stdout=fo, stderr=fe, env=denv, cwd=ROOT, timeout=240).returncode
+                                                "--no-cpu-baseline", "--no-train-leg", "--dump-outputs", os.path.join(out, "dump")], stdout=fo, stderr=fe, env=denv, cwd=ROOT, timeout=240).returncode
         except subprocess.TimeoutExpired:
             fe.write("\nTIMEOUT after 240 s\n")
             status["bench1d"] = -9

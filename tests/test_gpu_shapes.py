@@ -284,6 +284,30 @@ def test_bench_json_line_is_last_on_stdout_under_rccl(preflight):
     assert any("RCCL version" in ln for ln in lines[:-1]), "expected RCCL's banner in front of the JSON line (did the runtime stop printing it?)"
 
 
+def test_bench_dump_outputs_are_the_c2_render(preflight, M, R):
+    """`bench.py --dump-outputs DIR` (the same tests/preflight.py run as above): DIR holds what the last timed C2 step returned --
+    one float32 .npy per key of the result dict -- and that is the C2 batch (seeded rays, the "nerf" weight draw) rendered
+    here by the same library, and within 1e-4 max-rel of the oracle."""
+    from moco_flow_amd import synth
+    assert preflight and preflight["status"].get("bench1d") == 0, preflight.get("status")
+    d = os.path.join(preflight["dir"], "dump")
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert sorted(got) == ["depth_coarse", "opacity_coarse", "rgb_coarse"], sorted(got)
+    c = dict(RENDER_CASES["r_nerf_dir_dense"])
+    tags = dict(coarse="nerf")
+    rays_np, bg_np = synth.rays(0, 4096)
+    embs, nerfs, kw = build_case(M, c, 0, device="cuda", tags=tags)
+    embs_o, nerfs_o, kw_o = build_case(R, c, 0, tags=tags)
+    with torch.no_grad():
+        res = M.render_rays(torch.from_numpy(rays_np).cuda(), torch.from_numpy(bg_np).cuda(), embs, nerfs, **kw)
+        want = R.render_rays(torch.from_numpy(rays_np), torch.from_numpy(bg_np), embs_o, nerfs_o, **kw_o)
+    for k, a in got.items():
+        assert a.dtype == np.float32 and a.shape == tuple(res[k].shape), (k, a.dtype, a.shape)
+        same, e = relerr(a, res[k]), relerr(a, want[k])
+        print(f"bench dump {k}: max-rel {same:.2e} vs this process' render, {e:.2e} vs the oracle")
+        assert same <= 1e-6 and e <= TOL, (k, same, e)
+
+
 def test_lazy_consensus_vectors(M):
     """The consensus vectors as lazy.MaskedVector (moco_flow_amd/lazy.py): what the unchanged trainer does with them --
     torch.mean(res["nof_local_disp_coarse"]) (trainer_moco_flow.py:317-328) -- involves no compaction and NO host

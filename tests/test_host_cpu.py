@@ -847,6 +847,45 @@ def test_bench_under_torch_distributed_run():
     assert d["dryrun"][0] == 3.0 and len(last.encode()) <= 1800
 
 
+def test_bench_dump_outputs_host_logic(tmp_path):
+    """bench.py --dump-outputs (the writer, on CPU tensors): one DIR/<key>.npy per array of the result dict -- float64 kept,
+    float32 / bool / int32 as float32, a lazy consensus vector materialised -- values unchanged; beyond the byte limit every
+    array keeps the same fraction of its rows, the same rows from call to call, at most the limit in all.  And --steps
+    below 1 is refused before anything runs (ms_per_step = elapsed / steps)."""
+    import subprocess
+    import bench
+    from moco_flow_amd.lazy import ConsensusPass, MaskedVector
+    torch.manual_seed(0)
+    alphas = torch.rand(6, 5)
+    plane = torch.rand(6, 5)
+    g = ConsensusPass(alphas, {"local": plane}, None, lambda: {"local": plane[alphas.ge(0.5)]}, False)
+    out = {"rgb_coarse": torch.rand(1000, 3), "depth_coarse": torch.rand(1000), "loss_partials": torch.rand(12, dtype=torch.float64),
+           "mask": torch.rand(1000) > 0.5, "nof_local_disp_coarse": MaskedVector(g, "local")}
+    d = tmp_path / "full"
+    written = bench.dump_outputs(out, str(d))
+    assert sorted(os.listdir(d)) == sorted(k + ".npy" for k in out) and set(written) == set(out)
+    for k, v in out.items():
+        a = np.load(d / (k + ".npy"))
+        want = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        assert a.dtype == (np.float64 if k == "loss_partials" else np.float32), (k, a.dtype)
+        assert a.shape == want.shape and np.array_equal(a, want.astype(a.dtype)), k
+    assert written["nof_local_disp_coarse"] == [[int(alphas.ge(0.5).sum())], int(alphas.ge(0.5).sum())]
+    limit = 8000
+    runs = []
+    for i in range(2):
+        di = tmp_path / f"sampled{i}"
+        w = bench.dump_outputs({k: out[k] for k in ("rgb_coarse", "depth_coarse")}, str(di), limit=limit)
+        assert sum(os.path.getsize(di / f) - 128 for f in os.listdir(di)) <= limit           # (128 B: the .npy header)
+        runs.append({k: np.load(di / (k + ".npy")) for k in w})
+        assert w["rgb_coarse"][1] == 1000 and 0 < w["rgb_coarse"][0][0] < 1000
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    rows = [int(np.flatnonzero((out["rgb_coarse"].numpy() == r).all(1))[0]) for r in runs[0]["rgb_coarse"]]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert bad.returncode != 0 and "--steps" in bad.stderr
+
+
 def test_profile_summary_splits_coarse_and_fine_launches():
     """tools/summarize_prof.py: the dispatches of ONE kernel that fall into two duration classes -- the coarse and
     the fine pass of a render_rays call: same grid, dynamic LDS the trace does not record -- are reported per class, never as one
