@@ -891,14 +891,15 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
     const int r_max = (tile_samples - 1) / a->n_samples + 2;
     p.rb_buf_bytes = (uint32_t)round_up((int64_t)r_max * p.rb_layers * 512, 1024);
     p.rb_off = lds; lds += 2 * p.rb_buf_bytes;
-    if (lds + 20u * (uint32_t)a->n_samples > 160u * 1024u)
+    // (two rows per buffer are the fewest any S needs, S >= tile: then the samples do not fit, refused just below)
+    if (r_max > 2 && lds + 20u * (uint32_t)a->n_samples > 160u * 1024u)
       return fail(MF_E_UNSUPPORTED, "mf_render_pass(bf16): n_samples=%d leaves no room for the per-ray NoF bias rows of a tile "
                   "(%d rays); use MF_PREC_F32 for such short rays", a->n_samples, r_max);
   }
 
   // rays per group: smallest G with G*S a multiple of the tile (256 samples; x3: 128), capped by the LDS left
   const uint32_t lds_cap = 160 * 1024;
-  const int max_samples = (int)((lds_cap - lds) / 20);
+  const int max_samples = lds < lds_cap ? (int)((lds_cap - lds) / 20) : 0;
   const int S = a->n_samples;
   if (S > max_samples) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
   int G = 1;

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from cases import RENDER_CASES
-from helpers import OracleOps, build_case, case_inputs, load_golden, pad_to, relerr
+from helpers import OracleOps, _check_grads_vs_float64, _l2rel, build_case, case_inputs, load_golden, pad_to, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -399,50 +399,9 @@ def _oracle_grads(R, c, seed, rays, bg, loss_fn, dtype=torch.float32):
 # float64 oracles differ by percents on some tensors (r3 measured 30-120 % max-rel on r_moco_global's NeRF / backward-NoF
 # tensors, 0.6 % at default init), and a fixed bar either hides a regression on the well-conditioned tensors or fails on the
 # others -- rounds 1-3 used 5e-2 / 3e-3 against the fp32 oracle; per-tensor noise floors replace them.  What pins each backward
-# KERNEL at 1e-4 is test_*_backward_vs_oracle* (same function at the same points, masks included).
+# KERNEL at 1e-4 is test_*_backward_vs_oracle* (same function at the same points, masks included).  The check itself is
+# helpers._check_grads_vs_float64 (tests/test_gpu_launch_shapes.py holds its training steps to it too).
 GRAD_CASES = ["r_nerf_dir_dense", "r_nerf_ind_dense", "r_moco_global", "r_moco_global_default"]
-
-
-def _check_grads_vs_float64(nets, want32, want64, skip=lambda k: False, label="", fp32_bar=None):
-    """fp32_bar: fixed max-rel bar against the fp32 oracle (NeRF-only passes: HIP and the fp32 oracle evaluate the same ReLU
-    masks and agree to ~1e-6 where both sit 1e-3 from the float64 truth -- there the fixed 1e-4 is the tighter test).
-    The yardstick of a tensor is the larger of its own noise and the MEDIAN noise of its network's tensors: one fp32-vs-float64
-    pair is a single draw of a random distance, and on some tensor it comes out several times under the typical one
-    (r_moco_global_default, xyz_encoding_8.weight: 1.6e-5 where the network's median is 3e-4 and HIP sits at 2.1e-4)."""
-    checked, worst, floor = 0, (0.0, ""), (0.0, "")
-    for i, m in enumerate(nets):
-        live = [k for k, _ in m.named_parameters() if not skip(k) and want64[f"{i}.{k}"] is not None
-                and float(want64[f"{i}.{k}"].abs().max()) > 0.0]
-        net_l2 = float(np.median([_l2rel(want32[f"{i}.{k}"], want64[f"{i}.{k}"]) for k in live])) if live else 0.0
-        net_mr = float(np.median([relerr(want32[f"{i}.{k}"], want64[f"{i}.{k}"]) for k in live])) if live else 0.0
-        for k, p in m.named_parameters():
-            key = f"{i}.{k}"
-            if skip(k):
-                assert p.grad is None, key
-                continue
-            w64, w32 = want64[key], want32[key]
-            if w64 is None or float(w64.abs().max()) == 0.0:
-                assert p.grad is None or float(p.grad.abs().max()) == 0.0, key
-                continue
-            assert p.grad is not None, key
-            noise_l2, noise_mr = max(_l2rel(w32, w64), net_l2), max(relerr(w32, w64), net_mr)
-            e_l2, e_mr32 = _l2rel(p.grad, w64), relerr(p.grad, w32)
-            worst, floor = max(worst, (e_l2, key)), max(floor, (noise_l2, key))
-            # (NeRF-only passes, fp32_bar given: the multiplier is capped -- ADVICE r4 -- 3 x a 7.6e-3 first-layer floor would let
-            #  a 2e-2 error through; the MoCo cases' floors reach 100 % on some tensors and cannot be capped)
-            # (HIP shares the fp32 oracle's ReLU masks there and so sits AT the fp32 oracle's own distance from the truth: the cap
-            #  cannot go under 1.5 x that distance; the fixed fp32_bar below is what catches a mis-scaled gradient)
-            assert e_l2 <= max(TOL, 3 * noise_l2 if fp32_bar is None else min(3 * noise_l2, max(1.5 * noise_l2, 5e-3))), (key, e_l2, noise_l2)
-            # max-rel guard against a wrong element.  Its floor is 2e-3, not 1e-4: ONE ReLU unit whose pre-activation rounds to the
-            # other side of zero between two fp32 evaluation orders moves a weight-gradient row of the layers in front of it by
-            # that sample's whole contribution -- a discrete event (measured 1.4e-4 .. 3.8e-4 of max|dW| at 6144 samples, layers
-            # 1-3 only, the layers behind the unit agreeing to 2e-7, with the fp32 backward kernels too: a one-off script, since removed) that
-            # the fp32-vs-float64 pair of the same batch need not contain
-            assert e_mr32 <= (fp32_bar if fp32_bar is not None else max(2e-3, 3 * noise_mr)), (key, e_mr32, noise_mr)
-            checked += 1
-    print(f"{label}: end-to-end gradients vs the float64 oracle, worst l2-rel {worst[0]:.2e} at {worst[1]} (the fp32 oracle's own worst "
-          f"{floor[0]:.2e} at {floor[1]}; {checked} tensors, each within max(1e-4, 3 x its noise floor))")
-    return checked
 
 
 @pytest.mark.parametrize("name", ["r_nerf_dir_dense", "r_nerf_ind_dense"])
@@ -780,11 +739,6 @@ def _psnr(a, b):
     """models/metrics.py:4-13 with unit peak: -10 log10(mean((a-b)^2))."""
     mse = float(((torch.as_tensor(a).detach().cpu().double() - torch.as_tensor(b).detach().cpu().double()) ** 2).mean())
     return -10 * np.log10(mse) if mse > 0 else 200.0
-
-
-def _l2rel(a, b):
-    a, b = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(b).detach().cpu().double()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 # bf16 bars: a few dB / a factor ~2 under what the kernels measure (printed by the tests; profiles/README.md), so
@@ -1726,11 +1680,13 @@ def test_render_image_vs_golden(M):
 
 
 @pytest.mark.parametrize("act,use_noise,use_bg,N,S", [("relu", False, True, 33, 64), ("softplus", True, True, 9, 200),
-                                                     ("relu", True, False, 5, 2), ("softplus", False, False, 3, 700)])
+                                                     ("relu", True, False, 5, 2), ("softplus", False, False, 3, 700),
+                                                     ("relu", True, True, 7, 65), ("softplus", True, True, 2, 2048)])
 def test_composite_backward_unit(M, R, act, use_noise, use_bg, N, S):
     """autograd.CompositeSamples (mf_composite_backward) against the oracle's CPU autograd of the composite
     (cpu_ref.composite: rendering.py:157-192) on the same planes: dL/d[rgb, sigma] per sample to 1e-4,
-    including the 1e10 last interval, multi-chunk rays (S > 64) and S = 2 (S = 1 is degenerate in the
+    including the 1e10 last interval, multi-chunk rays (S > 64; S = 65: a second chunk of one sample), S = 2048 (the kernel
+    stages 80 S bytes of LDS per ray: 2048 fills the 160 KiB exactly) and S = 2 (S = 1 is degenerate in the
     reference itself: `ones_like(deltas[:, :1])` of an empty tensor drops the only interval, rendering.py:158-160)."""
     from moco_flow_amd import autograd as A
     O = OracleOps(R)
@@ -1753,6 +1709,22 @@ def test_composite_backward_unit(M, R, act, use_noise, use_bg, N, S):
     torch.autograd.backward(list(outs), g)
     assert relerr(b.grad[:, :3], a.grad[:, :3]) <= 1e-5
     assert relerr(b.grad[:, 3], a.grad[:, 3]) <= 1e-4, relerr(b.grad[:, 3], a.grad[:, 3])
+
+
+def test_composite_backward_refuses_more_samples_than_it_stages(M):
+    """One sample past the 160 KiB of LDS of mf_composite_backward (S = 2049): refused on the host before any launch, with the
+    envelope in the message, and the gradient left untouched."""
+    from moco_flow_amd import autograd as A
+    N, S = 2, 2049
+    rays = torch.zeros(N, 9, device="cuda")
+    rays[:, 5] = 1.0
+    z = torch.linspace(2, 6, S, device="cuda").expand(N, S).contiguous()
+    b = torch.rand(N * S, 4, device="cuda").requires_grad_(True)
+    zero = torch.zeros(N, device="cuda")
+    outs = A.CompositeSamples.apply(b, rays, z, None, "relu", None, torch.zeros(N, 3, device="cuda"), zero, zero)
+    with pytest.raises(NotImplementedError, match=r"mf_composite_backward: S=2049 \(1\.\.2048\)"):
+        torch.autograd.backward(list(outs), [torch.ones(N, 3, device="cuda"), torch.ones(N, device="cuda"), torch.ones(N, device="cuda")])
+    assert b.grad is None
 
 
 @pytest.mark.parametrize("precision", ["bf16", "bf16x3"])

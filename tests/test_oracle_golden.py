@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from cases import RENDER_CASES
-from helpers import build_case, case_inputs, load_golden, relerr
+from helpers import build_case, case_inputs, load_golden, relerr, subset_rays, varied_indices
 from oracle import cpu_ref as R
 
 TOL = 1e-6
@@ -259,3 +259,31 @@ def test_bf16_ref_modes_sit_where_their_arithmetic_puts_them():
             e = B.Embedding(3, nf)
             e.mode = mode
             assert float((e(x) - ref).abs().max()) <= tol, (nf, mode, float((e(x) - ref).abs().max()))
+
+
+@pytest.mark.parametrize("arith", ["cpu_ref", "bf16_ref"])
+@pytest.mark.parametrize("name", ["r_nerf_dir_dense", "r_moco_global", "r_moco_global_fine", "r_nerf_dir_fine_train"])
+def test_oracle_of_a_ray_subset_is_the_subset_of_the_oracle(name, arith):
+    """What tests/test_gpu_launch_shapes.py rests on: the oracle of rays[idx] is the oracle of all rays, indexed by idx -- per-ray
+    outputs do not depend on the batch around them -- for cpu_ref and for bf16_ref with its bf16 hooks on, on the fixtures'
+    own inputs and with per-ray varied image indices, first / last / scattered rays, two-pass cases included.  To 1e-6, not
+    bitwise: the CPU GEMM may block differently at another batch size."""
+    from oracle import bf16_ref as B
+    c = RENDER_CASES[name]
+    g = load_golden(name)
+    seed = int(g["meta_seed"])
+    backend = R if arith == "cpu_ref" else B.Backend(B.BF16)
+    embs, nerfs, kw = build_case(backend, c, seed)
+    bg = torch.from_numpy(g["in_background"])
+    rays0 = torch.from_numpy(g["in_rays"])
+    n = rays0.shape[0]
+    idx = subset_rays(n, n // 2, seed=1)
+    assert idx[0] == 0 and idx[-1] == n - 1 and 4 < len(idx) < n
+    for rays in (rays0, varied_indices(rays0, seed=2)):
+        with torch.no_grad():
+            full = R.render_rays(rays, bg, embs, nerfs, **kw)
+            part = R.render_rays(rays[idx], bg[idx], embs, nerfs, **kw)
+        keys = [k for k in full if k.split("_")[0] in ("rgb", "depth", "opacity")]
+        assert len(keys) == (6 if c["M"] > 0 else 3)
+        for k in keys:
+            assert relerr(part[k], full[k][idx]) <= TOL, (k, relerr(part[k], full[k][idx]))
