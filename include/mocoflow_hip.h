@@ -542,6 +542,23 @@ int32_t mf_smpl_frame_transforms(const float* T_src, const float* T_tgt, int64_t
 int32_t mf_apply_vertex_transforms(const float* trans, const int64_t* ind, int64_t V, const float* query, int64_t Q,
                                    float* cano, void* stream);
 
+/* ---- marching cubes: mcubes.marching_cubes of visualize_mesh (trainer_moco_flow.py:528-532, trainer_nerf.py:247-251)
+ * on the device.  vol: C-contiguous fp32 (n0, n1, n2), each side >= 2, at most 2^31 - 1 points (else MF_E_INVALID);
+ * clamp_zero != 0 reads every value as v < 0 ? 0 : v (the reference's np.maximum(sigma, 0)).  A corner is below iff v < iso.
+ * One vertex per crossing lattice edge (p, axis), at p + t e_axis in index coordinates of vol's axes, t = (iso - f(p)) /
+ * (f(p + e_axis) - f(p)) in fp32; vertices sorted by 3 p + axis (p: C-order point index), triangles by the C-order index of
+ * their cell, within a cell in the order of the case table (mf_mc_tables.hpp: classic Lorensen-Cline, scikit-image's
+ * triangulation and raw winding).  Deterministic: bit-identical from run to run.
+ * Bytes of the caller's scratch (or MF_E_INVALID on a bad shape): 4 per lattice point + 24 per 1024 points. */
+int64_t mf_mc_scratch_bytes(int64_t n0, int64_t n1, int64_t n2);
+/* Pass 1: classify the volume and write counts (device int64[2]) = [V, T]; scratch keeps what mf_mc_emit needs. */
+int32_t mf_mc_count(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
+                    void* scratch, int64_t* counts, void* stream);
+/* Pass 2, after mf_mc_count on the same stream with the same vol / shape / iso / clamp_zero / scratch: verts (V, 3) fp32 and
+ * tris (T, 3) int64 vertex indices, sized by the counts pass 1 wrote (NULL only when that count is 0). */
+int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
+                   const void* scratch, float* verts, int64_t* tris, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

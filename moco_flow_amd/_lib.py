@@ -161,6 +161,9 @@ SYMBOLS = {
     "mf_loss_partials_backward": (C.c_int32, [C.POINTER(mf_loss_grad_pass), C.POINTER(mf_loss_grad_pass), _fp, C.c_int64, _fp, _fp, _fp]),
     "mf_compact_scratch_bytes": (C.c_int64, [C.c_int64]),
     "mf_compact_mask": (C.c_int32, [_fp, _fp, _fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
+    "mf_mc_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_mc_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp]),
+    "mf_mc_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()

@@ -1,0 +1,303 @@
+// mf_mesh.hip -- marching cubes on the device (mf_mc_scratch_bytes / mf_mc_count / mf_mc_emit): the isosurface step of
+// visualize_mesh (trainer_moco_flow.py:528-545, trainer_nerf.py:247-259: mcubes.marching_cubes on the host) with the
+// volume and the mesh kept on the device.
+//
+// Contract (tests/mc_oracle.py restates it in numpy, bit for bit):
+//   - a corner is below iff v < iso (NaN is not); clamp_zero reads v < 0 ? 0 : v;
+//   - one vertex per crossing lattice edge (p, axis), shared by the cells around it, at p + t e_axis with
+//     t = (iso - f(p)) / (f(p + e_axis) - f(p)) in fp32 (index coordinates, one rounding per operation: -ffp-contract=off);
+//   - vertices sorted by edge id 3 p + axis, triangles by the C-order index of their cell and within a cell in table order
+//     (mf_mc_tables.hpp): the output does not depend on scheduling and is bit-identical from run to run.
+//
+// Three launches.  A block owns kPointsPerBlock consecutive lattice points (C order), 4 per thread, loaded as float4 along
+// n2 where the rows allow it.  Per point: the crossing mask of the 3 edges it owns and the case of the cell it is the first
+// corner of.  (1) count: block-local exclusive scans (wave ballots + LDS) of the vertex and triangle counts; per point that
+// owns a crossing edge, map[p] = (block-local vertex base << 3) | mask; per block its two totals.  (2) scan: one block turns
+// the per-block totals into int64 offsets and writes [V, T].  (3) emit: recomputes the masks and cases (the volume's second
+// read), writes the vertices, and resolves each triangle corner (q, axis) to off[block of q] + (map[q] >> 3) + the number of
+// q's crossing edges below `axis`.  map is read only where the count pass wrote it (the table uses crossing edges only).
+#include "mf_host.hpp"
+#include "mf_mc_tables.hpp"
+
+#include <climits>
+
+using namespace mf;
+using namespace mf::mc;
+
+namespace mf {
+namespace mc {
+
+constexpr int kThreads = 256;
+constexpr int kPerThread = 4;
+constexpr int kPointsPerBlock = kThreads * kPerThread;
+constexpr int kScanThreads = 1024;
+
+struct McParams {
+  const float* vol;
+  int n0, n1, n2;
+  long long S, P;               // n1 n2, n0 n1 n2 (< 2^31)
+  float iso;
+  int clamp_zero;
+  int nblocks;
+  long long* off;               // [2 nblocks]: exclusive vertex / triangle offset of each block (scan)
+  int* blk;                     // [2 nblocks]: vertex / triangle total of each block (count)
+  int* map;                     // [P]: (block-local vertex base << 3) | crossing mask, at points that own a crossing edge
+  long long* counts;            // [V, T]
+  float* verts;                 // (V, 3)
+  long long* tris;              // (T, 3)
+};
+
+// f(base + c), c = 0..4 (a thread's 4 points and the next one); entries at or past P are never used and read as 0
+template <bool kVec>
+__device__ __forceinline__ void load_row(const McParams& p, long long base, float f[5]) {
+  if (kVec && base + 4 < p.P) {
+    const float4 v = *reinterpret_cast<const float4*>(p.vol + base);
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+    f[4] = p.vol[base + 4];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) f[c] = base + c < p.P ? p.vol[base + c] : 0.f;
+  }
+  if (p.clamp_zero) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) f[c] = f[c] < 0.f ? 0.f : f[c];
+  }
+}
+
+// One thread's 4 points: values of the rows p, p + n2, p + S, p + S + n2 (row r = 2 o0 + o1 holds corner offsets (o0, o1)),
+// per point its lattice index, crossing mask (bit a: edge along axis a) and cell case (0 when p is not a cell's first corner).
+struct Points {
+  float f[4][5];
+  int i[kPerThread], j[kPerThread], k[kPerThread];
+  int mask[kPerThread], cases[kPerThread];
+  int nv, nt;
+};
+
+template <bool kVec>
+__device__ __forceinline__ void classify(const McParams& p, long long p0, Points& s) {
+  load_row<kVec>(p, p0, s.f[0]);
+  load_row<kVec>(p, p0 + p.n2, s.f[1]);
+  load_row<kVec>(p, p0 + p.S, s.f[2]);
+  load_row<kVec>(p, p0 + p.S + p.n2, s.f[3]);
+  unsigned b[4];                                                // bit c of b[r]: f[r][c] below
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    b[r] = 0;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) b[r] |= (s.f[r][c] < p.iso ? 1u : 0u) << c;
+  }
+  const unsigned pp = p0 < p.P ? (unsigned)p0 : 0u;
+  int k = (int)(pp % (unsigned)p.n2), j = (int)((pp / (unsigned)p.n2) % (unsigned)p.n1), i = (int)(pp / (unsigned)p.S);
+  s.nv = s.nt = 0;
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    s.i[q] = i; s.j[q] = j; s.k[q] = k;
+    int mask = 0, cs = 0;
+    if (p0 + q < p.P) {
+      const unsigned b0 = (b[0] >> q) & 1u;
+      if (i < p.n0 - 1 && b0 != ((b[2] >> q) & 1u)) mask |= 1;
+      if (j < p.n1 - 1 && b0 != ((b[1] >> q) & 1u)) mask |= 2;
+      if (k < p.n2 - 1 && b0 != ((b[0] >> (q + 1)) & 1u)) mask |= 4;
+      if (i < p.n0 - 1 && j < p.n1 - 1 && k < p.n2 - 1) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) cs |= (int)((b[c >> 1] >> (q + (c & 1))) & 1u) << c;   // corner c = 4 o0 + 2 o1 + o2
+      }
+    }
+    s.mask[q] = mask;
+    s.cases[q] = cs;
+    s.nv += __popc(mask);
+    s.nt += kNumTri[cs];
+    if (++k == p.n2) { k = 0; if (++j == p.n1) { j = 0; ++i; } }
+  }
+}
+
+// exclusive prefix over the block of (a, b), a < 16, b < 32 per thread: bit-sliced wave ballots, then the wave totals via LDS
+__device__ __forceinline__ void block_scan(int a, int b, int& a_ex, int& b_ex, int& a_tot, int& b_tot) {
+  __shared__ int wave_tot[2][kThreads / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  int ea = 0, eb = 0, ta = 0, tb = 0;
+#pragma unroll
+  for (int bit = 0; bit < 4; ++bit) {
+    const unsigned long long m = __ballot((a >> bit) & 1);
+    ea += __popcll(m & below) << bit;
+    ta += __popcll(m) << bit;
+  }
+#pragma unroll
+  for (int bit = 0; bit < 5; ++bit) {
+    const unsigned long long m = __ballot((b >> bit) & 1);
+    eb += __popcll(m & below) << bit;
+    tb += __popcll(m) << bit;
+  }
+  if (lane == 0) { wave_tot[0][w] = ta; wave_tot[1][w] = tb; }
+  __syncthreads();
+  a_tot = b_tot = 0;
+#pragma unroll
+  for (int v = 0; v < kThreads / 64; ++v) {
+    if (v < w) { ea += wave_tot[0][v]; eb += wave_tot[1][v]; }
+    a_tot += wave_tot[0][v];
+    b_tot += wave_tot[1][v];
+  }
+  a_ex = ea;
+  b_ex = eb;
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kThreads) void mc_count_kernel(const McParams p) {
+  const long long p0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPerThread;
+  Points s;
+  classify<kVec>(p, p0, s);
+  int v_ex, t_ex, v_tot, t_tot;
+  block_scan(s.nv, s.nt, v_ex, t_ex, v_tot, t_tot);
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    if (s.mask[q]) {
+      p.map[p0 + q] = (v_ex << 3) | s.mask[q];
+      v_ex += __popc(s.mask[q]);
+    }
+  }
+  if (threadIdx.x == 0) {
+    p.blk[blockIdx.x] = v_tot;
+    p.blk[p.nblocks + blockIdx.x] = t_tot;
+  }
+}
+
+// one block: exclusive int64 prefix of the per-block totals (vertices, triangles), and the two grand totals
+__global__ __launch_bounds__(kScanThreads) void mc_scan_kernel(const McParams p) {
+  __shared__ long long wave_tot[2][kScanThreads / 64];
+  const int nb = p.nblocks, per = (nb + kScanThreads - 1) / kScanThreads;
+  const int lo = min(nb, (int)threadIdx.x * per), hi = min(nb, lo + per);
+  long long sv = 0, st = 0;
+  for (int b = lo; b < hi; ++b) { sv += p.blk[b]; st += p.blk[nb + b]; }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  long long iv = sv, it = st;                                   // inclusive wave scan
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long uv = __shfl_up(iv, d), ut = __shfl_up(it, d);
+    if (lane >= d) { iv += uv; it += ut; }
+  }
+  if (lane == 63) { wave_tot[0][w] = iv; wave_tot[1][w] = it; }
+  __syncthreads();
+  long long bv = 0, bt = 0, tv = 0, tt = 0;
+  for (int v = 0; v < kScanThreads / 64; ++v) {
+    if (v < w) { bv += wave_tot[0][v]; bt += wave_tot[1][v]; }
+    tv += wave_tot[0][v];
+    tt += wave_tot[1][v];
+  }
+  long long ov = bv + iv - sv, ot = bt + it - st;
+  for (int b = lo; b < hi; ++b) {
+    p.off[b] = ov;
+    p.off[nb + b] = ot;
+    ov += p.blk[b];
+    ot += p.blk[nb + b];
+  }
+  if (threadIdx.x == 0) { p.counts[0] = tv; p.counts[1] = tt; }
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kThreads) void mc_emit_kernel(const McParams p) {
+  const long long p0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPerThread;
+  Points s;
+  classify<kVec>(p, p0, s);
+  int v_ex, t_ex, v_tot, t_tot;
+  block_scan(s.nv, s.nt, v_ex, t_ex, v_tot, t_tot);
+  long long vid = p.off[blockIdx.x] + v_ex;
+  long long tid = p.off[p.nblocks + blockIdx.x] + t_ex;
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    const float f0 = s.f[0][q];
+    const float f1[3] = {s.f[2][q], s.f[1][q], s.f[0][q + 1]};   // the far end of the edge along axis 0, 1, 2
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (s.mask[q] >> a & 1) {
+        const float t = (p.iso - f0) / (f1[a] - f0);
+        float x = (float)s.i[q], y = (float)s.j[q], z = (float)s.k[q];
+        if (a == 0) x = x + t; else if (a == 1) y = y + t; else z = z + t;
+        float* o = p.verts + vid * 3;
+        o[0] = x; o[1] = y; o[2] = z;
+        ++vid;
+      }
+    }
+    const int cs = s.cases[q], nt = kNumTri[cs];
+    for (int r = 0; r < nt; ++r) {
+      long long* o = p.tris + tid * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int e = kTriEdges[cs][3 * r + c];
+        const int a = e >> 2, u = (e >> 1) & 1, v = e & 1;
+        const long long qp = p0 + q + (a == 0 ? u * (long long)p.n2 + v
+                                     : a == 1 ? u * p.S + v
+                                              : u * p.S + v * (long long)p.n2);
+        const int m = p.map[qp];
+        o[c] = p.off[qp / kPointsPerBlock] + (m >> 3) + __popc(m & ((1 << a) - 1));
+      }
+      ++tid;
+    }
+  }
+}
+
+// shape check shared by the three entry points; fills the geometry of p
+int mc_shape(const char* what, int64_t n0, int64_t n1, int64_t n2, McParams& p) {
+  if (n0 < 2 || n1 < 2 || n2 < 2)
+    return fail(MF_E_INVALID, "%s: volume %lld x %lld x %lld (each side >= 2)", what, (long long)n0, (long long)n1, (long long)n2);
+  if (n0 > INT_MAX || n1 > INT_MAX || n2 > INT_MAX || n1 * n2 > INT_MAX || n0 * (n1 * n2) > INT_MAX)
+    return fail(MF_E_INVALID, "%s: volume %lld x %lld x %lld exceeds 2^31 - 1 points", what, (long long)n0, (long long)n1, (long long)n2);
+  p.n0 = (int)n0; p.n1 = (int)n1; p.n2 = (int)n2;
+  p.S = n1 * n2;
+  p.P = n0 * p.S;
+  p.nblocks = (int)((p.P + kPointsPerBlock - 1) / kPointsPerBlock);
+  return MF_OK;
+}
+
+// scratch: off int64 [2 nb] | blk int32 [2 nb] | map int32 [P]
+int64_t mc_scratch(const McParams& p) { return 16LL * p.nblocks + 8LL * p.nblocks + 4LL * p.P; }
+
+void mc_bind(McParams& p, void* scratch) {
+  char* base = static_cast<char*>(scratch);
+  p.off = reinterpret_cast<long long*>(base);
+  p.blk = reinterpret_cast<int*>(base + 16LL * p.nblocks);
+  p.map = reinterpret_cast<int*>(base + 24LL * p.nblocks);
+}
+
+bool vec_rows(const McParams& p) { return p.n2 % 4 == 0 && reinterpret_cast<uintptr_t>(p.vol) % 16 == 0; }
+
+}  // namespace mc
+}  // namespace mf
+
+extern "C" int64_t mf_mc_scratch_bytes(int64_t n0, int64_t n1, int64_t n2) {
+  McParams p{};
+  const int rc = mc_shape("mf_mc_scratch_bytes", n0, n1, n2, p);
+  return rc != MF_OK ? rc : mc_scratch(p);
+}
+
+extern "C" int32_t mf_mc_count(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
+                               void* scratch, int64_t* counts, void* stream) {
+  McParams p{};
+  const int rc = mc_shape("mf_mc_count", n0, n1, n2, p);
+  if (rc != MF_OK) return rc;
+  if (!vol || !scratch || !counts) return fail(MF_E_INVALID, "mf_mc_count: null argument");
+  p.vol = vol; p.iso = iso; p.clamp_zero = clamp_zero ? 1 : 0;
+  p.counts = reinterpret_cast<long long*>(counts);
+  mc_bind(p, scratch);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec_rows(p)) hipLaunchKernelGGL(mc_count_kernel<true>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
+  else hipLaunchKernelGGL(mc_count_kernel<false>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
+  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, p);
+  return check_launch("mf_mc_count");
+}
+
+extern "C" int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
+                              const void* scratch, float* verts, int64_t* tris, void* stream) {
+  McParams p{};
+  const int rc = mc_shape("mf_mc_emit", n0, n1, n2, p);
+  if (rc != MF_OK) return rc;
+  if (!vol || !scratch) return fail(MF_E_INVALID, "mf_mc_emit: null argument");
+  p.vol = vol; p.iso = iso; p.clamp_zero = clamp_zero ? 1 : 0;
+  p.verts = verts;
+  p.tris = reinterpret_cast<long long*>(tris);
+  mc_bind(p, const_cast<void*>(scratch));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec_rows(p)) hipLaunchKernelGGL(mc_emit_kernel<true>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
+  else hipLaunchKernelGGL(mc_emit_kernel<false>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
+  return check_launch("mf_mc_emit");
+}
