@@ -58,8 +58,6 @@ MF_HD int bwd_groups(const NetLayout& L, int layer) {
   return layer == 0 ? L.NK : (layer == 1 ? 2 * (L.NK + 1) : 2 * L.NK);
 }
 
-int device_cus();   // mf_forward.hip
-
 // ------------------------------------------------------------------ packing (transposed fragment stream)
 struct BwdPackJob {
   const float* W[MF_MAX_LAYERS + 3];   // forward weight feeding backward layer i
@@ -376,8 +374,7 @@ extern "C" int32_t mf_nerf_backward_x(const mf_nerf_desc* d, const void* packed_
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nerf_backward: cannot reserve %zu bytes of LDS", lds);
-  const long long ntiles = (P + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((P + kTile - 1) / kTile);
   hipLaunchKernelGGL(nerf_backward_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_nerf_backward");
 }

@@ -20,8 +20,6 @@
 
 namespace mf {
 
-int device_cus();   // mf_forward.hip
-
 namespace bf {
 
 // packed buffer: [resident: zeros 32 | rgb.0.weight 3 x 128 (natural order) | sigma.weight 256, 1 KiB-aligned]
@@ -405,8 +403,7 @@ extern "C" int32_t mf_nerf_backward3(const mf_nerf_desc* d, const void* packed_b
   p.P = P; p.stride = stride; p.g_out = g_out; p.acts = acts; p.rgbsigma = rgbsigma; p.gpre = gpre; p.ghead = ghead;
   uint32_t lds = bf::kB3ResBytes;
   p.ring_off = lds; p.buf_bytes = 32 * kGroupBytes; lds += 3 * p.buf_bytes;
-  const long long ntiles = (P + 127) / 128;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((P + 127) / 128);
   void (*kern)(const bf::Bwd3Params) = mask ? bf::nerf_backward_kernel_x3<true> : bf::nerf_backward_kernel_x3<false>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nerf_backward3: cannot reserve %u bytes of LDS", lds);

@@ -284,8 +284,7 @@ static int32_t nerf_forward_launch(const char* who, const mf_nerf_desc* d, const
   const void* fn = dump ? reinterpret_cast<const void*>(nerf_forward_kernel<true>) : reinterpret_cast<const void*>(nerf_forward_kernel<false>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-  const long long ntiles = (B + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((B + kTile - 1) / kTile);
   if (dump) hipLaunchKernelGGL(nerf_forward_kernel<true>, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   else hipLaunchKernelGGL(nerf_forward_kernel<false>, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch(who);
@@ -318,17 +317,9 @@ extern "C" int32_t mf_nof_forward(const mf_nof_desc* d, const void* packed, cons
   void (*kern)(NofFwdParams) = p.net.L.NK == 16 ? nof_forward_kernel<16> : nof_forward_kernel<8>;     // W = 256: the bare NoF() default
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nof_forward: cannot reserve %zu bytes of LDS", lds);
-  const long long ntiles = (B + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((B + kTile - 1) / kTile);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_nof_forward");
-}
-
-static void emb_to_params(const mf_embedding& e, EmbParams& o) {
-  for (int k = 0; k < 16; ++k) {
-    o.freq[k] = k < e.n_freqs ? e.freq[k] : 0.f;
-    o.weight[k] = k < e.n_freqs ? e.weight[k] : 0.f;
-  }
 }
 
 namespace mf {
@@ -381,7 +372,7 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   p.nerf.packed = static_cast<const char*>(nerf_packed);
   p.nerf.res_lds = lds; lds += (uint32_t)p.nerf.L.res_bytes;
   int max_groups = p.nerf.L.max_groups;
-  emb_to_params(*emb_xyz, p.exyz);
+  emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
   if (nof) {
     if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_sigma: NoF arguments missing");
     if (!nof_layout(*nof, p.nof.L)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NoF configuration");
@@ -390,8 +381,8 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
     p.nof.packed = static_cast<const char*>(nof_packed);
     p.nof.res_lds = lds; lds += (uint32_t)p.nof.L.res_bytes;
     if (p.nof.L.max_groups > max_groups) max_groups = p.nof.L.max_groups;
-    emb_to_params(*nof_emb_xyz, p.nxyz);
-    emb_to_params(*nof_emb_ind, p.nind);
+    emb_table(*nof_emb_xyz, p.nxyz.freq, p.nxyz.weight);
+    emb_table(*nof_emb_ind, p.nind.freq, p.nind.weight);
   }
   p.xyz = xyz; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.sigma = sigma; p.canon = canon;
   p.ring_off = lds;
@@ -400,8 +391,7 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   const void* fn = nof ? reinterpret_cast<const void*>(points_kernel<true>) : reinterpret_cast<const void*>(points_kernel<false>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_points_sigma: cannot reserve %u bytes of LDS", lds);
-  const long long ntiles = (B + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((B + kTile - 1) / kTile);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (nof) hipLaunchKernelGGL(points_kernel<true>, dim3(grid), dim3(kThreads), lds, st, p);
   else hipLaunchKernelGGL(points_kernel<false>, dim3(grid), dim3(kThreads), lds, st, p);

@@ -24,4 +24,78 @@ inline int check_launch(const char* what) {
   return MF_OK;
 }
 
+int device_cus();   // mf_forward.hip
+
+// grid of a persistent launch over `work` workgroup-sized items: at most one workgroup per CU
+inline int persistent_grid(long long work) {
+  const long long cus = device_cus();
+  return (int)(work < cus ? work : cus);
+}
+
+// an embedding's frequencies and weights as 16-entry tables, 0 beyond n_freqs; returns: the frequencies are exactly 2^k
+inline bool emb_table(const mf_embedding& e, float* freq, float* weight) {
+  bool pow2 = true;
+  for (int k = 0; k < 16; ++k) {
+    freq[k] = k < e.n_freqs ? e.freq[k] : 0.f;
+    weight[k] = k < e.n_freqs ? e.weight[k] : 0.f;
+    if (k < e.n_freqs && e.freq[k] != (float)(1 << k)) pow2 = false;
+  }
+  return pow2;
+}
+
+// ---- launch planning of the render passes (mf_render.hip: fp32, mf_render_bf16.hip: bf16 / bf16x3) ----
+constexpr uint32_t kRenderLdsCap = 160 * 1024;   // LDS of one render workgroup
+
+// Rays per group of a render pass whose workgroup holds `lds` bytes before its 20 bytes per staged sample (float4 rgb-sigma,
+// float depth): the smallest G with G*S a multiple of the tile (`tile` samples), capped by the LDS left; no exact fit: as many
+// rays as reduce the padding waste.  Then several such ray sets per group (up to 8): the composite phase between two groups
+// keeps at most one wave per ray busy and costs two workgroup barriers (~4 k cycles per 128-sample tile at G = 2 in the fp32
+// pass: tools/timeline.py), so it should come once per several tiles -- as long as the CUs' shares stay what they were (same
+// makespan in rays).
+inline int plan_ray_groups(long long n_rays, int S, int tile, uint32_t lds, int& G, long long& n_groups) {
+  const int max_samples = lds < kRenderLdsCap ? (int)((kRenderLdsCap - lds) / 20) : 0;
+  if (S > max_samples) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
+  G = 1;
+  while ((G * S) % tile != 0 && (G + 1) * S <= max_samples && G < 64) ++G;
+  if ((G * S) % tile != 0) {
+    int best = 1; double best_eff = 0;
+    for (int g = 1; g * S <= max_samples && g <= 64; ++g) {
+      const int tiles = (g * S + tile - 1) / tile;
+      const double eff = (double)(g * S) / (tiles * tile);
+      if (eff > best_eff + 1e-9) { best_eff = eff; best = g; }
+    }
+    G = best;
+  }
+  const long long cus = device_cus();
+  auto makespan = [&](long long g) { const long long groups = (n_rays + g - 1) / g; return (groups + cus - 1) / cus * g; };
+  const long long base = makespan(G);
+  int sets = 1;
+  for (int c = 2; c <= 8; ++c)
+    if ((long long)G * c * S <= max_samples && (long long)G * c <= 64 && makespan((long long)G * c) <= base) sets = c;
+  G *= sets;
+  n_groups = (n_rays + G - 1) / G;
+  return MF_OK;
+}
+
+// the ReLU bit rows of a render pass's NeRF dump (n_trunk = D + 1 layers): beside dump_acts, D + 2 rows of 8 words
+inline int check_dump_mask(const mf_render_args* a, int n_trunk) {
+  if (a->dump_mask && (!a->dump_acts || a->dump_mask_stride < (int64_t)(n_trunk + 1) * 8))
+    return fail(MF_E_INVALID, "mf_render_pass: dump_mask needs dump_acts and dump_mask_stride >= 8 (D + 2) words");
+  return MF_OK;
+}
+
+// dump_nof_plane: the plane each NoF chain step of the pass writes, a permutation of 0 .. steps - 1 -> `pack`, 3 bits per step
+inline int nof_plane_pack(const mf_render_args* a, uint32_t& pack) {
+  const int nsteps = 1 + ((a->flags & MF_F_CHAIN_LOCAL) ? 1 : 0) + ((a->flags & MF_F_CHAIN_GLOBAL) ? 3 : 0);
+  uint32_t seen = 0;
+  pack = 0;
+  for (int k = 0; k < nsteps; ++k) {
+    const int pl = a->dump_nof_plane[k];
+    if (pl < 0 || pl >= nsteps || ((seen >> pl) & 1u)) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_plane must be a permutation of 0..%d", nsteps - 1);
+    seen |= 1u << pl;
+    pack |= (uint32_t)pl << (3 * k);
+  }
+  return MF_OK;
+}
+
 }  // namespace mf

@@ -21,8 +21,6 @@
 
 namespace mf {
 
-int device_cus();   // mf_forward.hip
-
 constexpr int kNofW = 128;
 constexpr int kNofEmbCols = 80;       // embedded input row of the dump: [xyz 33 | ind 33 | 0 x 14]
 constexpr int kNofHeadPad = 16;       // head slot of the dump / gradient rows: T (9 | 3), zero padded
@@ -356,13 +354,6 @@ __global__ __launch_bounds__(kThreads, 2) void nof_backward_kernel(NofBwdParams 
   wait_vm0();
 }
 
-static void emb_params(const mf_embedding& e, EmbParams& o) {
-  for (int k = 0; k < 16; ++k) {
-    o.freq[k] = k < e.n_freqs ? e.freq[k] : 0.f;
-    o.weight[k] = k < e.n_freqs ? e.weight[k] : 0.f;
-  }
-}
-
 }  // namespace mf
 
 using namespace mf;
@@ -382,16 +373,15 @@ extern "C" int32_t mf_nof_points_dump(const mf_nof_desc* d, const void* packed, 
   if (P == 0) return MF_OK;
   p.net.packed = static_cast<const char*>(packed);
   p.net.res_lds = 0;
-  emb_params(*emb_xyz, p.exyz);
-  emb_params(*emb_ind, p.eind);
+  emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
+  emb_table(*emb_ind, p.eind.freq, p.eind.weight);
   p.pts = pts; p.inputs = nullptr; p.in_stride = 0; p.ind = ind; p.ind_stride = ind_stride; p.P = P; p.S = S; p.out = out; p.acts = acts; p.stride = stride; p.emb = emb;
   p.ring_off = (uint32_t)p.net.L.res_bytes;
   p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_points_dump_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nof_points_dump: cannot reserve %zu bytes of LDS", lds);
-  const long long ntiles = (P + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((P + kTile - 1) / kTile);
   hipLaunchKernelGGL(nof_points_dump_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_nof_points_dump");
 }
@@ -414,8 +404,7 @@ extern "C" int32_t mf_nof_forward_dump(const mf_nof_desc* d, const void* packed,
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_points_dump_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nof_forward_dump: cannot reserve %zu bytes of LDS", lds);
-  const long long ntiles = (B + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((B + kTile - 1) / kTile);
   hipLaunchKernelGGL(nof_points_dump_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_nof_forward_dump");
 }
@@ -467,7 +456,7 @@ extern "C" int32_t mf_nof_backward(const mf_nof_desc* d, const void* packed_bwd,
   if (P == 0) return MF_OK;
   p.net.packed = static_cast<const char*>(packed_bwd);
   p.net.res_lds = 0;
-  emb_params(*emb_xyz, p.exyz);
+  emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
   p.D = d->D; p.P = P; p.stride = stride;
   p.pts = pts; p.acts = acts; p.g_out = g_out; p.gpre = gpre; p.g_pts = g_pts;
   p.ring_off = (uint32_t)p.net.L.res_bytes;
@@ -477,8 +466,7 @@ extern "C" int32_t mf_nof_backward(const mf_nof_desc* d, const void* packed_bwd,
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_nof_backward: cannot reserve %zu bytes of LDS", lds);
-  const long long ntiles = (P + kTile - 1) / kTile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((P + kTile - 1) / kTile);
   hipLaunchKernelGGL(nof_backward_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_nof_backward");
 }

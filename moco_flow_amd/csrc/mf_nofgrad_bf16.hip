@@ -21,8 +21,6 @@
 
 namespace mf {
 
-int device_cus();   // mf_forward.hip
-
 namespace bf {
 
 constexpr int kNW = 128;                       // the NoF's width

@@ -322,14 +322,6 @@ __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
 #endif
 }
 
-static void to_table(const mf_embedding& e, float* o) {
-  for (int k = 0; k < 16; ++k) {
-    o[k] = k < e.n_freqs ? e.freq[k] : 0.f;
-    o[16 + k] = k < e.n_freqs ? e.weight[k] : 0.f;
-  }
-}
-
-int device_cus();   // mf_forward.hip
 int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only);   // mf_render_bf16.hip
 int64_t render_workspace_bytes_bf16(const mf_render_args* a);
 
@@ -394,8 +386,8 @@ static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_
   p.S = a->n_samples; p.z_vals = a->z_vals; p.z_steps = a->z_steps; p.use_disp = a->use_disp;
   p.noise = a->noise; p.activation = a->activation; p.flags = a->flags;
   p.nerf.packed = static_cast<const char*>(a->nerf_packed);
-  to_table(a->emb_xyz, p.emb_par[0]);
-  to_table(a->emb_extra, p.emb_par[1]);
+  emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
+  emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16);
   p.extra_type = a->nerf->extra_feat_type;
   p.rgb = a->rgb; p.depth = a->depth; p.opacity = a->opacity; p.weights = a->weights; p.alphas = a->alphas;
   p.disp_local = a->disp_local; p.disp_global = a->disp_global;
@@ -420,8 +412,8 @@ static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_
     if (a->nof_emb_xyz.in_channels != 3 || a->nof_emb_xyz.n_freqs > 5 || a->nof_emb_ind.in_channels != 1 ||
         a->nof_emb_ind.n_freqs > 16)
       return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
-    to_table(a->nof_emb_xyz, p.emb_par[2]);
-    to_table(a->nof_emb_ind, p.emb_par[3]);
+    emb_table(a->nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16);
+    emb_table(a->nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16);
   }
   if (bf16) return render_pass_bf16(a, static_cast<hipStream_t>(stream), prepare_only);     // validated above; own layout / launch
   if (prepare_only) return MF_OK;
@@ -430,50 +422,18 @@ static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_
   p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
   lds += 3 * p.buf_bytes;
 
-  // rays per group: smallest G with G*S a multiple of the 128-sample tile, capped by the LDS left
-  const uint32_t lds_cap = 160 * 1024;
-  const int max_samples = (int)((lds_cap - lds) / 20);
-  const int S = a->n_samples;
-  if (S > max_samples) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
-  int G = 1;
-  while ((G * S) % kTile != 0 && (G + 1) * S <= max_samples && G < 64) ++G;
-  if ((G * S) % kTile != 0) {           // no exact fit: take as many rays as reduce the padding waste
-    int best = 1; double best_eff = 0;
-    for (int g = 1; g * S <= max_samples && g <= 64; ++g) {
-      const int tiles = (g * S + kTile - 1) / kTile;
-      const double eff = (double)(g * S) / (tiles * kTile);
-      if (eff > best_eff + 1e-9) { best_eff = eff; best = g; }
-    }
-    G = best;
-  }
-  // Several such ray sets per group (up to 8): the composite phase between two groups keeps at most G of the 8 waves
-  // busy and costs two workgroup barriers (~4 k cycles per 128-sample tile at G = 2: tools/timeline.py), so it should
-  // come once per several tiles -- as long as the CUs' shares stay what they were (same makespan in rays).
-  {
-    const long long cus = device_cus();
-    auto makespan = [&](long long g) { const long long groups = (a->n_rays + g - 1) / g; return (groups + cus - 1) / cus * g; };
-    const long long base = makespan(G);
-    int best = 1;
-    for (int c = 2; c <= 8; ++c)
-      if ((long long)G * c * S <= max_samples && (long long)G * c <= 64 && makespan((long long)G * c) <= base) best = c;
-    G *= best;
-  }
-  p.G = G;
-  p.n_groups = (a->n_rays + G - 1) / G;
-  p.sbuf_off = lds; lds += (uint32_t)(G * S) * 16;
-  p.zbuf_off = lds; lds += (uint32_t)(G * S) * 4;
+  if (int e = plan_ray_groups(a->n_rays, a->n_samples, kTile, lds, p.G, p.n_groups)) return e;
+  p.sbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 16;
+  p.zbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 4;
   lds = (lds + 15u) & ~15u;
 
-  const int grid = (int)(p.n_groups < device_cus() ? p.n_groups : device_cus());
+  const int grid = persistent_grid(p.n_groups);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a->dump_acts && a->dump_stride < (int64_t)p.nerf.L.n_trunk * p.nerf.L.W + p.nerf.L.W / 2)
     return fail(MF_E_INVALID, "mf_render_pass: dump_stride %lld too small", (long long)a->dump_stride);
   p.dump_acts = a->dump_acts; p.dump_stride = a->dump_stride; p.dump_rgbsigma = a->dump_rgbsigma; p.dump_xyz = a->dump_xyz;
-  if (a->dump_mask) {
-    if (!a->dump_acts || a->dump_mask_stride < (int64_t)(p.nerf.L.n_trunk + 1) * 8)
-      return fail(MF_E_INVALID, "mf_render_pass: dump_mask needs dump_acts and dump_mask_stride >= 8 (D + 2) words");
-    p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
-  }
+  if (int e = check_dump_mask(a, p.nerf.L.n_trunk)) return e;
+  p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
   if (a->dump_nof_acts) {
     if (!moco || !a->dump_nof_emb || !a->dump_nof_out) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_acts needs NoF models, dump_nof_emb and dump_nof_out");
     if (a->dump_nof_stride < (int64_t)p.bw.L.n_trunk * p.bw.L.W + 16 || (a->dump_nof_stride & 3))
@@ -481,18 +441,9 @@ static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_
     if (a->nof_fw && (p.fw.L.n_trunk != p.bw.L.n_trunk || p.fw.L.W != p.bw.L.W))
       return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF dumps need bw and fw of the same depth and width");
     if (a->precision != MF_PREC_F32) return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF dumps are fp32 only");
+    if (int e = nof_plane_pack(a, p.nof_plane_pack)) return e;
   }
   p.dump_nof_acts = a->dump_nof_acts; p.dump_nof_stride = a->dump_nof_stride; p.dump_nof_emb = a->dump_nof_emb; p.dump_nof_out = a->dump_nof_out;
-  if (a->dump_nof_acts) {
-    const int nsteps = 1 + ((a->flags & MF_F_CHAIN_LOCAL) ? 1 : 0) + ((a->flags & MF_F_CHAIN_GLOBAL) ? 3 : 0);
-    uint32_t seen = 0;
-    for (int k = 0; k < nsteps; ++k) {
-      const int pl = a->dump_nof_plane[k];
-      if (pl < 0 || pl >= nsteps || ((seen >> pl) & 1u)) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_plane must be a permutation of 0..%d", nsteps - 1);
-      seen |= 1u << pl;
-      p.nof_plane_pack |= (uint32_t)pl << (3 * k);
-    }
-  }
   void (*kern)(RenderParams) =
       dump ? (moco ? render_kernel<true, true> : render_kernel<false, true>)
            : (moco ? render_kernel<true, false> : render_kernel<false, false>);

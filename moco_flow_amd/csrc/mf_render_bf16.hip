@@ -4,11 +4,9 @@
 // written to HBM -- on the 32x32x16 bf16 core of mf_bf16.hpp: a wave owns 32 samples, a workgroup tile is 256
 // samples, a weight panel is one 32-row tile of a layer.
 #include <cstddef>
-#include <cstdlib>
 #include <type_traits>
 
 #include "mf_bf16.hpp"
-#include "mf_bf16_2b.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 
@@ -65,7 +63,6 @@ struct RayBiasParams {
 };
 
 constexpr int kRbEntries = 8;       // entries (rays) per workgroup of nof_raybias_kernel
-constexpr int kFastBlocksDefault = 1; // column blocks per wave of the fast mode's render kernels (see render_pass_bf16)
 
 // grid (ceil(n_entries / 8), n_combos), 256 threads.  Thread (embedded layer, row) first requests its 33 index-column
 // weights + bias (coalesced: the packed block is [layer][column][row]); while they travel, threads (entry e, frequency k)
@@ -475,186 +472,6 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void render_kernel
 #endif
 }
 
-// The fast mode with two column blocks per wave (mf_bf16_2b.hpp): 4 waves, one per SIMD, 64 samples each -- 256-sample tiles as
-// render_kernel_bf16<*, false>, the same panel program, the same arithmetic (bit-identical outputs); every weight fragment read
-// from LDS feeds two MFMAs.  The per-sample code of a tile runs once per block b: sample slot wave * 64 + 32 b + (lane & 31).
-template <bool MOCO>
-__global__ __launch_bounds__(256, 1) void render_kernel_bf16_2b(const Params p) {
-  constexpr int NW = kWaves2;
-  constexpr int TILE = NW * kBlockSamples;
-  const Lane id;
-  load_resident<NW>(p.nerf, id);
-  if (MOCO) {
-    load_resident<NW>(p.bw, id);
-    if (p.flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL)) load_resident<NW>(p.fw, id);
-  }
-  if (threadIdx.x < 128) {
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Params, emb_par);
-    *(float*)(smem + p.par_off + threadIdx.x * 4) = ((const __attribute__((address_space(4))) float*)ka)[threadIdx.x];
-  }
-  const uint32_t par_nerf_xyz = p.par_off, par_nerf_ext = p.par_off + 128, par_nof_xyz = p.par_off + 256;
-  Stream2 st;
-  st.tl.start(p.alphas, id);
-  Carry carry;
-  const Next prog_first = MOCO ? first_of<8, kKsNofXyz, true, kNofTpp0, 2, kNofTppH, kNofTppS>(p.bw) : first_of<16, kKsNerfXyz, false, kNerfTpp0>(p.nerf);
-  int seq = 0;
-  if (MOCO) {
-    const long long g0 = blockIdx.x;
-    const int nr0 = group_rays(p.n_rays, g0, p.G);
-    int f0, n0;
-    tile_rays<TILE>(0, nr0, p.S, f0, n0);
-    stage_raybias<NW>(p, g0 * p.G + f0, n0, 0, p.rb_off, id);
-  }
-  if (MOCO) start_program<8, kKsNofXyz, true, kNofTpp0, 2, kNofTppH, kNofTppS>(p.bw, st, carry, p.ring_off, p.buf_bytes, id);
-  else start_program<16, kKsNerfXyz, false, kNerfTpp0>(p.nerf, st, carry, p.ring_off, p.buf_bytes, id);
-
-  const int S = p.S;
-  const bool sigma_only = p.flags & MF_F_SIGMA_ONLY;
-  float4* sbuf = reinterpret_cast<float4*>(smem + p.sbuf_off);
-  float* zbuf = reinterpret_cast<float*>(smem + p.zbuf_off);
-
-  for (long long group = blockIdx.x; group < p.n_groups; group += gridDim.x) {
-    const long long ray0 = group * p.G;
-    const int nr = group_rays(p.n_rays, group, p.G);
-    const int nsamp = nr * S;
-    const int ntiles = (nsamp + TILE - 1) / TILE;
-
-    for (int tile = 0; tile < ntiles; ++tile) {
-      st.tl.stamp(1, id);
-      int ln;
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-      int srel[2], rr[2], si[2];
-      bool valid[2];
-      const float* rp[2];
-      float z[2], x[2][3], xin[2][3];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        srel[b] = tile * TILE + id.wave * kBlockSamples + b * kWaveSamples + (ln & 31);
-        valid[b] = srel[b] < nsamp;
-        const int sl = valid[b] ? srel[b] : nsamp - 1;
-        rr[b] = sl / S;
-        si[b] = sl - rr[b] * S;
-        const long long ray = ray0 + rr[b];
-        rp[b] = p.rays + ray * p.ray_stride;
-        const float o[3] = {rp[b][0], rp[b][1], rp[b][2]};
-        const float d[3] = {rp[b][3], rp[b][4], rp[b][5]};
-        if (p.z_vals) {
-          z[b] = p.z_vals[ray * S + si[b]];
-        } else {
-          const float nearv = rp[b][6], farv = rp[b][7], t = p.z_steps[si[b]];
-          if (!p.use_disp) z[b] = nearv * (1.f - t) + farv * t;                    // rendering.py:247
-          else z[b] = 1.f / (1.f / nearv * (1.f - t) + 1.f / farv * t);            // rendering.py:249
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { x[b][c] = o[c] + d[c] * z[b]; xin[b][c] = x[b][c]; }      // rendering.py:262-263
-      }
-      st.tl.stamp(2, id);
-      if (MOCO) {
-        // chain program (rendering.py:270-282), as render_kernel_bf16
-        const bool loc = p.flags & MF_F_CHAIN_LOCAL, glob = p.flags & MF_F_CHAIN_GLOBAL;
-        const int nsteps = 1 + (loc ? 1 : 0) + (glob ? 3 : 0);
-        float canon[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, cur[2][3];
-        float dl[2] = {0.f, 0.f}, dg[2] = {0.f, 0.f};
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) cur[b][c] = x[b][c];
-        for (int step = 0; step < nsteps; ++step) {
-          const int role = step;
-          const bool use_fw = (role == 1 || role == 2 || role == 4);
-          const Net net = use_fw ? p.fw : p.bw;
-          int tf, tn;
-          tile_rays<TILE>(tile, nr, S, tf, tn);
-          const uint32_t rbase = p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes;
-          const LdsRayBias rb[2] = {LdsRayBias{rbase + (uint32_t)(rr[0] - tf) * (uint32_t)(p.rb_layers * 512)},
-                                    LdsRayBias{rbase + (uint32_t)(rr[1] - tf) * (uint32_t)(p.rb_layers * 512)}};
-          ++seq;
-          if (role == 1 || role == 2) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-              for (int c = 0; c < 3; ++c) cur[b][c] = canon[b][c];
-          }
-          const bool last = step == nsteps - 1;
-          const bool next_fw = (role + 1 == 1 || role + 1 == 2 || role + 1 == 4);
-          const Next follow = last ? first_of<16, kKsNerfXyz, false, kNerfTpp0>(p.nerf)
-                                   : first_of<8, kKsNofXyz, true, kNofTpp0, 2, kNofTppH, kNofTppS>(next_fw ? p.fw : p.bw);
-          u32x4 nhi[2][kKsNofXyz], nlo[2][kKsNofXyz];
-          float out[2][3];
-          nof_embed<true>(nhi[0], nlo[0], cur[0], par_nof_xyz, id.h, p.pow2 & 4);
-          nof_embed<true>(nhi[1], nlo[1], cur[1], par_nof_xyz, id.h, p.pow2 & 4);
-          auto stage_next = [&] {
-            if (!last) stage_raybias<NW>(p, ray0 + tf, tn, role + 1 == 4 ? 1 : role + 1, p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes, id);
-          };
-          nof_eval2(net, nhi, nlo, cur, st, carry, id, follow, out, rb, stage_next);
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            if (role == 0) { canon[b][0] = out[b][0]; canon[b][1] = out[b][1]; canon[b][2] = out[b][2]; }
-            if (role == 1) dl[b] = (fabsf(x[b][0] - out[b][0]) + fabsf(x[b][1] - out[b][1]) + fabsf(x[b][2] - out[b][2])) / 3.f;
-            if (role == 4) dg[b] = (fabsf(x[b][0] - out[b][0]) + fabsf(x[b][1] - out[b][1]) + fabsf(x[b][2] - out[b][2])) / 3.f;
-            cur[b][0] = out[b][0]; cur[b][1] = out[b][1]; cur[b][2] = out[b][2];
-          }
-        }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          xin[b][0] = canon[b][0]; xin[b][1] = canon[b][1]; xin[b][2] = canon[b][2];
-          if (valid[b] && id.h == 0) {
-            const long long idx = (ray0 + rr[b]) * S + si[b];
-            if (loc && p.disp_local) p.disp_local[idx] = dl[b];
-            if (glob && p.disp_global) p.disp_global[idx] = dg[b];
-          }
-        }
-        // rows of the NEXT tile's first evaluation (see render_kernel_bf16)
-        const bool more = tile + 1 < ntiles;
-        const long long ng = more ? group : group + gridDim.x;
-        if (ng < p.n_groups) {
-          const int nnr = group_rays(p.n_rays, ng, p.G);
-          int nf, nn;
-          tile_rays<TILE>(more ? tile + 1 : 0, nnr, S, nf, nn);
-          stage_raybias<NW>(p, ng * p.G + nf, nn, 0, p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes, id);
-        }
-      }
-      st.tl.stamp(3, id);
-#pragma unroll
-      for (int b = 0; b < 2; ++b)          // (depth to LDS now, carrying the NaN poison: see render_kernel_bf16)
-        if (valid[b] && id.h == 0) zbuf[srel[b]] = z[b] + (xin[b][0] + xin[b][1] + xin[b][2]) * 0.f;
-      float sigma[2], rgb[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-      u32x4 xe[2][kKsNerfXyz];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        float embx[B2Xyz10::SLOTS];
-        emb_eval<3, 10, true>(embx, xin[b], par_nerf_xyz, id.h, p.pow2 & 1);
-        pack_operands<kKsNerfXyz>(embx, B2Xyz10::SLOTS, xe[b]);
-      }
-      auto make_extra = [&](int b, u32x4 (&eo)[kKsExtraMax]) {
-        float ext[8 * kKsExtraMax];
-#pragma unroll
-        for (int e = 0; e < 8 * kKsExtraMax; ++e) ext[e] = 0.f;
-        const float* q = b ? rp[1] : rp[0];
-        if (p.extra_type == MF_EXTRA_DIR) {
-          const float dd[3] = {q[3], q[4], q[5]};
-          emb_eval<3, 4, true>(ext, dd, par_nerf_ext, id.h, p.pow2 & 2);                         // rendering.py:138-142
-        } else if (p.extra_type == MF_EXTRA_IND) {
-          const float iv[1] = {q[8]};
-          emb_eval<1, 2, true>(ext, iv, par_nerf_ext, id.h, p.pow2 & 2);                         // rendering.py:133-137
-        }
-        pack_operands<kKsExtraMax>(ext, 8 * kKsExtraMax, eo);
-      };
-      st.tl.stamp(4, id);
-      nerf_eval2(p.nerf, xe, make_extra, sigma_only, st, carry, id, prog_first, sigma, rgb);
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-        if (valid[b] && id.h == 0) sbuf[srel[b]] = make_float4(rgb[b][0], rgb[b][1], rgb[b][2], sigma[b]);
-      st.tl.stamp(5, id);
-    }
-    __syncthreads();
-    composite_group<NW>(p, id, ray0, nr, S, sigma_only, sbuf, zbuf);
-    __syncthreads();
-  }
-  wait_vm0();
-}
-
 // sigma (and the canonical position) of free points in bf16 mode: the lattice / SMPL-point query of mf_forward.hip's
 // points_kernel (trainer_moco_flow.py:146-187, 500-526) on the 32x32x16 core -- xyz -> [bw NoF(ind)] -> encode -> NeRF
 // trunk -> sigma, 256 points per workgroup tile, nothing else written.
@@ -760,16 +577,6 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void points_kernel
   wait_vm0();
 }
 
-static bool emb_table(const mf_embedding& e, float* dst) {      // returns: frequencies are exactly 2^k
-  bool pow2 = true;
-  for (int k = 0; k < 16; ++k) {
-    dst[k] = k < e.n_freqs ? e.freq[k] : 0.f;
-    dst[16 + k] = k < e.n_freqs ? e.weight[k] : 0.f;
-    if (k < e.n_freqs && e.freq[k] != (float)(1 << k)) pow2 = false;
-  }
-  return pow2;
-}
-
 // combination c of a ray-bias table: network (packed buffer + layout) and the index column it reads
 // largest panel of a network in groups when its trunk tiles stream several per panel (the fast mode's <TPP0, TPPH, TPPS>:
 // layer 0, hidden-only layers, skip layers; the NoF's head / the NeRF's extra_encoding tiles are one panel each)
@@ -793,9 +600,20 @@ static void raybias_combo(RayBiasParams& r, int c, const void* packed, const Net
   r.col[c] = col;
 }
 
-}  // namespace bf
+// a network of a pass: its packed buffer, its resident block at LDS offset `lds` (advanced past the block), depth D, aux steps
+static Net net_at(const NetLayout& L, const void* packed, int D, int aux, uint32_t& lds) {
+  Net n;
+  n.packed = static_cast<const char*>(packed);
+  n.res_lds = lds;
+  n.res_bytes = (uint32_t)L.res_bytes;
+  n.D = D;
+  n.emb_mask = L.emb_mask;
+  n.aux = aux;
+  lds += (uint32_t)L.res_bytes;
+  return n;
+}
 
-int device_cus();   // mf_forward.hip
+}  // namespace bf
 
 // combinations (network, index value) and embedded layers per network of a bf16 pass with NoF; 0 combos = no table
 static void raybias_shape(const mf_render_args* a, int& combos, int& layers) {
@@ -826,35 +644,24 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
   p.S = a->n_samples; p.z_vals = a->z_vals; p.z_steps = a->z_steps; p.use_disp = a->use_disp;
   p.noise = a->noise; p.activation = a->activation; p.flags = a->flags;
   p.extra_type = a->nerf->extra_feat_type;
-  p.pow2 = (emb_table(a->emb_xyz, p.emb_par[0]) ? 1 : 0) | (emb_table(a->emb_extra, p.emb_par[1]) ? 2 : 0);
+  p.pow2 = (emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16) ? 1 : 0) | (emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16) ? 2 : 0);
   p.rgb = a->rgb; p.depth = a->depth; p.opacity = a->opacity; p.weights = a->weights; p.alphas = a->alphas;
   p.disp_local = a->disp_local; p.disp_global = a->disp_global;
 
   const int tile_samples = x3 ? 4 * bf::kWaveSamples : bf::kTile;      // x3: 4 waves per workgroup
   uint32_t lds = 0;
-  auto net_of = [&](const NetLayout& L, const void* packed, int D, int aux) {
-    Net n;
-    n.packed = static_cast<const char*>(packed);
-    n.res_lds = lds;
-    n.res_bytes = (uint32_t)L.res_bytes;
-    n.D = D;
-    n.emb_mask = L.emb_mask;
-    n.aux = aux;
-    lds += (uint32_t)L.res_bytes;
-    return n;
-  };
-  p.nerf = net_of(Ln, a->nerf_packed, Ln.n_trunk - 1, Ln.extra_steps);
+  p.nerf = net_at(Ln, a->nerf_packed, Ln.n_trunk - 1, Ln.extra_steps, lds);
   int max_groups = x3 ? Ln.max_groups : fast_panel_groups(Ln, false, bf::kNerfTpp0, bf::kNerfTppH, bf::kNerfTppS);
   if (moco) {
     if (!nof_layout(*a->nof_bw, Lb, prec)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported backward NoF configuration");
-    p.bw = net_of(Lb, a->nof_bw_packed, Lb.n_trunk, Lb.n_head);
+    p.bw = net_at(Lb, a->nof_bw_packed, Lb.n_trunk, Lb.n_head, lds);
     if (bf::nof_panel_groups(Lb, x3) > max_groups) max_groups = bf::nof_panel_groups(Lb, x3);
     if (chains) {
       if (!nof_layout(*a->nof_fw, Lf, prec)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported forward NoF configuration");
-      p.fw = net_of(Lf, a->nof_fw_packed, Lf.n_trunk, Lf.n_head);
+      p.fw = net_at(Lf, a->nof_fw_packed, Lf.n_trunk, Lf.n_head, lds);
       if (bf::nof_panel_groups(Lf, x3) > max_groups) max_groups = bf::nof_panel_groups(Lf, x3);
     }
-    p.pow2 |= (emb_table(a->nof_emb_xyz, p.emb_par[2]) ? 4 : 0) | (emb_table(a->nof_emb_ind, p.emb_par[3]) ? 8 : 0);
+    p.pow2 |= (emb_table(a->nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16) ? 4 : 0) | (emb_table(a->nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16) ? 8 : 0);
     // the per-ray bias table (image-index block of the NoFs' embedded-input layers), one small launch in front
     int combos, layers;
     raybias_shape(a, combos, layers);
@@ -892,46 +699,17 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
     p.rb_buf_bytes = (uint32_t)round_up((int64_t)r_max * p.rb_layers * 512, 1024);
     p.rb_off = lds; lds += 2 * p.rb_buf_bytes;
     // (two rows per buffer are the fewest any S needs, S >= tile: then the samples do not fit, refused just below)
-    if (r_max > 2 && lds + 20u * (uint32_t)a->n_samples > 160u * 1024u)
+    if (r_max > 2 && lds + 20u * (uint32_t)a->n_samples > kRenderLdsCap)
       return fail(MF_E_UNSUPPORTED, "mf_render_pass(bf16): n_samples=%d leaves no room for the per-ray NoF bias rows of a tile "
                   "(%d rays); use MF_PREC_F32 for such short rays", a->n_samples, r_max);
   }
 
-  // rays per group: smallest G with G*S a multiple of the tile (256 samples; x3: 128), capped by the LDS left
-  const uint32_t lds_cap = 160 * 1024;
-  const int max_samples = lds < lds_cap ? (int)((lds_cap - lds) / 20) : 0;
-  const int S = a->n_samples;
-  if (S > max_samples) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
-  int G = 1;
-  while ((G * S) % tile_samples != 0 && (G + 1) * S <= max_samples && G < 64) ++G;
-  if ((G * S) % tile_samples != 0) {        // no exact fit: take as many rays as reduce the padding waste
-    int best = 1; double best_eff = 0;
-    for (int g = 1; g * S <= max_samples && g <= 64; ++g) {
-      const int tiles = (g * S + tile_samples - 1) / tile_samples;
-      const double eff = (double)(g * S) / (tiles * tile_samples);
-      if (eff > best_eff + 1e-9) { best_eff = eff; best = g; }
-    }
-    G = best;
-  }
-  // Several such ray sets per group (up to 8), as in the fp32 pass (mf_render.hip): the composite phase between two groups
-  // keeps at most one wave per ray busy and costs two workgroup barriers, so it comes once per several tiles -- as long as the
-  // CUs' shares stay what they were (same makespan in rays).
-  {
-    const long long cus = device_cus();
-    auto makespan = [&](long long g) { const long long groups = (a->n_rays + g - 1) / g; return (groups + cus - 1) / cus * g; };
-    const long long base = makespan(G);
-    int best = 1;
-    for (int c = 2; c <= 8; ++c)
-      if ((long long)G * c * S <= max_samples && (long long)G * c <= 64 && makespan((long long)G * c) <= base) best = c;
-    G *= best;
-  }
-  p.G = G;
-  p.n_groups = (a->n_rays + G - 1) / G;
-  p.sbuf_off = lds; lds += (uint32_t)(G * S) * 16;
-  p.zbuf_off = lds; lds += (uint32_t)(G * S) * 4;
+  if (int e = plan_ray_groups(a->n_rays, a->n_samples, tile_samples, lds, p.G, p.n_groups)) return e;
+  p.sbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 16;
+  p.zbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 4;
   lds = (lds + 15u) & ~15u;
 
-  const int grid = (int)(p.n_groups < device_cus() ? p.n_groups : device_cus());
+  const int grid = persistent_grid(p.n_groups);
   const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
   if (dump) {      // (validated by the caller: bf16x3)
     if (a->dump_acts && a->dump_stride < (int64_t)Ln.n_trunk * Ln.W + Ln.W / 2)
@@ -939,44 +717,24 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
     if (a->dump_acts && ((a->dump_stride & 3) || (reinterpret_cast<uintptr_t>(a->dump_acts) & 15)))
       return fail(MF_E_INVALID, "mf_render_pass(bf16x3): dump_acts must be 16-byte aligned with a stride that is a multiple of 4 floats");
     p.dump_acts = a->dump_acts; p.dump_stride = a->dump_stride; p.dump_rgbsigma = a->dump_rgbsigma; p.dump_xyz = a->dump_xyz;
-    if (a->dump_mask) {
-      if (!a->dump_acts || a->dump_mask_stride < (int64_t)(Ln.n_trunk + 1) * 8)
-        return fail(MF_E_INVALID, "mf_render_pass: dump_mask needs dump_acts and dump_mask_stride >= 8 (D + 2) words");
-      p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
-    }
+    if (int e = check_dump_mask(a, Ln.n_trunk)) return e;
+    p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
     if (a->dump_nof_acts) {
       // the chain's evaluations: rows [h_1 .. h_D | T padded to 16] (no ReLU bit words, no embedded-input plane: mf_nof_embed_rows)
       if (!moco || !a->dump_nof_out) return fail(MF_E_INVALID, "mf_render_pass(bf16x3): dump_nof_acts needs NoF models and dump_nof_out");
       if (a->dump_nof_stride < (int64_t)Lb.n_trunk * Lb.W + 16 || (a->dump_nof_stride & 3) || (reinterpret_cast<uintptr_t>(a->dump_nof_acts) & 15))
         return fail(MF_E_INVALID, "mf_render_pass(bf16x3): dump_nof_acts must be 16-byte aligned with a stride >= D W + 16 that is a multiple of 4 floats");
       if (chains && (Lf.n_trunk != Lb.n_trunk)) return fail(MF_E_UNSUPPORTED, "mf_render_pass(bf16x3): the NoF dump needs both flows of one depth");
-      const int nsteps = 1 + ((a->flags & MF_F_CHAIN_LOCAL) ? 1 : 0) + ((a->flags & MF_F_CHAIN_GLOBAL) ? 3 : 0);
-      uint32_t seen = 0;
-      for (int k = 0; k < nsteps; ++k) {
-        const int pl = a->dump_nof_plane[k];
-        if (pl < 0 || pl >= nsteps || ((seen >> pl) & 1u)) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_plane must be a permutation of 0..%d", nsteps - 1);
-        seen |= 1u << pl;
-        p.nof_plane_pack |= (uint32_t)pl << (3 * k);
-      }
+      if (int e = nof_plane_pack(a, p.nof_plane_pack)) return e;
       p.dump_nof_acts = a->dump_nof_acts; p.dump_nof_stride = a->dump_nof_stride; p.dump_nof_out = a->dump_nof_out;
     }
   }
-  // the fast mode's kernels: one column block per wave (8 waves, two per SIMD: the default) or two (mf_bf16_2b.hpp: 4 waves, one
-  // per SIMD, every weight fragment read from LDS feeds two MFMAs); same tiles, same LDS layout, bit-identical results.
-  // MF_BF16_BLOCKS=1|2 selects the family.  Round 6 measured the two-block kernels at parity, not ahead (profiles/r06_two_blocks.txt:
-  // half the LDS instructions, 13 % more cycles with a lone wave per SIMD, a higher clock -- C2 shape -0.5 %, C3 +0.7 %), so
-  // they ship opt-in.
-  // (read per call: a getenv is ~100 ns beside a >= 300 us pass, and a test can switch families inside one process)
-  const char* be = getenv("MF_BF16_BLOCKS");
-  const int blocks = be && be[0] == '1' ? 1 : (be && be[0] == '2' ? 2 : kFastBlocksDefault);
-  const bool two = !x3 && blocks == 2;
   void (*kern)(const Params) = x3 ? (moco ? (dump ? render_kernel_bf16<true, true, true> : render_kernel_bf16<true, true>)
                                           : (dump ? render_kernel_bf16<false, true, true> : render_kernel_bf16<false, true>))
-                                  : two ? (moco ? render_kernel_bf16_2b<true> : render_kernel_bf16_2b<false>)
-                                        : (moco ? render_kernel_bf16<true, false> : render_kernel_bf16<false, false>);
+                                  : (moco ? render_kernel_bf16<true, false> : render_kernel_bf16<false, false>);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_render_pass: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3((x3 || two) ? 256 : kThreads), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(x3 ? 256 : kThreads), lds, st, p);
   return check_launch("mf_render_pass(bf16)");
 }
 
@@ -997,25 +755,14 @@ int points_sigma_bf16(int prec, const mf_nerf_desc* nerf, const void* nerf_packe
   if (x3 && nof && ind) return fail(MF_E_UNSUPPORTED, "mf_points_sigma(bf16x3): per-point image indices are not built (use MF_PREC_F32 or MF_PREC_BF16)");
   if (!nerf_layout(*nerf, Ln, prec)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NeRF configuration (bf16: W = 256)");
   uint32_t lds = 0;
-  auto net_of = [&](const NetLayout& L, const void* packed, int D, int aux) {
-    Net n;
-    n.packed = static_cast<const char*>(packed);
-    n.res_lds = lds;
-    n.res_bytes = (uint32_t)L.res_bytes;
-    n.D = D;
-    n.emb_mask = L.emb_mask;
-    n.aux = aux;
-    lds += (uint32_t)L.res_bytes;
-    return n;
-  };
-  p.nerf = net_of(Ln, nerf_packed, Ln.n_trunk - 1, Ln.extra_steps);
+  p.nerf = net_at(Ln, nerf_packed, Ln.n_trunk - 1, Ln.extra_steps, lds);
   int max_groups = x3 ? Ln.max_groups : fast_panel_groups(Ln, false, bf::kNerfTpp0, bf::kNerfTppH, bf::kNerfTppS);
-  p.pow2 = emb_table(*emb_xyz, p.emb_par[0]) ? 1 : 0;
+  p.pow2 = emb_table(*emb_xyz, p.emb_par[0], p.emb_par[0] + 16) ? 1 : 0;
   if (nof) {
     if (!nof_layout(*nof, Lb, prec)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NoF configuration");
-    p.bw = net_of(Lb, nof_packed, Lb.n_trunk, Lb.n_head);
+    p.bw = net_at(Lb, nof_packed, Lb.n_trunk, Lb.n_head, lds);
     if (nof_panel_groups(Lb, x3) > max_groups) max_groups = nof_panel_groups(Lb, x3);
-    p.pow2 |= (emb_table(*nof_emb_xyz, p.emb_par[2]) ? 4 : 0) | (emb_table(*nof_emb_ind, p.emb_par[3]) ? 8 : 0);
+    p.pow2 |= (emb_table(*nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16) ? 4 : 0) | (emb_table(*nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16) ? 8 : 0);
     // per-point (ind given) or single (ind_scalar) bias of the NoF's embedded-input layers, see nof_raybias_kernel
     const int64_t need = points_workspace_bytes_bf16(nof, ind != nullptr, B);
     if (!workspace || workspace_bytes < need)
@@ -1041,8 +788,7 @@ int points_sigma_bf16(int prec, const mf_nerf_desc* nerf, const void* nerf_packe
   if (nof) { p.rb_off = lds; lds += (uint32_t)round_up((int64_t)Lb.n_emb_layers * 512, 1024); }
   p.xyz = xyz; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.sigma = sigma; p.canon = canon;
   const int tile = x3 ? 4 * bf::kWaveSamples : bf::kTile;
-  const long long ntiles = (B + tile - 1) / tile;
-  const int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
+  const int grid = persistent_grid((B + tile - 1) / tile);
   void (*kern)(const PointsParamsBf) = x3 ? (nof ? points_kernel_bf16<true, false, true> : points_kernel_bf16<false, false, true>)
                                           : (nof ? (ind ? points_kernel_bf16<true, true> : points_kernel_bf16<true, false>)
                                                  : points_kernel_bf16<false>);

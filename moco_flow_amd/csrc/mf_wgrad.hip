@@ -22,8 +22,6 @@
 
 namespace mf {
 
-int device_cus();   // mf_forward.hip
-
 constexpr int kWgStage = 16;          // samples per stage
 constexpr int kWgMaxItems = MF_WG_MAX_ITEMS;
 

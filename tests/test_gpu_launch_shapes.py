@@ -17,8 +17,6 @@ per-ray outputs do not depend on the batch around them (tests/test_oracle_golden
 nof_*_disp_* (alpha >= 0.01 mask, all-true if none) are compared only where the oracle sees the whole batch.  Bars are the
 existing ones: 1e-4 max-rel for f32 and bf16x3 (test_c3_full_size_*), the oracle-of-its-arithmetic bars of
 tests/test_gpu_bf16_oracle.py for the fast mode, helpers._check_grads_vs_float64 for the fp32 training step's gradients."""
-import os
-
 import pytest
 import torch
 
@@ -96,24 +94,17 @@ def _inputs(net, n):
     return (varied_indices(rays, seed=n) if net == "moco" else rays), torch.from_numpy(bg)
 
 
-def _render(M, c, rays, bg, precision, env=None):
-    """The HIP pass over rays (cuda tensors, any row stride) in `precision`, gradient-free; env: MF_BF16_BLOCKS for the call."""
+def _render(M, c, rays, bg, precision):
+    """The HIP pass over rays (cuda tensors, any row stride) in `precision`, gradient-free."""
     from moco_flow_amd import rendering
     embs, nerfs, kw = build_case(M, c, 0, device="cuda")
-    prev = os.environ.get("MF_BF16_BLOCKS")
     strict = rendering.STRICT_RNG
     try:
         rendering.STRICT_RNG = False
         rendering.set_precision(precision)
-        if env is not None:
-            os.environ["MF_BF16_BLOCKS"] = env
         with torch.no_grad():
             return M.render_rays(rays, bg, embs, nerfs, **kw)
     finally:
-        if prev is None:
-            os.environ.pop("MF_BF16_BLOCKS", None)
-        else:
-            os.environ["MF_BF16_BLOCKS"] = prev
         rendering.set_precision("f32")
         rendering.STRICT_RNG = strict
 
@@ -230,8 +221,7 @@ def _split_points(n):
 def test_launch_invariants_bit_exact(M, cus, net, prec, n_of, S, full):
     """Over the whole batch, bit for bit: one launch = the concatenation of three launches over an uneven split (what
     tools/ragged_sweep.py checks by hand); a row-strided rays view = its contiguous copy (the pointer and stride(0) go to the
-    kernels as they are), for a (N, 12) buffer's leading columns and for rays[::2]; in the fast mode the two-column-block
-    kernels (MF_BF16_BLOCKS=2) = the default family."""
+    kernels as they are), for a (N, 12) buffer's leading columns and for rays[::2]."""
     n = n_of[0] * cus + n_of[1]
     c = _case(net, S)
     rays, bg = _inputs(net, n)
@@ -256,8 +246,6 @@ def test_launch_invariants_bit_exact(M, cus, net, prec, n_of, S, full):
     twice[::2] = rays
     assert twice[::2].stride(0) == 2 * rays.shape[1]
     same(_render(M, c, twice[::2], bg, prec), "rays[::2]")
-    if prec == "bf16":
-        same(_render(M, c, rays, bg, prec, env="2"), "MF_BF16_BLOCKS=2")
 
 
 @pytest.mark.parametrize("net", sorted(NETS))
