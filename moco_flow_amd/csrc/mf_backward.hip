@@ -28,19 +28,14 @@ namespace mf {
 // features, K = W) and, with one skip layer, layer D+2 = that layer's embedded columns transposed:
 //     d emb = W_0[:, :63]^T d_z_0 + W_skip[:, :63]^T d_z_skip.
 // (More than one skip layer: not built; n_head = number of these layers, 0 = g_emb unsupported.)
-inline int bwd_skip_layer(const mf_nerf_desc& d) {      // the single skip layer, 0 = none, -1 = several
-  int s = 0;
-  for (int l = 1; l < d.D; ++l)
-    if ((d.skip_mask >> l) & 1u) { if (s) return -1; s = l; }
-  return s;
-}
 inline bool nerf_bwd_layout(const mf_nerf_desc& d, NetLayout& L) {
   NetLayout F;
   if (!nerf_layout(d, F, 0) || F.W != 256) return false;
   L = NetLayout{};
   L.W = F.W; L.NK = F.NK; L.NP = F.NP;
   L.n_trunk = d.D + 1;
-  L.n_head = bwd_skip_layer(d) < 0 ? 0 : (bwd_skip_layer(d) > 0 ? 2 : 1);
+  const int skip = single_skip_layer(d.skip_mask, d.D);
+  L.n_head = skip < 0 ? 0 : (skip > 0 ? 2 : 1);
   L.emb_steps = kBwdSigSteps;
   L.emb_mask = 2u;
   L.relu_mask = 0;
@@ -56,54 +51,6 @@ inline bool nerf_bwd_layout(const mf_nerf_desc& d, NetLayout& L) {
 }
 MF_HD int bwd_groups(const NetLayout& L, int layer) {
   return layer == 0 ? L.NK : (layer == 1 ? 2 * (L.NK + 1) : 2 * L.NK);
-}
-
-// ------------------------------------------------------------------ packing (transposed fragment stream)
-struct BwdPackJob {
-  const float* W[MF_MAX_LAYERS + 3];   // forward weight feeding backward layer i
-  int ld[MF_MAX_LAYERS + 3];           // its row length (forward in-features)
-  int col0[MF_MAX_LAYERS + 3];         // first hidden column
-  int groups[MF_MAX_LAYERS + 3];
-  long long g0[MF_MAX_LAYERS + 4];
-  int ncols[MF_MAX_LAYERS + 3];        // forward input columns present (output rows beyond are zero): emb layers
-  int n_layers, NP;
-  const float* sigma_w;
-  const float* rgb_w;
-  int res_floats, off_rgb_w, n_rgb_w;
-  float* res;
-  float* panels;
-  long long total_groups;
-};
-
-__global__ void pack_bwd_kernel(BwdPackJob job) {
-  const long long gidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gidx < job.res_floats) {
-    const int o = (int)gidx - job.off_rgb_w;
-    job.res[gidx] = (o >= 0 && o < job.n_rgb_w) ? job.rgb_w[o] : 0.f;
-  }
-  const long long grp = gidx >> 6;
-  if (grp >= job.total_groups) return;
-  const int lane = (int)(gidx & 63);
-  int li = 0;
-  while (li + 1 < job.n_layers && grp >= job.g0[li + 1]) ++li;
-  const long long local = grp - job.g0[li];
-  const int P = (int)(local / job.groups[li]), gi = (int)(local % job.groups[li]);
-  const int b = gi >> 1, half = gi & 1;
-  const int i = lane & 15, g = lane >> 4;
-  const int n = 32 * P + 16 * half + i;            // output feature of the backward layer = forward input column
-  const int sig = li == 1 ? 1 : 0;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (sig && b == 0) {
-    if (g == 0) v.x = job.sigma_w[n];              // step 0 of lane group 0 carries d_sigma
-  } else {
-    const int bh = b - sig;
-    float* pv = &v.x;
-    for (int r = 0; r < 4; ++r) {
-      const int k = 16 * bh + 4 * g + r;           // forward output row
-      pv[r] = n < job.ncols[li] ? job.W[li][(long long)k * job.ld[li] + job.col0[li] + n] : 0.f;
-    }
-  }
-  reinterpret_cast<float4*>(job.panels)[gidx] = v;
 }
 
 // ------------------------------------------------------------------ the kernel
@@ -271,53 +218,32 @@ extern "C" int32_t mf_nerf_pack_bwd(const mf_nerf_desc* d, void* packed, void* s
   NetLayout L;
   if (!d || !packed) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: null argument");
   if (!nerf_bwd_layout(*d, L)) return fail(MF_E_UNSUPPORTED, "mf_nerf_pack_bwd: unsupported NeRF configuration (W=%d D=%d)", d->W, d->D);
-  BwdPackJob job{};
+  // the forward layout of W^T (mf_layout.hpp): backward layer 0 = extra_encoding[:, :W]^T (K = W/2), 1 = [sigma.weight (the
+  // d_sigma slot: step 0 of lane group 0) ; xyz_encoding_final^T], 2..D = trunk layers D-1..1 transposed (hidden columns),
+  // then the embedded-input layers (64 rows = 2 panels, rows >= in_channels_xyz zero)
+  PackJob job{};
   const int ext = d->extra_feat_type == MF_EXTRA_NONE ? 0 : d->extra_feat_dim;
-  job.n_layers = d->D + 1;
-  job.NP = L.NP;
-  long long g0 = 0;
+  auto wt = [&](const float* W, int ld, int quads) { return PackBlock{W, 1, ld, kPackHidden, quads, 1, 16 * quads}; };
   for (int i = 0; i <= d->D; ++i) {
-    if (i == 0) { job.W[i] = d->extra_w; job.ld[i] = L.W + ext; job.col0[i] = 0; }
-    else if (i == 1) { job.W[i] = d->final_w; job.ld[i] = L.W; job.col0[i] = 0; }
-    else {
-      const int l = d->D + 1 - i;
-      const bool skip = (d->skip_mask >> l) & 1u;
-      job.W[i] = d->trunk_w[l];
-      job.ld[i] = L.W + (skip ? d->in_channels_xyz : 0);
-      job.col0[i] = skip ? d->in_channels_xyz : 0;
-    }
-    if (!job.W[i]) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: missing weight pointer (backward layer %d)", i);
-    job.groups[i] = bwd_groups(L, i);
-    job.g0[i] = g0;
-    g0 += (long long)job.groups[i] * L.NP;
+    const int l = d->D + 1 - i, col0 = (i > 1 && ((d->skip_mask >> l) & 1u)) ? d->in_channels_xyz : 0;
+    const float* W = i == 0 ? d->extra_w : (i == 1 ? d->final_w : d->trunk_w[l]);
+    if (!W) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: missing weight pointer (backward layer %d)", i);
+    if (i == 0) job.add(L.NP, bwd_groups(L, 0), wt(W, L.W + ext, L.NK / 2));
+    else if (i == 1) job.add(L.NP, bwd_groups(L, 1), PackBlock{d->sigma_w, 1, 0, kPackHidden, 1, 1, 1}, wt(W, L.W, L.NK));
+    else job.add(L.NP, bwd_groups(L, i), wt(W + col0, L.W + col0, L.NK));
   }
-  for (int i = 0; i <= d->D; ++i) job.ncols[i] = 1 << 30;
   for (int e = 0; e < L.n_head; ++e) {                      // embedded-input gradient layers
-    const int i = d->D + 1 + e, l = e == 0 ? 0 : bwd_skip_layer(*d);
-    job.W[i] = d->trunk_w[l];
-    if (!job.W[i]) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: missing weight pointer (layer %d)", l);
-    job.ld[i] = (l == 0 ? 0 : L.W) + d->in_channels_xyz;
-    job.col0[i] = 0;
-    job.ncols[i] = d->in_channels_xyz;
-    job.groups[i] = 2 * L.NK;
-    job.g0[i] = g0;
-    g0 += (long long)job.groups[i] * 2;
+    const int l = e == 0 ? 0 : single_skip_layer(d->skip_mask, d->D);
+    if (!d->trunk_w[l]) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: missing weight pointer (layer %d)", l);
+    job.add(2, 2 * L.NK, wt(d->trunk_w[l], (l == 0 ? 0 : L.W) + d->in_channels_xyz, L.NK)).n_rows = d->in_channels_xyz;
   }
-  job.n_layers = d->D + 1 + L.n_head;
-  job.g0[job.n_layers] = g0;
   if (!d->sigma_w || !d->rgb_w) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: missing sigma / rgb weight");
-  job.sigma_w = d->sigma_w;
-  job.rgb_w = d->rgb_w;
+  job.res[job.n_res++] = ResCopy{d->rgb_w, L.off_rgb_w, 3 * (L.W / 2)};
   job.res_floats = (int)(L.res_bytes / 4);
-  job.off_rgb_w = L.off_rgb_w;
-  job.n_rgb_w = 3 * (L.W / 2);
-  job.res = static_cast<float*>(packed);
+  job.resident = static_cast<float*>(packed);
   job.panels = reinterpret_cast<float*>(static_cast<char*>(packed) + L.res_bytes);
-  job.total_groups = g0;
-  if (g0 * kGroupBytes != L.panel_bytes) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: layout mismatch");
-  const long long slots = g0 * 64;
-  hipLaunchKernelGGL(pack_bwd_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), job);
-  return check_launch("mf_nerf_pack_bwd");
+  if (job.total_groups * kGroupBytes != L.panel_bytes) return fail(MF_E_INVALID, "mf_nerf_pack_bwd: layout mismatch");
+  return launch_pack(job, static_cast<hipStream_t>(stream), "mf_nerf_pack_bwd");
 }
 
 extern "C" int32_t mf_nerf_backward(const mf_nerf_desc* d, const void* packed_bwd, int64_t P, const float* g_out,
@@ -359,7 +285,7 @@ extern "C" int32_t mf_nerf_backward_x(const mf_nerf_desc* d, const void* packed_
   if (!nerf_bwd_layout(*d, p.net.L)) return fail(MF_E_UNSUPPORTED, "mf_nerf_backward: unsupported NeRF configuration");
   if (g_emb && p.net.L.n_head == 0) return fail(MF_E_UNSUPPORTED, "mf_nerf_backward: the embedded-input gradient is built for at most one skip layer");
   p.g_emb = g_emb;
-  p.skip = bwd_skip_layer(*d) > 0 ? bwd_skip_layer(*d) : 0;
+  p.skip = single_skip_layer(d->skip_mask, d->D) > 0 ? single_skip_layer(d->skip_mask, d->D) : 0;
   if (stride < (int64_t)(d->D + 1) * d->W + d->W / 2 || (stride & 3))
     return fail(MF_E_INVALID, "mf_nerf_backward: stride %lld too small or not a multiple of 4", (long long)stride);
   if (P == 0) return MF_OK;

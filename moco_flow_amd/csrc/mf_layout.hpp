@@ -7,6 +7,69 @@ namespace mf {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// the single skip layer of a D-layer trunk (skip_mask bits 1 .. D-1): 0 = none, -1 = several
+inline int single_skip_layer(uint32_t skip_mask, int D) {
+  int s = 0;
+  for (int l = 1; l < D; ++l)
+    if ((skip_mask >> l) & 1u) { if (s) return -1; s = l; }
+  return s;
+}
+
+// ------------------------------------------------------------------ the packed fragment streams (mf_pack.hip: pack_panels_kernel)
+// Every stream -- the forward's W and each backward chain's W^T -- is a list of regions written by one kernel.  A region is
+// `tiles` panels of `groups` 1 KiB groups; a panel's k range is up to two blocks in stream order.  Element (n, c) of a block's
+// matrix is src[n * s_n + c * s_k]: a forward block reads W, (s_n, s_k) = (n_in, 1), a backward block the same layout of W^T,
+// (1, ld).  fp32: panel = 32 rows, its groups alternate between its two 16-row tiles; group (tile half, k-quad q) holds, for
+// lane (i = lane & 15, g = lane >> 4) and r = 0..3, row 32 P + 16 half + i at column c(step = 4 q + r, g).  bf16 (mf_bf16.hpp):
+// panel = ONE 32-row tile, group = A fragment of v_mfma_f32_32x32x16_bf16: lane (i = lane & 31, h = lane >> 5) holds 8 bf16 =
+// row 32 P + i at column c(k-step, slot 8 h + e), e = 0..7, each k-step as `split` groups (hi, lo[, ...] terms).
+constexpr int kPackHidden = -1;   // PackBlock::kind of a plain k range: c = 16 q + 4 g + r (fp32) | 16 ks + hid_perm2(h, e) (bf16)
+struct PackBlock {
+  const float* src;
+  int s_n, s_k;
+  int kind;                  // kPackHidden, or the EmbKind of an embedded-input block (emb_feature / emb_feature2, mf_core.hpp)
+  int steps;                 // fp32: k-quads (two groups each); bf16: 16-k steps (`split` groups each); 0 = no block
+  int split;                 // bf16: groups per k-step: 1 = plain, 2 = (hi, lo), 3 = (hi, mid, lo)
+  int cols;                  // columns present (c >= cols: zero)
+};
+
+struct PackRegion {          // one layer's panels
+  PackBlock blk[2];
+  int tiles;                 // panels
+  int groups;                // groups per panel
+  int n_rows;                // rows present (n >= n_rows: zero; 0 = all)
+  int row_terms;             // bf16 head panels of the fast mode (NetLayout::head_tiles): tile row c < n_rows = bf16(W[c]), row row_terms + c =
+                             // bf16(W[c] - hi); row_terms = 8 (NeRF sigma / rgb: <= 4 rows) or 16 (NoF head: 3 | 9 rows); 0 = off
+  long long dst_group0;      // first group index (in 1 KiB units) within the panel area
+};
+
+struct ResCopy { const float* src; int dst_off; int n; float scale = 1.f; };
+
+struct PackJob {
+  PackRegion reg[MF_MAX_LAYERS + 3];
+  int n_regions;
+  int bf16;                  // groups hold 8 bf16 per lane (32x32x16 A fragments) instead of 4 fp32
+  int xyz_cols;              // kEmbNofIn blocks: the index block starts there
+  int half;                  // the split terms are IEEE halves of wscale * w (NetLayout::half) instead of bf16
+  float wscale;
+  long long total_groups;
+  float* panels;
+  float* poison;             // half-pair layouts: resident head-bias rows 27 (+ 4 = 31), set to NaN when a weight saturates; else null
+  ResCopy res[2];            // the resident block, filled by the same launch (backward streams; the forward's has a launch of its own)
+  int n_res, res_floats;
+  float* resident;
+  PackRegion& add(int tiles, int groups, const PackBlock& b0, const PackBlock& b1 = PackBlock{}) {   // host: the next region
+    PackRegion& R = reg[n_regions++];
+    R = PackRegion{{b0, b1}, tiles, groups, 0, 0, total_groups};
+    total_groups += (long long)groups * tiles;
+    return R;
+  }
+};
+static_assert(sizeof(PackJob) <= 2048, "pack_panels_kernel's argument block");
+
+// one launch of pack_panels_kernel: the job's resident block and its panels (mf_pack.hip)
+int launch_pack(const PackJob& job, hipStream_t st, const char* what);
+
 // returns false (layout zeroed) for configurations the kernels do not implement
 // `bf16` = the MF_PREC_* value: 0 fp32, 1 bf16, 2 bf16x3 (bf16 layout with more (hi, lo) split ranges, mf_bf16.hpp)
 inline bool nerf_layout(const mf_nerf_desc& d, NetLayout& L, int bf16 = 0) {

@@ -126,12 +126,9 @@ __global__ __launch_bounds__(kThreads, 2) void nof_points_dump_kernel(NofDumpPar
 inline bool nof_bwd_layout(const mf_nof_desc& d, NetLayout& L, int& skip) {
   NetLayout F;
   if (!nof_layout(d, F, 0)) return false;
-  skip = -1;
-  for (int l = 1; l < d.D; ++l)
-    if ((d.skip_mask >> l) & 1u) {
-      if (skip >= 0) return false;               // one skip layer at most (every reference config)
-      skip = l;
-    }
+  skip = single_skip_layer(d.skip_mask, d.D);
+  if (skip < 0) return false;                    // one skip layer at most (every reference config)
+  if (skip == 0) skip = -1;                      // (the kernel's "none")
   L = NetLayout{};
   L.W = F.W; L.NK = F.NK; L.NP = F.NP;
   L.n_trunk = d.D;
@@ -144,58 +141,6 @@ inline bool nof_bwd_layout(const mf_nof_desc& d, NetLayout& L, int& skip) {
   L.max_groups = 2 * k_emb;
   L.panel_bytes = ((int64_t)(d.D - 1) * L.NP * 2 * L.NK + 2 * 2 * k_emb) * kGroupBytes;
   return true;
-}
-
-struct NofBwdPackJob {
-  const float* W[MF_MAX_LAYERS];       // forward trunk weights
-  int ld[MF_MAX_LAYERS];
-  int D, skip, NK, NP;
-  const float* head_w;
-  int n_head_w, off_head_w, res_floats;
-  float* res;
-  float* panels;
-  long long total_groups;
-};
-
-__global__ void pack_nof_bwd_kernel(NofBwdPackJob job) {
-  const long long gidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gidx < job.res_floats) {
-    const int o = (int)gidx - job.off_head_w;
-    job.res[gidx] = (o >= 0 && o < job.n_head_w) ? job.head_w[o] : 0.f;
-  }
-  const long long grp = gidx >> 6;
-  if (grp >= job.total_groups) return;
-  const int lane = (int)(gidx & 63);
-  const int i = lane & 15, g = lane >> 4;
-  const int per_layer = job.NP * 2 * job.NK;            // groups of a W -> W layer
-  const long long chain = (long long)(job.D - 1) * per_layer;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  float* pv = &v.x;
-  if (grp < chain) {
-    const int li = (int)(grp / per_layer), local = (int)(grp % per_layer);
-    const int l = job.D - 1 - li;                        // forward layer
-    const int P = local / (2 * job.NK), gi = local % (2 * job.NK);
-    const int b = gi >> 1, half = gi & 1;
-    const int n = 32 * P + 16 * half + i;
-    const int col0 = l == job.skip ? job.ld[l] - 16 * job.NK : 0;
-    for (int r = 0; r < 4; ++r) {
-      const int k = 16 * b + 4 * g + r;
-      pv[r] = job.W[l][(long long)k * job.ld[l] + col0 + n];
-    }
-  } else {
-    const int kq = job.skip >= 0 ? 2 * job.NK : job.NK;
-    const int local = (int)(grp - chain);
-    const int P = local / (2 * kq), gi = local % (2 * kq);
-    const int b = gi >> 1, half = gi & 1;
-    const int n = 32 * P + 16 * half + i;                // embedded column 0..63
-    for (int r = 0; r < 4; ++r) {
-      const int k = 16 * b + 4 * g + r;                  // [d z_0 ; d z_skip]
-      const int l = k < 16 * job.NK ? 0 : job.skip;
-      const int kk = k < 16 * job.NK ? k : k - 16 * job.NK;
-      pv[r] = job.W[l][(long long)kk * job.ld[l] + n];
-    }
-  }
-  reinterpret_cast<float4*>(job.panels)[gidx] = v;
 }
 
 // ------------------------------------------------------------------ the backward kernel
@@ -421,25 +366,25 @@ extern "C" int32_t mf_nof_pack_bwd(const mf_nof_desc* d, void* packed, void* str
   int skip;
   if (!d || !packed) return fail(MF_E_INVALID, "mf_nof_pack_bwd: null argument");
   if (!nof_bwd_layout(*d, L, skip)) return fail(MF_E_UNSUPPORTED, "mf_nof_pack_bwd: unsupported NoF configuration");
-  NofBwdPackJob job{};
+  // the forward layout of W^T (mf_layout.hpp): backward layers 0 .. D-2 = trunk layers D-1 .. 1 transposed (hidden columns), then
+  // [W_0^T ; W_skip^T] stacked along k in one 64-row layer (rows >= the embedded columns zero)
+  PackJob job{};
   const int cin = d->in_channels_xyz + d->extra_feat_dim;
-  for (int l = 0; l < d->D; ++l) {
+  for (int l = 0; l < d->D; ++l)
     if (!d->trunk_w[l]) return fail(MF_E_INVALID, "mf_nof_pack_bwd: missing weight pointer for layer %d", l);
-    job.W[l] = d->trunk_w[l];
-    job.ld[l] = (l == 0 ? cin : L.W) + ((l > 0 && l == skip) ? cin : 0);
-  }
   if (!d->head_w) return fail(MF_E_INVALID, "mf_nof_pack_bwd: missing head weight");
-  job.D = d->D; job.skip = skip; job.NK = L.NK; job.NP = L.NP;
-  job.head_w = d->head_w;
-  job.n_head_w = L.n_head * L.W;
-  job.off_head_w = L.off_head_w;
+  auto wt = [&](int l, int col0) {
+    const int ld = (l == 0 ? cin : L.W) + ((l > 0 && l == skip) ? cin : 0);
+    return PackBlock{d->trunk_w[l] + col0, 1, ld, kPackHidden, L.NK, 1, L.W};
+  };
+  for (int l = d->D - 1; l >= 1; --l) job.add(L.NP, 2 * L.NK, wt(l, l == skip ? cin : 0));
+  job.add(2, skip >= 0 ? 4 * L.NK : 2 * L.NK, wt(0, 0), skip >= 0 ? wt(skip, 0) : PackBlock{}).n_rows = cin;
+  job.res[job.n_res++] = ResCopy{d->head_w, L.off_head_w, L.n_head * L.W};
   job.res_floats = (int)(L.res_bytes / 4);
-  job.res = static_cast<float*>(packed);
+  job.resident = static_cast<float*>(packed);
   job.panels = reinterpret_cast<float*>(static_cast<char*>(packed) + L.res_bytes);
-  job.total_groups = L.panel_bytes / kGroupBytes;
-  const long long slots = job.total_groups * 64 > job.res_floats ? job.total_groups * 64 : job.res_floats;
-  hipLaunchKernelGGL(pack_nof_bwd_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), job);
-  return check_launch("mf_nof_pack_bwd");
+  if (job.total_groups * kGroupBytes != L.panel_bytes) return fail(MF_E_INVALID, "mf_nof_pack_bwd: layout mismatch");
+  return launch_pack(job, static_cast<hipStream_t>(stream), "mf_nof_pack_bwd");
 }
 
 extern "C" int32_t mf_nof_backward(const mf_nof_desc* d, const void* packed_bwd, const mf_embedding* emb_xyz, int64_t P,

@@ -14,7 +14,7 @@
 // pipe's cost per product; ten launches of ~0.3 ms per joint training step at 52 % MFMA busy, profiles/r04_train_joint_*); what
 // stays here is the VALU work around the chain -- the transform's forward-mode partials, the 9 x 128 head product, the
 // sin / cos of the chain rule.
-#include "mf_bf16.hpp"
+#include "mf_bwd3.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nofbwd.hpp"
@@ -32,49 +32,6 @@ constexpr int kN3Zero = 0, kN3Head = 32;
 inline int n3_res_bytes(int n_head) { return (int)round_up((int64_t)(32 + n_head * kNW) * 4, kGroupBytes); }
 inline long long n3_groups_total(int D, int n_emb) { return (long long)(D - 1) * 4 * 16 + (long long)n_emb * 2 * 16; }
 
-struct N3PackJob {
-  const float* W[MF_MAX_LAYERS + 2];   // forward weight feeding backward layer i
-  int ld[MF_MAX_LAYERS + 2];           // its row length
-  int col0[MF_MAX_LAYERS + 2];         // first column read
-  int tiles[MF_MAX_LAYERS + 2];        // 32-row tiles of the backward layer's output
-  long long g0[MF_MAX_LAYERS + 3];     // first group of layer i
-  int n_layers;
-  const float* head_w; int n_head;
-  float* res; int res_floats; unsigned* panels;
-  long long total_groups;
-};
-
-__device__ inline unsigned short n3_rne(float x) {
-  const unsigned u = __float_as_uint(x);
-  const unsigned rnd = u + 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(((u & 0x7f800000u) == 0x7f800000u ? u : rnd) >> 16);
-}
-
-__global__ void pack_nof_bwd3_kernel(N3PackJob job) {
-  const long long gidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gidx < job.res_floats) {
-    const int o = (int)gidx - kN3Head;
-    job.res[gidx] = (o >= 0 && o < job.n_head * kNW) ? job.head_w[o] : 0.f;
-  }
-  const long long grp = gidx >> 6;
-  if (grp >= job.total_groups) return;
-  const int lane = (int)(gidx & 63), i = lane & 31, h = lane >> 5;
-  int li = 0;
-  while (li + 1 < job.n_layers && grp >= job.g0[li + 1]) ++li;
-  const long long local = grp - job.g0[li];
-  const int P = (int)(local / 16), gi = (int)(local % 16), ks = gi >> 1, lo = gi & 1;
-  const int n = 32 * P + i;                               // output feature of the backward layer = forward input column
-  unsigned short h8[8];
-  for (int e = 0; e < 8; ++e) {
-    const int k = 16 * ks + hid_perm2(h, e);              // forward output row
-    const float w = job.W[li][(long long)k * job.ld[li] + job.col0[li] + n];
-    const unsigned short hi = n3_rne(w);
-    h8[e] = lo ? n3_rne(w - __uint_as_float((unsigned)hi << 16)) : hi;
-  }
-  unsigned* dst = job.panels + gidx * 4;
-  for (int w = 0; w < 4; ++w) dst[w] = (unsigned)h8[2 * w] | ((unsigned)h8[2 * w + 1] << 16);
-}
-
 struct Nof3Params {
   Net net;                 // packed, res_lds, res_bytes, D; aux = head rows (3 | 9)
   float exyz[32];          // xyz embedding: freq[16], weight[16]
@@ -85,98 +42,6 @@ struct Nof3Params {
   float* gpre; float* g_pts;
   uint32_t par_off, ring_off, buf_bytes;
 };
-
-// value of accumulator register r, masked by the forward activation (m: the four float4 of this lane's activations of the tile;
-// BITS: m[0][0] carries the two mask bytes of this lane half for the tile -- lane groups g = h and g = 2 + h of the forward's panel
-// t, relu_mask_pair in mf_core.hpp: row 8 q + 4 h + i of the tile sits at bit 8 (q & 1) + 4 (q >> 1) + i)
-template <bool BITS>
-MF_D float n3_val(const f32x16& acc, const f32x4 (&m)[4], int r) {
-  if (BITS) return ((__builtin_bit_cast(unsigned, m[0][0]) >> (((r >> 2) & 1) * 8 + ((r >> 2) >> 1) * 4 + (r & 3))) & 1u) ? acc[r] : 0.f;
-  return m[r >> 2][r & 3] > 0.f ? acc[r] : 0.f;
-}
-
-// One backward layer of the chain: (out, outlo) <- split(mask * (Wt (in, inlo))), the fp32 values to grow[32 t + ...].
-// mrow / grow: this lane's dump row / gradient row of the layer + 4 (lane >> 5).  OUT: the result is an operand again.
-// BITS: `mrow` points at the layer's 4 mask words of this lane's sample instead (one 4-byte load per tile).
-template <bool OUT, bool BITS, class ST>
-MF_D void nof3_layer(ST& st, const Lane& id, CarryX& carry, const u32x4 (&in)[8], const u32x4 (&inlo)[8], u32x4 (&out)[8],
-                     u32x4 (&outlo)[8], uint32_t zero_off, const Next& nxt, const float* mrow, float* grow) {
-  constexpr int NT = 4, KHID = 8, NG = 2 * KHID, NM = 3 * KHID, kSteps = 16;
-  f32x16 pend = {};
-  f32x4 pm[4] = {}, hm[4] = {};
-  // The mask is applied ONCE per element -- in the hi step of its pair, written back into the pending accumulators -- and the lo
-  // step and the row store read the masked value (round 5; before, each of the three re-did the bit test: 144 instead of 48
-  // VALU per tile in a kernel that runs against the VALU).  Every hi step (sidx <= 14) lies in front of the first store gap.
-  auto step = [&](f32x16& acc, const f32x4 (&m)[4], int sidx, int t) __attribute__((always_inline)) {
-    const int u = sidx >> 1, w = u & 3, r = u < 4 ? 2 * u : 8 + 2 * (u - 4);
-    if (!OUT) return;
-    if (!(sidx & 1)) { acc[r] = n3_val<BITS>(acc, m, r); acc[r + 1] = n3_val<BITS>(acc, m, r + 1); }
-    const float v0 = acc[r], v1 = acc[r + 1];
-    u32x4& hv = u < 4 ? out[2 * t] : out[2 * t + 1];
-    if (!(sidx & 1)) {
-      unsigned hi = pack_bf16x2(v0, v1);
-      asm volatile("" : "+v"(hi));
-      hv[w] = hi;
-    } else {
-      const unsigned hi = hv[w];
-      unsigned lo = pack_bf16x2(v0 - bflo(hi), v1 - bfhi(hi));
-      asm volatile("" : "+v"(lo));
-      (u < 4 ? outlo[2 * t] : outlo[2 * t + 1])[w] = lo;
-    }
-  };
-  auto store = [&](const f32x16& acc, const f32x4 (&m)[4], int t, int q) __attribute__((always_inline)) {
-    f32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = OUT ? acc[4 * q + i] : n3_val<BITS>(acc, m, 4 * q + i);      // (OUT: masked by the hi steps)
-    *reinterpret_cast<f32x4*>(grow + 32 * t + 8 * q) = v;
-  };
-  auto run = [&](auto tc) __attribute__((always_inline)) {
-    constexpr int t = decltype(tc)::value;
-    const Ahead two{t + 2 < NT ? NG : (t == NT - 2 ? nxt.groups : nxt.groups2),
-                    t == NT - 2 ? nxt.jump : (t == NT - 1 ? nxt.jump2 : nullptr), 0, nullptr, t + 2 < NT ? NG : -1, -1};
-    if constexpr (BITS) {                                      // this tile's two mask bytes: in flight across its MFMAs
-      hm[0][0] = __builtin_bit_cast(float, relu_mask_pair(reinterpret_cast<const unsigned*>(mrow), t, id.h));
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) hm[q] = *reinterpret_cast<const f32x4*>(mrow + 32 * t + 8 * q);
-    }
-    constexpr int tp = t > 0 ? t - 1 : 0;
-    auto gap = [&](int m) __attribute__((always_inline)) {
-      if (t == 0) return;
-#pragma unroll
-      for (int sidx = kSteps * m / NM; sidx < kSteps * (m + 1) / NM; ++sidx) step(pend, pm, sidx, tp);
-      if (m >= NM - 4) store(pend, pm, tp, m - (NM - 4));
-    };
-    f32x16 acc;
-    // VM operations younger than the previous panel's last piece at this tile's barrier: the four row stores that closed the
-    // previous tile (tile 0: the layer in front; none behind tile 0) + this tile's four mask loads
-    constexpr int KEEP = (t == 1 ? 0 : 4) + (BITS ? 2 : 4);
-    mma_tile_x<0, KHID, 2, true, KEEP, true>(st, id, carry, in, inlo, in, inlo, zero_off, two, acc, gap);
-    st.advance();
-    pend = acc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pm[q] = hm[q];
-  };
-  run(std::integral_constant<int, 0>{}); run(std::integral_constant<int, 1>{});
-  run(std::integral_constant<int, 2>{}); run(std::integral_constant<int, 3>{});
-#pragma unroll
-  for (int sidx = 0; sidx < kSteps; ++sidx) step(pend, pm, sidx, NT - 1);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) store(pend, pm, NT - 1, q);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// A 64-row layer behind the chain (the embedded-input gradient): res[t] = Wt_tile (in, inlo), t = 0, 1; nothing stored.
-template <class ST>
-MF_D void nof3_emb(ST& st, const Lane& id, CarryX& carry, const u32x4 (&in)[8], const u32x4 (&inlo)[8], uint32_t zero_off,
-                   const Next& nxt, f32x16 (&res)[2]) {
-  const Ahead t0{nxt.groups, nxt.jump, 0, nullptr}, t1{nxt.groups2, nxt.jump2, 0, nullptr};
-  auto nogap = [](int) {};
-  mma_tile_x<0, 8, 2, true>(st, id, carry, in, inlo, in, inlo, zero_off, t0, res[0], nogap);
-  st.advance();
-  mma_tile_x<0, 8, 2, true>(st, id, carry, in, inlo, in, inlo, zero_off, t1, res[1], nogap);
-  st.advance();
-}
 
 // eight fp32 values (two float4 of a row: features 16 ks + 4 h + (0..3) and 16 ks + 8 + 4 h + (0..3)) -> (hi, lo) operand dwords
 MF_D void n3_split8(const f32x4& v0, const f32x4& v1, u32x4& hi4, u32x4& lo4) {
@@ -278,13 +143,14 @@ __global__ __launch_bounds__(256, 1) void nof_backward_kernel_x3(const Nof3Param
     }
     // chain: d z_{l-1} = (W_l[:, hidden]^T d z_l) [h_l > 0],  l = D-1 .. 1   (a -> b, copied back)
     for (int l = D - 1; l >= 1; --l) {
-      nof3_layer<true, BITS>(st, id, carry, ah, al, bh, bl, zero_off, n16, arow + (long long)(l - 1) * LW, grow + (long long)(l - 1) * kNW);
+      bwd_layer_x<4, 8, true, false, true, BITS>(st, id, carry, ah, al, bh, bl, zero_off, n16, arow + (long long)(l - 1) * LW,
+                                                grow + (long long)(l - 1) * kNW, 0u, 0.f);
 #pragma unroll
       for (int t = 0; t < 8; ++t) { ah[t] = bh[t]; al[t] = bl[t]; }
     }
     // embedded-input gradient, columns 0..63:  W_0[:, :64]^T d z_0 (+ W_skip[:, :64]^T d z_skip)
     f32x16 ge[2];
-    nof3_emb(st, id, carry, ah, al, zero_off, p.skip >= 0 ? n16 : nfirst, ge);
+    bwd_emb_x(st, id, carry, ah, al, zero_off, p.skip >= 0 ? n16 : nfirst, ge);
     if (p.skip >= 0) {
       // d z_skip was stored by this very lane several layers ago (the panel barriers' vmcnt waits retired the stores)
       const float* zrow = grow + (long long)p.skip * kNW;
@@ -292,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void nof_backward_kernel_x3(const Nof3Param
       for (int ks = 0; ks < 8; ++ks)
         n3_split8(*reinterpret_cast<const f32x4*>(zrow + 16 * ks), *reinterpret_cast<const f32x4*>(zrow + 16 * ks + 8), ah[ks], al[ks]);
       f32x16 g2[2];
-      nof3_emb(st, id, carry, ah, al, zero_off, nfirst, g2);
+      bwd_emb_x(st, id, carry, ah, al, zero_off, nfirst, g2);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -367,12 +233,9 @@ static bool nof_bwd3_shape(const mf_nof_desc* d, int& skip) {
   // ONE condition for the size query, the packer and the launch: the transposed embedded-input tiles are built for the
   // full 33 + 33 input block (64 packed columns); narrower blocks take the fp32 kernel (autograd.nof_backward_hip falls back)
   if (d->in_channels_xyz + d->extra_feat_dim < 64) return false;
-  skip = -1;
-  for (int l = 1; l < d->D; ++l)
-    if ((d->skip_mask >> l) & 1u) {
-      if (skip >= 0) return false;
-      skip = l;
-    }
+  skip = single_skip_layer(d->skip_mask, d->D);
+  if (skip < 0) return false;                                 // one skip layer at most
+  if (skip == 0) skip = -1;                                   // (the kernel's "none")
   return true;
 }
 
@@ -386,37 +249,28 @@ extern "C" int32_t mf_nof_pack_bwd3(const mf_nof_desc* d, void* packed, void* st
   int skip;
   if (!d || !packed) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: null argument");
   if (!nof_bwd3_shape(d, skip)) return fail(MF_E_UNSUPPORTED, "mf_nof_pack_bwd3: unsupported NoF configuration (W=%d D=%d)", d->W, d->D);
-  bf::N3PackJob job{};
+  // the forward layout of W^T (mf_layout.hpp), every k-step as (hi, lo) bf16 groups: backward layers 0 .. D-2 = trunk layers
+  // D-1 .. 1 transposed (hidden columns), then embedded columns 0..63 of layer 0 / the skip layer
+  PackJob job{};
   const int cin = d->in_channels_xyz + d->extra_feat_dim, n_head = d->use_quat ? 9 : 3;
-  long long g0 = 0;
-  for (int i = 0; i + 1 < d->D; ++i) {                       // backward layer i = trunk layer l = D-1-i, hidden columns
-    const int l = d->D - 1 - i;
-    job.W[i] = d->trunk_w[l];
-    job.ld[i] = bf::kNW + (l == skip ? cin : 0);
-    job.col0[i] = l == skip ? cin : 0;
-    job.tiles[i] = 4; job.g0[i] = g0; g0 += 4 * 16;
+  for (int i = 0; i + 1 < d->D; ++i) {
+    const int l = d->D - 1 - i, col0 = l == skip ? cin : 0;
+    if (!d->trunk_w[l]) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: missing weight pointer (backward layer %d)", i);
+    job.add(4, 16, PackBlock{d->trunk_w[l] + col0, 1, bf::kNW + col0, kPackHidden, 8, 2, bf::kNW});
   }
-  job.n_layers = d->D - 1;
-  for (int e = 0; e < (skip >= 0 ? 2 : 1); ++e) {              // embedded columns 0..63 of layer 0 / the skip layer
-    const int i = job.n_layers++, l = e == 0 ? 0 : skip;
-    job.W[i] = d->trunk_w[l];
-    job.ld[i] = l == 0 ? cin : bf::kNW + cin;
-    job.col0[i] = 0; job.tiles[i] = 2; job.g0[i] = g0; g0 += 2 * 16;
+  for (int e = 0; e < (skip >= 0 ? 2 : 1); ++e) {
+    const int l = e == 0 ? 0 : skip;
+    if (!d->trunk_w[l]) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: missing weight pointer (backward layer %d)", d->D - 1 + e);
+    job.add(2, 16, PackBlock{d->trunk_w[l], 1, l == 0 ? cin : bf::kNW + cin, kPackHidden, 8, 2, bf::kNW}).n_rows = cin;
   }
-  job.g0[job.n_layers] = g0;
-  for (int i = 0; i < job.n_layers; ++i)
-    if (!job.W[i]) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: missing weight pointer (backward layer %d)", i);
   if (!d->head_w) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: missing head weight");
-  if (cin < 64) return fail(MF_E_UNSUPPORTED, "mf_nof_pack_bwd3: needs >= 64 embedded input columns");
-  job.head_w = d->head_w; job.n_head = n_head;
-  job.res = static_cast<float*>(packed);
+  job.bf16 = 1;
+  job.res[job.n_res++] = ResCopy{d->head_w, bf::kN3Head, n_head * bf::kNW};
   job.res_floats = bf::n3_res_bytes(n_head) / 4;
-  job.panels = reinterpret_cast<unsigned*>(static_cast<char*>(packed) + bf::n3_res_bytes(n_head));
-  job.total_groups = bf::n3_groups_total(d->D, skip >= 0 ? 2 : 1);
-  if (g0 != job.total_groups) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: layout mismatch");
-  const long long slots = job.total_groups * 64 > job.res_floats ? job.total_groups * 64 : job.res_floats;
-  hipLaunchKernelGGL(bf::pack_nof_bwd3_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), job);
-  return check_launch("mf_nof_pack_bwd3");
+  job.resident = static_cast<float*>(packed);
+  job.panels = reinterpret_cast<float*>(static_cast<char*>(packed) + bf::n3_res_bytes(n_head));
+  if (job.total_groups != bf::n3_groups_total(d->D, skip >= 0 ? 2 : 1)) return fail(MF_E_INVALID, "mf_nof_pack_bwd3: layout mismatch");
+  return launch_pack(job, static_cast<hipStream_t>(stream), "mf_nof_pack_bwd3");
 }
 
 extern "C" int32_t mf_nof_backward3(const mf_nof_desc* d, const void* packed_bwd3, const mf_embedding* emb_xyz, int64_t P,
