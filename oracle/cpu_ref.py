@@ -433,7 +433,7 @@ def make_rays(H, W, focal, center, c2w, near, far, idx):
         rays_d = directions / torch.norm(directions, dim=-1, keepdim=True)
         rays_o = torch.zeros_like(directions)
     else:
-        m = torch.from_numpy(np.asarray(c2w)[:3, :4]).float()
+        m = torch.from_numpy(np.asarray(c2w)[:3, :4]).to(directions.dtype)      # (utils/camera.py:141 says .float(); the same under the fp32 default)
         rays_d = directions @ m[:, :3].T
         rays_d = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
         rays_o = m[:, 3].expand(rays_d.shape)

@@ -27,6 +27,13 @@ def relerr(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
+def pdf_per_wave_floats(nb, Mi):
+    """The LDS floats one ray's wave needs in mf_sample_pdf, as its entry point computes them (four 16-byte aligned arrays:
+    the S + M depths, bins, cdf, pdf); a workgroup is four waves and the limit 64 KiB."""
+    r4 = lambda n: (n + 3) & ~3
+    return r4(nb + 1 + Mi) + 2 * r4(nb) + r4(nb - 1)
+
+
 def _l2rel(a, b):
     a, b = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(b).detach().cpu().double()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))

@@ -152,6 +152,103 @@ def test_embedding_rows_validates_on_the_host():
     assert lib.mf_embedding_forward_rows(None, ptr, 1, 1, ptr, 64, None) == -1
 
 
+def test_bookkeeping_entry_points_validate_on_the_host():
+    """The refusals mf_sample_pdf / _merge, mf_compact_mask, mf_loss_partials / _backward, mf_knn1, mf_nof_embed_rows and
+    mf_make_rays make BEFORE any launch (every call here returns from the entry's argument checks).  Where a refusal sits
+    behind the null checks, the pointers are a dummy non-null host address: the host never dereferences them."""
+    import moco_flow_amd._lib as L
+    from helpers import pdf_per_wave_floats
+    lib = L.lib()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf)
+    INVALID, UNSUPPORTED = -1, -3
+    # mf_sample_pdf(bins, z_coarse, weights, w_stride, n_rays, n_bins, M, u, u_stride, cdf_in, z_new, inds, z_sorted, stream)
+    assert lib.mf_sample_pdf(p, None, p, 1, 4, 1, 8, p, 8, None, p, None, None, None) == INVALID and b"n_bins=1" in lib.mf_last_error()
+    assert lib.mf_sample_pdf(p, None, p, 63, 4, 64, 0, p, 0, None, p, None, None, None) == INVALID and b"M=0" in lib.mf_last_error()
+    assert lib.mf_sample_pdf(None, None, p, 63, 4, 64, 8, p, 8, None, p, None, None, None) == INVALID and b"null" in lib.mf_last_error()
+    assert lib.mf_sample_pdf(p, None, p, 63, 4, 64, 8, p, 8, None, p, None, p, None) == INVALID and b"z_coarse" in lib.mf_last_error()
+    assert lib.mf_sample_pdf(p, p, p, 63, 4, 64, 8, p, 8, None, p, None, p, None) == INVALID and b"either" in lib.mf_last_error()
+    # LDS: four waves x per_wave_floats x 4 bytes must fit 64 KiB; the first n_bins + M past it is refused (the last one
+    # inside it runs: tests/test_gpu_bookkeeping.py::test_sample_pdf_largest_accepted_shape)
+    for nb in (2, 64, 255):
+        Mi = 1
+        while pdf_per_wave_floats(nb, Mi) * 16 <= 64 * 1024:
+            Mi += 1
+        assert pdf_per_wave_floats(nb, Mi - 1) == 4096
+        assert lib.mf_sample_pdf(p, None, p, nb - 1, 4, nb, Mi, p, Mi, None, p, None, None, None) == UNSUPPORTED
+        assert b"too large" in lib.mf_last_error() and f"n_bins+M={nb + 1 + Mi}".encode() in lib.mf_last_error()
+        assert lib.mf_sample_pdf_eps(None, p, p, nb - 1, 4, nb, Mi, p, 0, None, None, None, p, 1e-3, None) == UNSUPPORTED
+    assert lib.mf_sample_pdf_merge(p, p, 4, 2, 8, p, p, None, None, None) == INVALID and b"S=2" in lib.mf_last_error()
+    # mf_compact_mask(alphas, vals_a, vals_b, n_rays, S, out_a, out_b, count, scratch, stream)
+    assert lib.mf_compact_mask(p, p, p, 4, 64, p, p, None, p, None) == INVALID and b"count / scratch" in lib.mf_last_error()
+    assert lib.mf_compact_mask(p, p, p, 4, 64, p, p, p, None, None) == INVALID
+    assert lib.mf_compact_mask(p, p, p, 4, 0, p, p, p, p, None) == INVALID and b"S=0" in lib.mf_last_error()
+    assert lib.mf_compact_mask(p, p, p, -1, 64, p, p, p, p, None) == INVALID
+    assert lib.mf_compact_mask(p, None, p, 4, 64, p, p, p, p, None) == INVALID and b"null" in lib.mf_last_error()   # out_a without vals_a
+    for n in (0, 1, 1023, 5000):
+        assert lib.mf_compact_scratch_bytes(n) == (n + 2) * 8
+    # mf_loss_partials(coarse, fine, target, n_rays, out12, means6, scratch, stream)
+    s = L.mf_loss_pass()
+    assert lib.mf_loss_partials(None, None, p, 4, p, None, p, None) == INVALID
+    assert lib.mf_loss_partials(ctypes.byref(s), None, p, 4, None, None, p, None) == INVALID
+    assert lib.mf_loss_partials(ctypes.byref(s), None, p, 4, p, None, None, None) == INVALID and b"null" in lib.mf_last_error()
+    s.rgb = p
+    assert lib.mf_loss_partials(ctypes.byref(s), None, None, 4, p, None, p, None) == INVALID and b"target" in lib.mf_last_error()
+    for plane in ("disp_local", "disp_global"):
+        s = L.mf_loss_pass()
+        setattr(s, plane, p)
+        s.n_samples = 8
+        assert lib.mf_loss_partials(ctypes.byref(s), None, p, 4, p, None, p, None) == INVALID and b"alphas" in lib.mf_last_error()
+        s.alphas, s.n_samples = p, 0
+        assert lib.mf_loss_partials(ctypes.byref(s), None, p, 4, p, None, p, None) == INVALID
+        ok = L.mf_loss_pass()
+        assert lib.mf_loss_partials(ctypes.byref(ok), ctypes.byref(s), p, 4, p, None, p, None) == INVALID     # the fine pass is checked too
+    # mf_loss_partials_backward(coarse, fine, target, n_rays, out12, g12, stream): its three refusals
+    g = L.mf_loss_grad_pass()
+    assert lib.mf_loss_partials_backward(None, None, p, 4, p, p, None) == INVALID and b"null" in lib.mf_last_error()
+    assert lib.mf_loss_partials_backward(ctypes.byref(g), None, p, 4, None, p, None) == INVALID
+    assert lib.mf_loss_partials_backward(ctypes.byref(g), None, p, 4, p, None, None) == INVALID
+    assert lib.mf_loss_partials_backward(ctypes.byref(g), None, p, -1, p, p, None) == INVALID
+    g.g_rgb = p
+    assert lib.mf_loss_partials_backward(ctypes.byref(g), None, p, 4, p, p, None) == INVALID and b"g_rgb" in lib.mf_last_error()
+    g.rgb = p
+    assert lib.mf_loss_partials_backward(ctypes.byref(g), None, None, 4, p, p, None) == INVALID and b"g_rgb" in lib.mf_last_error()
+
+    def cons():
+        c = L.mf_loss_grad_pass()
+        c.alphas, c.rays, c.z_vals, c.n_samples, c.ray_stride = p, p, p, 8, 9
+        c.recon_local, c.g_recon_local, c.recon_global, c.g_recon_global = p, p, p, p
+        return c
+    for field, bad in (("alphas", None), ("rays", None), ("z_vals", None), ("n_samples", 0), ("ray_stride", 5), ("recon_local", None),
+                       ("recon_global", None)):
+        c = cons()
+        setattr(c, field, bad)
+        assert lib.mf_loss_partials_backward(ctypes.byref(c), None, p, 4, p, p, None) == INVALID, field
+        assert b"consensus" in lib.mf_last_error(), field
+        assert lib.mf_loss_partials_backward(ctypes.byref(L.mf_loss_grad_pass()), ctypes.byref(c), p, 4, p, p, None) == INVALID, field
+    # mf_knn1(ref, V, query, Q, dist, ind, stream)
+    assert lib.mf_knn1(p, 0, p, 4, p, p, None) == INVALID and b"V=0" in lib.mf_last_error()
+    assert lib.mf_knn1(p, 4, p, -1, p, p, None) == INVALID
+    assert lib.mf_knn1(None, 4, p, 4, p, p, None) == INVALID and b"null" in lib.mf_last_error()
+    # mf_nof_embed_rows(emb_xyz, pts, ind_emb, ind_width, S, P, out, stream)
+    e = L.mf_embedding()
+    e.in_channels, e.n_freqs = 3, 6
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), p, p, 33, 64, 4, p, None) == UNSUPPORTED and b"5 frequencies" in lib.mf_last_error()
+    e.in_channels, e.n_freqs = 2, 5
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), p, p, 33, 64, 4, p, None) == UNSUPPORTED
+    e.in_channels = 3
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), p, p, 34, 64, 4, p, None) == INVALID
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), p, p, 33, 0, 4, p, None) == INVALID
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), p, None, 5, 64, 4, p, None) == INVALID
+    assert lib.mf_nof_embed_rows(None, p, p, 33, 64, 4, p, None) == INVALID
+    assert lib.mf_nof_embed_rows(ctypes.byref(e), None, None, 33, 64, 0, None, None) == 0                 # no rows: a no-op
+    # mf_make_rays(H, W, focal, cx, cy, c2w_host, near, far, idx, rays_out, stream)
+    assert lib.mf_make_rays(4, 4, 0.0, 2.0, 2.0, None, 1.0, 2.0, 0.0, p, None) == INVALID and b"focal=0" in lib.mf_last_error()
+    assert lib.mf_make_rays(-1, 4, 50.0, 2.0, 2.0, None, 1.0, 2.0, 0.0, p, None) == INVALID
+    assert lib.mf_make_rays(4, 4, 50.0, 2.0, 2.0, None, 1.0, 2.0, 0.0, None, None) == INVALID
+    assert lib.mf_make_rays(0, 4, 50.0, 2.0, 2.0, None, 1.0, 2.0, 0.0, None, None) == 0
+
+
 def test_packed_layout_sizes():
     """Packed sizes follow from the panel program: NeRF dir/27 = resident 13 KiB +
     (L0 8 + 3x32 + skip 40 + 3x32 + final 32) groups x 8 panels + extra 36 groups x 4 panels."""
