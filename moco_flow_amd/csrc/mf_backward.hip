@@ -268,12 +268,8 @@ extern "C" int32_t mf_embedding_backward(const mf_embedding* e, const float* g_e
   // wide embeddings (in_channels (2 N_freqs + 1) > 127, e.g. Embedding(4, 16)) need more than the 64 KiB a launch gets by
   // default: raise the kernel's limit up to the CU's 160 KiB, refuse beyond
   if (lds > 160 * 1024) return fail(MF_E_UNSUPPORTED, "mf_embedding_backward: %d embedded columns exceed the staged width (312)", ncols);
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(embed_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_embedding_backward: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL(embed_backward_kernel, dim3((unsigned)((P + kEmbBwdSamples - 1) / kEmbBwdSamples)), dim3(256), lds,
-                     static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_embedding_backward");
+  return launch_lds(embed_backward_kernel, (unsigned)((P + kEmbBwdSamples - 1) / kEmbBwdSamples), 256, lds, static_cast<hipStream_t>(stream), p,
+                    "mf_embedding_backward", "mf_embedding_backward", lds > 48 * 1024);
 }
 
 extern "C" int32_t mf_nerf_backward_x(const mf_nerf_desc* d, const void* packed_bwd, int64_t P, const float* g_out,
@@ -298,9 +294,5 @@ extern "C" int32_t mf_nerf_backward_x(const mf_nerf_desc* d, const void* packed_
   p.dbg = 0;
   if (const char* e = getenv("MF_DEBUG_FLAGS")) p.dbg = atoi(e);   // timing ablations only
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nerf_backward: cannot reserve %zu bytes of LDS", lds);
-  const int grid = persistent_grid((P + kTile - 1) / kTile);
-  hipLaunchKernelGGL(nerf_backward_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nerf_backward");
+  return launch_lds(nerf_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nerf_backward", "mf_nerf_backward");
 }

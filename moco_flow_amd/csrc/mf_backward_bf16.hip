@@ -237,8 +237,5 @@ extern "C" int32_t mf_nerf_backward3(const mf_nerf_desc* d, const void* packed_b
   p.ring_off = lds; p.buf_bytes = 32 * kGroupBytes; lds += 3 * p.buf_bytes;
   const int grid = persistent_grid((P + 127) / 128);
   void (*kern)(const bf::Bwd3Params) = mask ? bf::nerf_backward_kernel_x3<true> : bf::nerf_backward_kernel_x3<false>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nerf_backward3: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nerf_backward3");
+  return launch_lds(kern, grid, 256, lds, static_cast<hipStream_t>(stream), p, "mf_nerf_backward3", "mf_nerf_backward3");
 }

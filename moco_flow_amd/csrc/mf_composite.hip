@@ -134,9 +134,5 @@ extern "C" int32_t mf_composite_backward(const float* rays, int64_t ray_stride, 
   if (n_rays == 0) return MF_OK;
   CompBwdParams p{rays, ray_stride, n_rays, S, z_vals, rgbsigma, noise, activation, background, g_rgb, g_depth, g_opacity, g_rgbsigma};
   const size_t lds = (size_t)kCompWaves * 5 * S * 4;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(composite_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_composite_backward: cannot reserve %zu bytes of LDS", lds);
-  const unsigned grid = (unsigned)((n_rays + kCompWaves - 1) / kCompWaves);
-  hipLaunchKernelGGL(composite_backward_kernel, dim3(grid), dim3(64 * kCompWaves), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_composite_backward");
+  return launch_lds(composite_backward_kernel, (unsigned)((n_rays + kCompWaves - 1) / kCompWaves), 64 * kCompWaves, lds, static_cast<hipStream_t>(stream), p, "mf_composite_backward", "mf_composite_backward");
 }

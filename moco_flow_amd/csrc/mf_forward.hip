@@ -281,13 +281,8 @@ static int32_t nerf_forward_launch(const char* who, const mf_nerf_desc* d, const
   p.ring_off = (uint32_t)p.net.L.res_bytes;
   p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  const void* fn = dump ? reinterpret_cast<const void*>(nerf_forward_kernel<true>) : reinterpret_cast<const void*>(nerf_forward_kernel<false>);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-  const int grid = persistent_grid((B + kTile - 1) / kTile);
-  if (dump) hipLaunchKernelGGL(nerf_forward_kernel<true>, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  else hipLaunchKernelGGL(nerf_forward_kernel<false>, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch(who);
+  void (*kern)(NerfFwdParams) = dump ? nerf_forward_kernel<true> : nerf_forward_kernel<false>;
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, who, who);
 }
 
 extern "C" int32_t mf_nerf_forward(const mf_nerf_desc* d, const void* packed, const float* inputs, int64_t in_stride,
@@ -315,11 +310,7 @@ extern "C" int32_t mf_nof_forward(const mf_nof_desc* d, const void* packed, cons
   p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
   void (*kern)(NofFwdParams) = p.net.L.NK == 16 ? nof_forward_kernel<16> : nof_forward_kernel<8>;     // W = 256: the bare NoF() default
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nof_forward: cannot reserve %zu bytes of LDS", lds);
-  const int grid = persistent_grid((B + kTile - 1) / kTile);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nof_forward");
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward", "mf_nof_forward");
 }
 
 namespace mf {
@@ -388,12 +379,6 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   p.ring_off = lds;
   p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
   lds += 3 * p.buf_bytes;
-  const void* fn = nof ? reinterpret_cast<const void*>(points_kernel<true>) : reinterpret_cast<const void*>(points_kernel<false>);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_points_sigma: cannot reserve %u bytes of LDS", lds);
-  const int grid = persistent_grid((B + kTile - 1) / kTile);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nof) hipLaunchKernelGGL(points_kernel<true>, dim3(grid), dim3(kThreads), lds, st, p);
-  else hipLaunchKernelGGL(points_kernel<false>, dim3(grid), dim3(kThreads), lds, st, p);
-  return check_launch("mf_points_sigma");
+  void (*kern)(PointsParams) = nof ? points_kernel<true> : points_kernel<false>;
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_points_sigma", "mf_points_sigma");
 }

@@ -24,6 +24,17 @@ inline int check_launch(const char* what) {
   return MF_OK;
 }
 
+// A kernel that takes its parameter struct by value and `lds` bytes of dynamic LDS: raise its limit (`reserve` false: the size is
+// inside every launch's default), launch, report the launch (what_launch null: the caller checks after its further launches).
+template <class P>
+inline int launch_lds(void (*kern)(P), unsigned grid, unsigned threads, size_t lds, hipStream_t stream, const P& params,
+                      const char* what_reserve, const char* what_launch, bool reserve = true) {
+  if (reserve && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(MF_E_LAUNCH, "%s: cannot reserve %zu bytes of LDS", what_reserve, lds);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, params);
+  return what_launch ? check_launch(what_launch) : MF_OK;
+}
+
 int device_cus();   // mf_forward.hip
 
 // grid of a persistent launch over `work` workgroup-sized items: at most one workgroup per CU
@@ -74,27 +85,6 @@ inline int plan_ray_groups(long long n_rays, int S, int tile, uint32_t lds, int&
     if ((long long)G * c * S <= max_samples && (long long)G * c <= 64 && makespan((long long)G * c) <= base) sets = c;
   G *= sets;
   n_groups = (n_rays + G - 1) / G;
-  return MF_OK;
-}
-
-// the ReLU bit rows of a render pass's NeRF dump (n_trunk = D + 1 layers): beside dump_acts, D + 2 rows of 8 words
-inline int check_dump_mask(const mf_render_args* a, int n_trunk) {
-  if (a->dump_mask && (!a->dump_acts || a->dump_mask_stride < (int64_t)(n_trunk + 1) * 8))
-    return fail(MF_E_INVALID, "mf_render_pass: dump_mask needs dump_acts and dump_mask_stride >= 8 (D + 2) words");
-  return MF_OK;
-}
-
-// dump_nof_plane: the plane each NoF chain step of the pass writes, a permutation of 0 .. steps - 1 -> `pack`, 3 bits per step
-inline int nof_plane_pack(const mf_render_args* a, uint32_t& pack) {
-  const int nsteps = 1 + ((a->flags & MF_F_CHAIN_LOCAL) ? 1 : 0) + ((a->flags & MF_F_CHAIN_GLOBAL) ? 3 : 0);
-  uint32_t seen = 0;
-  pack = 0;
-  for (int k = 0; k < nsteps; ++k) {
-    const int pl = a->dump_nof_plane[k];
-    if (pl < 0 || pl >= nsteps || ((seen >> pl) & 1u)) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_plane must be a permutation of 0..%d", nsteps - 1);
-    seen |= 1u << pl;
-    pack |= (uint32_t)pl << (3 * k);
-  }
   return MF_OK;
 }
 

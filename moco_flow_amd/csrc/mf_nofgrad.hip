@@ -324,11 +324,7 @@ extern "C" int32_t mf_nof_points_dump(const mf_nof_desc* d, const void* packed, 
   p.ring_off = (uint32_t)p.net.L.res_bytes;
   p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_points_dump_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nof_points_dump: cannot reserve %zu bytes of LDS", lds);
-  const int grid = persistent_grid((P + kTile - 1) / kTile);
-  hipLaunchKernelGGL(nof_points_dump_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nof_points_dump");
+  return launch_lds(nof_points_dump_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_points_dump", "mf_nof_points_dump");
 }
 
 extern "C" int32_t mf_nof_forward_dump(const mf_nof_desc* d, const void* packed, const float* inputs, int64_t in_stride,
@@ -347,11 +343,7 @@ extern "C" int32_t mf_nof_forward_dump(const mf_nof_desc* d, const void* packed,
   p.ring_off = (uint32_t)p.net.L.res_bytes;
   p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_points_dump_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nof_forward_dump: cannot reserve %zu bytes of LDS", lds);
-  const int grid = persistent_grid((B + kTile - 1) / kTile);
-  hipLaunchKernelGGL(nof_points_dump_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nof_forward_dump");
+  return launch_lds(nof_points_dump_kernel, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward_dump", "mf_nof_forward_dump");
 }
 
 extern "C" int64_t mf_nof_bwd_packed_bytes(const mf_nof_desc* d) {
@@ -409,9 +401,5 @@ extern "C" int32_t mf_nof_backward(const mf_nof_desc* d, const void* packed_bwd,
   p.dbg = 0;
   if (const char* e = getenv("MF_DEBUG_FLAGS")) p.dbg = atoi(e);   // timing ablations only
   const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(nof_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nof_backward: cannot reserve %zu bytes of LDS", lds);
-  const int grid = persistent_grid((P + kTile - 1) / kTile);
-  hipLaunchKernelGGL(nof_backward_kernel, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nof_backward");
+  return launch_lds(nof_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_backward", "mf_nof_backward");
 }

@@ -310,8 +310,5 @@ extern "C" int32_t mf_nof_backward3(const mf_nof_desc* d, const void* packed_bwd
   // the forward wrote the layers' ReLU bit rows when the row has room for them (nof_eval's `masks`)
   const bool bits = stride >= (int64_t)d->D * bf::kNW + 16 + 4 * d->D;
   void (*kern)(const bf::Nof3Params) = bits ? bf::nof_backward_kernel_x3<true> : bf::nof_backward_kernel_x3<false>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_nof_backward3: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), p);
-  return check_launch("mf_nof_backward3");
+  return launch_lds(kern, grid, 256, lds, static_cast<hipStream_t>(stream), p, "mf_nof_backward3", "mf_nof_backward3");
 }

@@ -21,6 +21,7 @@
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_raypass.hpp"
 
 namespace mf {
 
@@ -47,27 +48,17 @@ struct RenderParams {
   uint32_t nof_plane_pack;     // plane of step k = (pack >> 3k) & 7   (a packed scalar: no runtime index into the kernarg)
 };
 
-// inclusive product scan across the 64 lanes of a wave
-
 template <bool MOCO, bool DUMP>
 __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
   const LaneId id;
   const NetDev nerf = p.nerf;
-#ifdef MF_TIMELINE
-  const unsigned long long tl_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  const WgClock wg;
   load_resident(nerf, id);
   if (MOCO) {
     load_resident(p.bw, id);
     if (p.flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL)) load_resident(p.fw, id);
   }
-  if (threadIdx.x < 128) {
-    // embedding tables kernarg -> LDS through the kernarg segment pointer (a runtime index into the by-value struct
-    // would make hipcc keep a scratch copy of all of `p`); published by start_program's barrier
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(RenderParams, emb_par);
-    *(float*)(smem + p.par_off + threadIdx.x * 4) = ((const __attribute__((address_space(4))) float*)ka)[threadIdx.x];
-  }
+  emb_tables_to_lds(p);
   const uint32_t par_nerf_xyz = p.par_off, par_nerf_ext = p.par_off + 128, par_nof_xyz = p.par_off + 256,
                  par_nof_ind = p.par_off + 384;
   Stream st;
@@ -121,16 +112,8 @@ __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
         const float* rp = w.rp;
         const float o[3] = {rp[0], rp[1], rp[2]};
         const float d[3] = {rp[3], rp[4], rp[5]};
-        float z;
-        if (p.z_vals) {
-          z = p.z_vals[w.ray * S + w.si];
-        } else {
-          const float nearv = rp[6], farv = rp[7], t = p.z_steps[w.si];
-          if (!p.use_disp) z = nearv * (1.f - t) + farv * t;                    // rendering.py:247
-          else z = 1.f / (1.f / nearv * (1.f - t) + 1.f / farv * t);            // rendering.py:249
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) xin[c] = o[c] + d[c] * z;                    // rendering.py:262-263
+        const float z = ray_depth(p, rp, w.ray, w.si);
+        ray_point(o, d, z, xin);
         if (w.valid && id.g == 0) {
           zbuf[w.srel] = z;
           if (MOCO) sbuf[w.srel] = make_float4(xin[0], xin[1], xin[2], 0.f);
@@ -141,24 +124,18 @@ __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
 #endif
       st.tl.stamp(2, id);
       if (MOCO) {
-        // chain program (rendering.py:270-282): step 0 bw(x,i) -> canon; local: fw(canon,i) -> recon;
-        // global: fw(canon,j) -> a; bw(a,j) -> b; fw(b,i) -> chained recon.
-        const bool loc = p.flags & MF_F_CHAIN_LOCAL, glob = p.flags & MF_F_CHAIN_GLOBAL;
-        const int nsteps = 1 + (loc ? 1 : 0) + (glob ? 3 : 0);
+        // chain program (rendering.py:270-282), roles: mf_raypass.hpp
+        const int nsteps = chain_steps(p.flags);
         float canon[3] = {0.f, 0.f, 0.f}, cur[3] = {xin[0], xin[1], xin[2]};
         for (int step = 0; step < nsteps; ++step) {
-          // role of this step: 0 = bw_i, 1 = local fw_i, 2 = fw_j, 3 = bw_j, 4 = final fw_i
-          // (chain_global implies chain_local -- checked on the host -- so role == step)
           const int role = step;
-          const bool use_fw = (role == 1 || role == 2 || role == 4);
-          const NetDev net = use_fw ? p.fw : p.bw;
+          const NetDev net = role_uses_fw(role) ? p.fw : p.bw;
           const Where w = where();
-          const float ind = w.rp[(role == 2 || role == 3) ? 9 : 8];
+          const float ind = w.rp[role_ind_column(role)];
           if (role == 1 || role == 2) { cur[0] = canon[0]; cur[1] = canon[1]; cur[2] = canon[2]; }
           // what follows this evaluation in the panel program
           const bool last = step == nsteps - 1;
-          const bool next_fw = (role + 1 == 1 || role + 1 == 2 || role + 1 == 4);
-          const NextLayer follow = last ? follow_of(nerf) : (next_fw ? follow_of(p.fw) : follow_of(p.bw));
+          const NextLayer follow = last ? follow_of(nerf) : (role_uses_fw(role + 1) ? follow_of(p.fw) : follow_of(p.bw));
           float emb[kStepsNofIn], out[3];
           nof_embed_lds(emb, cur, ind, par_nof_xyz, par_nof_ind, id.g);
           float* nof_row = nullptr;
@@ -247,79 +224,13 @@ __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
     __syncthreads();
     st.tl.stamp(6, id);
 
-    // ---- composite (rendering.py:157-192): one wave per ray, lanes over samples
-    for (int rr = id.wave; rr < ((MF_TIMING_FLAGS && (p.dbg & 8)) ? 0 : nr); rr += kWaves) {
-      const long long ray = ray0 + rr;
-      const float* rp = p.rays + ray * p.ray_stride;
-      const float dnorm = sqrtf(rp[3] * rp[3] + rp[4] * rp[4] + rp[5] * rp[5]);  // rendering.py:164
-      float carry = 1.f, acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
-      for (int base = 0; base < S; base += 64) {
-        // (opaque lane index: keeps hipcc from hoisting `plane + 4 lane` of every output plane out of the group loop
-        //  as 64-bit per-lane addresses that then sit in -- or spill from -- registers across the MFMA section)
-        int ln = id.lane;
-        asm volatile("" : "+v"(ln));
-        const int i = base + ln;
-        const bool v = i < S;
-        const int ii = v ? i : S - 1;
-        const float4 s4 = sbuf[rr * S + ii];
-        const float z = zbuf[rr * S + ii];
-        const float znext = zbuf[rr * S + (ii + 1 < S ? ii + 1 : ii)];
-        float delta = (ii == S - 1) ? 1e10f : znext - z;                       // :158-160
-        delta = delta * dnorm;
-        float sg = s4.w;
-        if (p.noise) sg = sg + p.noise[ray * S + ii];                          // :166 (pre-scaled)
-        float a;
-        if (p.activation == MF_ACT_RELU) a = fmaxf(sg, 0.f);
-        else a = sg > 20.f ? sg : log1pf(expf(sg));                            // nn.Softplus(beta=1, threshold=20)
-        float alpha = 1.f - expf(-delta * a);                                  // :170/172
-        if (!v) alpha = 0.f;
-        const float pt = v ? (1.f - alpha) + 1e-10f : 1.f;                     // :176-177
-        const float incl = wave_scan_mul_dpp(pt);
-        const float excl = wave_shr1_dpp(1.f, incl);
-        const float w = alpha * (carry * excl);                                // :178-179
-        carry = carry * wave_last(incl);
-        if (v) {
-          if (p.weights) p.weights[ray * S + i] = w;
-#ifndef MF_TIMELINE
-          if (p.alphas) p.alphas[ray * S + i] = alpha;
-#endif
-          acc_w += w;
-          acc_r += w * s4.x; acc_g += w * s4.y; acc_b += w * s4.z;
-          acc_d += w * z;
-        }
-      }
-      acc_w = wave_sum_dpp(acc_w);                                                 // :180
-      if (!sigma_only) {
-        acc_r = wave_sum_dpp(acc_r); acc_g = wave_sum_dpp(acc_g); acc_b = wave_sum_dpp(acc_b);   // :186
-        acc_d = wave_sum_dpp(acc_d);                                               // :187
-      }
-      if (id.lane == 0) {
-        if (p.opacity) p.opacity[ray] = acc_w;
-        if (!sigma_only) {
-          if (p.bg) {                                                          // :189-190
-            const float k = 1.f - acc_w;
-            acc_r = acc_r + p.bg[ray * 3 + 0] * k;
-            acc_g = acc_g + p.bg[ray * 3 + 1] * k;
-            acc_b = acc_b + p.bg[ray * 3 + 2] * k;
-          }
-          if (p.rgb) { p.rgb[ray * 3 + 0] = acc_r; p.rgb[ray * 3 + 1] = acc_g; p.rgb[ray * 3 + 2] = acc_b; }
-          if (p.depth) p.depth[ray] = acc_d;
-        }
-      }
-    }
+    composite_group<kWaves>(p, id.lane, id.wave, ray0, (MF_TIMING_FLAGS && (p.dbg & 8)) ? 0 : nr, S, sigma_only, sbuf, zbuf);
     st.tl.stamp(7, id);
     __syncthreads();
     st.tl.stamp(8, id);
   }
   wait_vm0();   // the stream runs two panels ahead: drain the LDS-DMA before the workgroup retires
-#ifdef MF_TIMELINE      // (timing builds only) every workgroup's start / end on the chip-wide 100 MHz clock, in alphas[2..3] of its last group
-  if (threadIdx.x == 0 && p.alphas && blockIdx.x < p.n_groups) {
-    const long long lastg = blockIdx.x + ((p.n_groups - 1 - blockIdx.x) / gridDim.x) * gridDim.x;
-    float* o = p.alphas + lastg * p.G * p.S;
-    o[2] = (float)(tl_rt0 & 0xFFFFFFull);
-    o[3] = (float)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);
-  }
-#endif
+  wg.stamp(p);
 }
 
 int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only);   // mf_render_bf16.hip
@@ -341,27 +252,19 @@ extern "C" int32_t mf_nof_emb_slot_features(int32_t* features80) {
   return MF_OK;
 }
 
-static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_only);
-extern "C" int32_t mf_render_pass(const mf_render_args* a, void* stream) { return render_entry(a, stream, false); }
-extern "C" int32_t mf_render_prepare(const mf_render_args* a, void* stream) { return render_entry(a, stream, true); }
-
-static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_only) {
-  if (!a || !a->nerf || !a->nerf_packed) return fail(MF_E_INVALID, "mf_render_pass: null argument");
-  if (a->n_rays < 0 || a->n_samples < 1) return fail(MF_E_INVALID, "mf_render_pass: n_rays=%lld n_samples=%d",
-                                                    (long long)a->n_rays, a->n_samples);
-  if (a->n_rays == 0) return MF_OK;
+// what every precision checks, in this order -- the fp32 layouts too: a descriptor the fp32 pass cannot take is refused as such
+// before the bf16 pass looks at it; the fp32 layouts stay in L = {nerf, bw, fw} for render_pass_f32
+static int32_t check_render_args(const mf_render_args* a, NetLayout (&L)[3]) {
   if (!a->rays || a->ray_stride < 9) return fail(MF_E_INVALID, "mf_render_pass: rays missing or ray_stride < 9");
   if (!a->z_vals && !a->z_steps) return fail(MF_E_INVALID, "mf_render_pass: need z_vals or z_steps");
   if (a->activation != MF_ACT_RELU && a->activation != MF_ACT_SOFTPLUS)
     return fail(MF_E_INVALID, "mf_render_pass: activation %d not supported", a->activation);
   if (a->precision < MF_PREC_F32 || a->precision > MF_PREC_BF16X3)
     return fail(MF_E_INVALID, "mf_render_pass: precision %d", a->precision);
-  const int bf16 = a->precision != MF_PREC_F32;
-  RenderParams p{};
-  if (!nerf_layout(*a->nerf, p.nerf.L, 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported NeRF configuration");
-  if (p.nerf.L.NK != 16) return fail(MF_E_UNSUPPORTED, "mf_render_pass: only W=256 NeRF is built");
+  if (!nerf_layout(*a->nerf, L[0], 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported NeRF configuration");
+  if (L[0].NK != 16) return fail(MF_E_UNSUPPORTED, "mf_render_pass: only W=256 NeRF is built");
   const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
-  if (dump && bf16 && a->precision != MF_PREC_BF16X3)
+  if (dump && a->precision == MF_PREC_BF16)
     return fail(MF_E_UNSUPPORTED, "mf_render_pass: the activation dump (training forward) exists in fp32 and in bf16x3");
   if (a->emb_xyz.in_channels != 3 || a->emb_xyz.n_freqs > 10)
     return fail(MF_E_UNSUPPORTED, "mf_render_pass: xyz embedding must have 3 channels and <= 10 frequencies");
@@ -381,74 +284,77 @@ static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_
     return fail(MF_E_INVALID, "mf_render_pass: chain_global without chain_local (the reference raises UnboundLocalError, rendering.py:276-280)");
   if ((a->flags & MF_F_CHAIN_GLOBAL) && a->ray_stride < 10)
     return fail(MF_E_INVALID, "mf_render_pass: chain_global needs the chained image index column (ray_stride >= 10)");
-
-  p.rays = a->rays; p.ray_stride = a->ray_stride; p.n_rays = a->n_rays; p.bg = a->background;
-  p.S = a->n_samples; p.z_vals = a->z_vals; p.z_steps = a->z_steps; p.use_disp = a->use_disp;
-  p.noise = a->noise; p.activation = a->activation; p.flags = a->flags;
-  p.nerf.packed = static_cast<const char*>(a->nerf_packed);
-  emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
-  emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16);
-  p.extra_type = a->nerf->extra_feat_type;
-  p.rgb = a->rgb; p.depth = a->depth; p.opacity = a->opacity; p.weights = a->weights; p.alphas = a->alphas;
-  p.disp_local = a->disp_local; p.disp_global = a->disp_global;
-  { const char* e = getenv("MF_DEBUG_FLAGS"); p.dbg = e ? atoi(e) : 0; }   // timing ablations only
-
-  uint32_t lds = 0;
-  p.nerf.res_lds = lds; lds += (uint32_t)p.nerf.L.res_bytes;
-  int max_groups = p.nerf.L.max_groups;
   if (moco) {
     if (!a->nof_bw_packed) return fail(MF_E_INVALID, "mf_render_pass: nof_bw_packed missing");
-    if (!nof_layout(*a->nof_bw, p.bw.L, 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported backward NoF configuration");
-    p.bw.packed = static_cast<const char*>(a->nof_bw_packed);
-    p.bw.res_lds = lds; lds += (uint32_t)p.bw.L.res_bytes;
-    if (p.bw.L.max_groups > max_groups) max_groups = p.bw.L.max_groups;
+    if (!nof_layout(*a->nof_bw, L[1], 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported backward NoF configuration");
     if (chains) {
       if (!a->nof_fw || !a->nof_fw_packed) return fail(MF_E_INVALID, "mf_render_pass: chain flags need the forward NoF");
-      if (!nof_layout(*a->nof_fw, p.fw.L, 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported forward NoF configuration");
-      p.fw.packed = static_cast<const char*>(a->nof_fw_packed);
-      p.fw.res_lds = lds; lds += (uint32_t)p.fw.L.res_bytes;
-      if (p.fw.L.max_groups > max_groups) max_groups = p.fw.L.max_groups;
+      if (!nof_layout(*a->nof_fw, L[2], 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported forward NoF configuration");
     }
     if (a->nof_emb_xyz.in_channels != 3 || a->nof_emb_xyz.n_freqs > 5 || a->nof_emb_ind.in_channels != 1 ||
         a->nof_emb_ind.n_freqs > 16)
       return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
+  }
+  return MF_OK;
+}
+
+// the fp32 pass of checked arguments: LDS placement, launch planning, the dumps' checks, launch
+static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3], hipStream_t st) {
+  const bool moco = a->nof_bw != nullptr;
+  const bool chains = a->flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL);
+  RenderParams p{};
+  fill_render_io(p, a);
+  { const char* e = getenv("MF_DEBUG_FLAGS"); p.dbg = e ? atoi(e) : 0; }   // timing ablations only
+  uint32_t lds = 0;
+  int max_groups = 0;
+  auto place = [&](NetDev& n, const NetLayout& l, const void* packed) {     // resident block at `lds`, largest panel so far
+    n.L = l; n.packed = static_cast<const char*>(packed);
+    n.res_lds = lds; lds += (uint32_t)l.res_bytes;
+    if (l.max_groups > max_groups) max_groups = l.max_groups;
+  };
+  place(p.nerf, L[0], a->nerf_packed);
+  emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
+  emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16);
+  if (moco) {
+    place(p.bw, L[1], a->nof_bw_packed);
+    if (chains) place(p.fw, L[2], a->nof_fw_packed);
     emb_table(a->nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16);
     emb_table(a->nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16);
   }
-  if (bf16) return render_pass_bf16(a, static_cast<hipStream_t>(stream), prepare_only);     // validated above; own layout / launch
-  if (prepare_only) return MF_OK;
   p.par_off = lds; lds += 512;
   p.ring_off = lds;
   p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
   lds += 3 * p.buf_bytes;
 
   if (int e = plan_ray_groups(a->n_rays, a->n_samples, kTile, lds, p.G, p.n_groups)) return e;
-  p.sbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 16;
-  p.zbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 4;
-  lds = (lds + 15u) & ~15u;
+  place_sample_buffers(p, lds);
 
-  const int grid = persistent_grid(p.n_groups);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (a->dump_acts && a->dump_stride < (int64_t)p.nerf.L.n_trunk * p.nerf.L.W + p.nerf.L.W / 2)
-    return fail(MF_E_INVALID, "mf_render_pass: dump_stride %lld too small", (long long)a->dump_stride);
-  p.dump_acts = a->dump_acts; p.dump_stride = a->dump_stride; p.dump_rgbsigma = a->dump_rgbsigma; p.dump_xyz = a->dump_xyz;
-  if (int e = check_dump_mask(a, p.nerf.L.n_trunk)) return e;
-  p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
+  if (int e = check_dump_rows(a, p.nerf.L)) return e;
+  if (int e = check_dump_mask(a, p.nerf.L)) return e;
   if (a->dump_nof_acts) {
     if (!moco || !a->dump_nof_emb || !a->dump_nof_out) return fail(MF_E_INVALID, "mf_render_pass: dump_nof_acts needs NoF models, dump_nof_emb and dump_nof_out");
     if (a->dump_nof_stride < (int64_t)p.bw.L.n_trunk * p.bw.L.W + 16 || (a->dump_nof_stride & 3))
       return fail(MF_E_INVALID, "mf_render_pass: dump_nof_stride %lld invalid", (long long)a->dump_nof_stride);
     if (a->nof_fw && (p.fw.L.n_trunk != p.bw.L.n_trunk || p.fw.L.W != p.bw.L.W))
       return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF dumps need bw and fw of the same depth and width");
-    if (a->precision != MF_PREC_F32) return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF dumps are fp32 only");
     if (int e = nof_plane_pack(a, p.nof_plane_pack)) return e;
   }
   p.dump_nof_acts = a->dump_nof_acts; p.dump_nof_stride = a->dump_nof_stride; p.dump_nof_emb = a->dump_nof_emb; p.dump_nof_out = a->dump_nof_out;
+  const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
   void (*kern)(RenderParams) =
       dump ? (moco ? render_kernel<true, true> : render_kernel<false, true>)
            : (moco ? render_kernel<true, false> : render_kernel<false, false>);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_render_pass: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, st, p);
-  return check_launch("mf_render_pass");
+  return launch_lds(kern, persistent_grid(p.n_groups), kThreads, lds, st, p, "mf_render_pass", "mf_render_pass");
 }
+
+static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_only) {
+  if (!a || !a->nerf || !a->nerf_packed) return fail(MF_E_INVALID, "mf_render_pass: null argument");
+  if (a->n_rays < 0 || a->n_samples < 1) return fail(MF_E_INVALID, "mf_render_pass: n_rays=%lld n_samples=%d", (long long)a->n_rays, a->n_samples);
+  if (a->n_rays == 0) return MF_OK;
+  NetLayout L[3];
+  if (int e = check_render_args(a, L)) return e;
+  if (a->precision != MF_PREC_F32) return render_pass_bf16(a, static_cast<hipStream_t>(stream), prepare_only);   // own layouts / launch
+  return prepare_only ? MF_OK : render_pass_f32(a, L, static_cast<hipStream_t>(stream));
+}
+extern "C" int32_t mf_render_pass(const mf_render_args* a, void* stream) { return render_entry(a, stream, false); }
+extern "C" int32_t mf_render_prepare(const mf_render_args* a, void* stream) { return render_entry(a, stream, true); }

@@ -9,6 +9,7 @@
 #include "mf_bf16.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
+#include "mf_raypass.hpp"
 
 namespace mf {
 namespace bf {
@@ -160,70 +161,6 @@ MF_D void tile_rays(int tile, int nr, int S, int& first, int& n) {
   n = s1 / S - first + 1;
 }
 
-// ---- composite (rendering.py:157-192) of a group's rays out of the LDS sample buffers: one wave per ray, lanes over samples
-template <int NW>
-MF_D void composite_group(const Params& p, const Lane& id, long long ray0, int nr, int S, bool sigma_only, const float4* sbuf, const float* zbuf) {
-    for (int rr = id.wave; rr < nr; rr += NW) {
-    const long long ray = ray0 + rr;
-    const float* rp = p.rays + ray * p.ray_stride;
-    const float dnorm = sqrtf(rp[3] * rp[3] + rp[4] * rp[4] + rp[5] * rp[5]);  // rendering.py:164
-    float carry_t = 1.f, acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
-    for (int base = 0; base < S; base += 64) {
-      // (the lane index is made opaque here: hipcc otherwise hoists `plane + 4 lane` of every output plane out of the
-      //  whole group loop as 64-bit per-lane addresses and spills them across the MFMA section)
-      int ln = id.lane;
-      asm volatile("" : "+v"(ln));
-      const int i = base + ln;
-      const bool v = i < S;
-      const int ii = v ? i : S - 1;
-      const float4 s4 = sbuf[rr * S + ii];
-      const float z = zbuf[rr * S + ii];
-      const float znext = zbuf[rr * S + (ii + 1 < S ? ii + 1 : ii)];
-      float delta = (ii == S - 1) ? 1e10f : znext - z;                       // :158-160
-      delta = delta * dnorm;
-      float sg = s4.w;
-      if (p.noise) sg = sg + p.noise[ray * S + ii];                          // :166 (pre-scaled)
-      float a;
-      if (p.activation == MF_ACT_RELU) a = fmaxf(sg, 0.f);
-      else a = sg > 20.f ? sg : log1pf(expf(sg));                            // nn.Softplus(beta=1, threshold=20)
-      float alpha = 1.f - expf(-delta * a);                                  // :170/172
-      if (!v) alpha = 0.f;
-      const float pt = v ? (1.f - alpha) + 1e-10f : 1.f;                     // :176-177
-      const float incl = wave_scan_mul_dpp(pt);
-      const float excl = wave_shr1_dpp(1.f, incl);
-      const float w = alpha * (carry_t * excl);                              // :178-179
-      carry_t = carry_t * wave_last(incl);
-      if (v) {
-        if (p.weights) p.weights[ray * S + i] = w;
-#ifndef MF_TIMELINE
-        if (p.alphas) p.alphas[ray * S + i] = alpha;
-#endif
-        acc_w += w;
-        acc_r += w * s4.x; acc_g += w * s4.y; acc_b += w * s4.z;
-        acc_d += w * z;
-      }
-    }
-    acc_w = wave_sum_dpp(acc_w);                                                 // :180
-    if (!sigma_only) {
-      acc_r = wave_sum_dpp(acc_r); acc_g = wave_sum_dpp(acc_g); acc_b = wave_sum_dpp(acc_b);   // :186
-      acc_d = wave_sum_dpp(acc_d);                                               // :187
-    }
-    if (id.lane == 0) {
-      if (p.opacity) p.opacity[ray] = acc_w;
-      if (!sigma_only) {
-        if (p.bg) {                                                          // :189-190
-          const float k = 1.f - acc_w;
-          acc_r = acc_r + p.bg[ray * 3 + 0] * k;
-          acc_g = acc_g + p.bg[ray * 3 + 1] * k;
-          acc_b = acc_b + p.bg[ray * 3 + 2] * k;
-        }
-        if (p.rgb) { p.rgb[ray * 3 + 0] = acc_r; p.rgb[ray * 3 + 1] = acc_g; p.rgb[ray * 3 + 2] = acc_b; }
-        if (p.depth) p.depth[ray] = acc_d;
-      }
-    }
-  }
-}
-
 // X3: MF_PREC_BF16X3 (mf_bf16.hpp: every matrix product as a three-product split, heads on fp32 accumulators): 4 waves,
 // one per SIMD, 128-sample tiles; else 8 waves, two per SIMD, 256-sample tiles
 // DUMP (X3 && !MOCO): the training forward -- every sample's layer activations, (rgb, sigma) and input point are stored
@@ -234,21 +171,13 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void render_kernel
   constexpr int NW = X3 ? 4 : kWaves;
   constexpr int TILE = NW * kWaveSamples;
   const Lane id;
-#ifdef MF_TIMELINE
-  const unsigned long long tl_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  const WgClock wg;
   load_resident<NW>(p.nerf, id);
   if (MOCO) {
     load_resident<NW>(p.bw, id);
     if (p.flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL)) load_resident<NW>(p.fw, id);
   }
-  if (threadIdx.x < 128) {
-    // the embedding tables go kernarg -> LDS through the kernarg segment pointer: indexing the by-value struct with
-    // a runtime index would make hipcc keep a private (scratch) copy of all of `p`
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Params, emb_par);
-    *(float*)(smem + p.par_off + threadIdx.x * 4) = ((const __attribute__((address_space(4))) float*)ka)[threadIdx.x];
-  }
+  emb_tables_to_lds(p);
   const uint32_t par_nerf_xyz = p.par_off, par_nerf_ext = p.par_off + 128, par_nof_xyz = p.par_off + 256;
   StreamT<NW> st;
   st.tl.start(p.alphas, id);
@@ -297,17 +226,9 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void render_kernel
       const float* rp = p.rays + ray * p.ray_stride;
       const float o[3] = {rp[0], rp[1], rp[2]};
       const float d[3] = {rp[3], rp[4], rp[5]};
-      float z;
-      if (p.z_vals) {
-        z = p.z_vals[ray * S + si];
-      } else {
-        const float nearv = rp[6], farv = rp[7], t = p.z_steps[si];
-        if (!p.use_disp) z = nearv * (1.f - t) + farv * t;                    // rendering.py:247
-        else z = 1.f / (1.f / nearv * (1.f - t) + 1.f / farv * t);            // rendering.py:249
-      }
+      const float z = ray_depth(p, rp, ray, si);
       float x[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) x[c] = o[c] + d[c] * z;                      // rendering.py:262-263
+      ray_point(o, d, z, x);
 
 #ifdef MF_TIMELINE
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]));
@@ -315,33 +236,28 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void render_kernel
       st.tl.stamp(2, id);
       float xin[3] = {x[0], x[1], x[2]};      // what the canonical NeRF sees
       if (MOCO) {
-        // chain program (rendering.py:270-282): step 0 bw(x,i) -> canon; local: fw(canon,i) -> recon;
-        // global: fw(canon,j) -> a; bw(a,j) -> b; fw(b,i) -> chained recon.
+        // chain program (rendering.py:270-282), roles: mf_raypass.hpp
         const bool loc = p.flags & MF_F_CHAIN_LOCAL, glob = p.flags & MF_F_CHAIN_GLOBAL;
-        const int nsteps = 1 + (loc ? 1 : 0) + (glob ? 3 : 0);
+        const int nsteps = chain_steps(p.flags);
         float canon[3] = {0.f, 0.f, 0.f}, cur[3] = {x[0], x[1], x[2]};
         float dl = 0.f, dg = 0.f;
         for (int step = 0; step < nsteps; ++step) {
-          // role of this step: 0 = bw_i, 1 = local fw_i, 2 = fw_j, 3 = bw_j, 4 = final fw_i
           const int role = step;
-          const bool use_fw = (role == 1 || role == 2 || role == 4);
-          const Net net = use_fw ? p.fw : p.bw;
-          // per-ray bias of this (network, image index): rows bw(i), fw(i), fw(j), bw(j) of the table (the final fw(i) is
-          // row 1), staged in LDS one evaluation ahead
+          const Net net = role_uses_fw(role) ? p.fw : p.bw;
+          // per-ray bias of this (network, image index): row role_bias_row(role) of the table, staged in LDS one evaluation ahead
           int tf, tn;
           tile_rays<TILE>(tile, nr, S, tf, tn);
           LdsRayBias rb{p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes + (uint32_t)(rr - tf) * (uint32_t)(p.rb_layers * 512)};
           ++seq;
           if (role == 1 || role == 2) { cur[0] = canon[0]; cur[1] = canon[1]; cur[2] = canon[2]; }
           const bool last = step == nsteps - 1;
-          const bool next_fw = (role + 1 == 1 || role + 1 == 2 || role + 1 == 4);
-          const Next follow = last ? first_of<16, kKsNerfXyz, X3, NF0>(p.nerf) : first_of<8, kKsNofXyz, true, NP2, TN, NPH, NPS>(next_fw ? p.fw : p.bw);
+          const Next follow = last ? first_of<16, kKsNerfXyz, X3, NF0>(p.nerf) : first_of<8, kKsNofXyz, true, NP2, TN, NPH, NPS>(role_uses_fw(role + 1) ? p.fw : p.bw);
           u32x4 nhi[kKsNofXyz], nmid[TN == 3 ? kKsNofXyz : 1], nlo[kKsNofXyz];
           float out[3];
           if constexpr (X3) nof_embed_t<false, TN, kNofHalfX3>(nhi, reinterpret_cast<u32x4(&)[kKsNofXyz]>(nmid), nlo, cur, par_nof_xyz, id.h, p.pow2 & 4);
           else nof_embed<true>(nhi, nlo, cur, par_nof_xyz, id.h, p.pow2 & 4);
           auto stage_next = [&] {
-            if (!last) stage_raybias<NW>(p, ray0 + tf, tn, role + 1 == 4 ? 1 : role + 1, p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes, id);
+            if (!last) stage_raybias<NW>(p, ray0 + tf, tn, role_bias_row(role + 1), p.rb_off + (uint32_t)(seq & 1) * p.rb_buf_bytes, id);
           };
           if constexpr (X3 && DUMP) {
             // training forward: what autograd.NofPointsDumped's backward reads, per chain step (step-major planes; the embedded
@@ -456,20 +372,13 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void render_kernel
     __syncthreads();
     st.tl.stamp(6, id);
 
-    composite_group<NW>(p, id, ray0, nr, S, sigma_only, sbuf, zbuf);
+    composite_group<NW>(p, id.lane, id.wave, ray0, nr, S, sigma_only, sbuf, zbuf);
     st.tl.stamp(7, id);
     __syncthreads();
     st.tl.stamp(8, id);
   }
   wait_vm0();   // the stream runs two panels ahead: drain the LDS-DMA before the workgroup retires
-#ifdef MF_TIMELINE      // (timing builds only) every workgroup's start / end on the chip-wide 100 MHz clock, in alphas[2..3] of its last group
-  if (threadIdx.x == 0 && p.alphas && blockIdx.x < p.n_groups) {
-    const long long lastg = blockIdx.x + ((p.n_groups - 1 - blockIdx.x) / gridDim.x) * gridDim.x;
-    float* o = p.alphas + lastg * p.G * p.S;
-    o[2] = (float)(tl_rt0 & 0xFFFFFFull);
-    o[3] = (float)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);
-  }
-#endif
+  wg.stamp(p);
 }
 
 // sigma (and the canonical position) of free points in bf16 mode: the lattice / SMPL-point query of mf_forward.hip's
@@ -503,11 +412,7 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void points_kernel
   load_resident<NW>(p.nerf, id);
   if (NOF) load_resident<NW>(p.bw, id);
   if (NOF && !PERPT) stage_raybias<NW>(p.raybias, 1, p.rb_layers, 0, 1, 0, p.rb_off, id);
-  if (threadIdx.x < 128) {
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(PointsParamsBf, emb_par);
-    *(float*)(smem + p.par_off + threadIdx.x * 4) = ((const __attribute__((address_space(4))) float*)ka)[threadIdx.x];
-  }
+  emb_tables_to_lds(p);
   const uint32_t par_nerf_xyz = p.par_off, par_nof_xyz = p.par_off + 256;
   StreamT<NW> st;
   st.tl.start(nullptr, id);
@@ -577,7 +482,6 @@ __global__ __launch_bounds__(X3 ? 256 : kThreads, X3 ? 1 : 2) void points_kernel
   wait_vm0();
 }
 
-// combination c of a ray-bias table: network (packed buffer + layout) and the index column it reads
 // largest panel of a network in groups when its trunk tiles stream several per panel (the fast mode's <TPP0, TPPH, TPPS>:
 // layer 0, hidden-only layers, skip layers; the NoF's head / the NeRF's extra_encoding tiles are one panel each)
 static int fast_panel_groups(const NetLayout& L, bool is_nof, int tpp0, int tpph, int tpps) {
@@ -590,14 +494,6 @@ static int fast_panel_groups(const NetLayout& L, bool is_nof, int tpp0, int tpph
 }
 static int nof_panel_groups(const NetLayout& L, bool x3) {
   return x3 ? fast_panel_groups(L, true, 1, 1, 1) : fast_panel_groups(L, true, bf::kNofTpp0, bf::kNofTppH, bf::kNofTppS);
-}
-
-static void raybias_combo(RayBiasParams& r, int c, const void* packed, const NetLayout& L, int col) {
-  const char* base = static_cast<const char*>(packed);
-  r.bias[c] = reinterpret_cast<const float*>(base) + L.off_bias_trunk;
-  r.wind[c] = reinterpret_cast<const float*>(base + L.res_bytes + L.panel_bytes);
-  r.emb_mask[c] = L.emb_mask;
-  r.col[c] = col;
 }
 
 // a network of a pass: its packed buffer, its resident block at LDS offset `lds` (advanced past the block), depth D, aux steps
@@ -613,13 +509,71 @@ static Net net_at(const NetLayout& L, const void* packed, int D, int aux, uint32
   return n;
 }
 
+// embedding table t of a pass (emb_par[t], and bit t of pow2: its frequencies are exactly 2^k)
+template <class P>
+static void set_emb_table(P& p, int t, const mf_embedding& e) {
+  if (emb_table(e, p.emb_par[t], p.emb_par[t] + 16)) p.pow2 |= 1 << t;
+}
+
+// The networks of a bf16 / bf16x3 pass: layouts -> L = {nerf, bw, fw}, resident blocks from LDS offset 0 (nerf -> p.nerf, bw -> p.bw,
+// fw -> *fw_net; bw, fw may be null), the NoFs' embedding tables, the tables' LDS copy, the ring of the largest panel; `lds`: bytes
+// placed.  Returns 0, or 1 + the index of the network whose configuration is not built (the caller words the refusal).
+struct NofSrc { const mf_nof_desc* desc; const void* packed; };
+template <class P>
+static int place_networks(P& p, Net* fw_net, int prec, const mf_nerf_desc* nerf, const void* nerf_packed, NofSrc bw_src, NofSrc fw_src,
+                          const mf_embedding* nof_emb_xyz, const mf_embedding* nof_emb_ind, NetLayout (&L)[3], uint32_t& lds) {
+  const bool x3 = prec == MF_PREC_BF16X3;
+  const mf_nof_desc *bw = bw_src.desc, *fw = fw_src.desc;
+  const void *bw_packed = bw_src.packed, *fw_packed = fw_src.packed;
+  NetLayout &Ln = L[0], &Lb = L[1], &Lf = L[2];
+  if (!nerf_layout(*nerf, Ln, prec)) return 1;
+  lds = 0;
+  p.nerf = net_at(Ln, nerf_packed, Ln.n_trunk - 1, Ln.extra_steps, lds);
+  int max_groups = x3 ? Ln.max_groups : fast_panel_groups(Ln, false, kNerfTpp0, kNerfTppH, kNerfTppS);
+  if (bw) {
+    if (!nof_layout(*bw, Lb, prec)) return 2;
+    p.bw = net_at(Lb, bw_packed, Lb.n_trunk, Lb.n_head, lds);
+    if (nof_panel_groups(Lb, x3) > max_groups) max_groups = nof_panel_groups(Lb, x3);
+    if (fw) {
+      if (!nof_layout(*fw, Lf, prec)) return 3;
+      *fw_net = net_at(Lf, fw_packed, Lf.n_trunk, Lf.n_head, lds);
+      if (nof_panel_groups(Lf, x3) > max_groups) max_groups = nof_panel_groups(Lf, x3);
+    }
+    set_emb_table(p, 2, *nof_emb_xyz);
+    set_emb_table(p, 3, *nof_emb_ind);
+  }
+  p.par_off = lds; lds += 512;
+  p.ring_off = lds;
+  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
+  lds += 3 * p.buf_bytes;
+  return MF_OK;
+}
+
+// the per-entry bias table of `n_combos` combinations (network, index column) -> out, see nof_raybias_kernel; emb_ind: emb_par[3]
+struct RbCombo { const void* packed; const NetLayout* L; int col; };
+static void launch_raybias(const RbCombo* combo, int n_combos, int n_layers, const float* ind, long long ind_stride, float ind_scalar,
+                           long long n_entries, const float* emb_ind, void* out, hipStream_t st) {
+  RayBiasParams r{};
+  r.ind = ind; r.ind_stride = ind_stride; r.ind_scalar = ind_scalar; r.n_entries = n_entries; r.n_combos = n_combos; r.n_layers = n_layers;
+  for (int c = 0; c < n_combos; ++c) {
+    const char* base = static_cast<const char*>(combo[c].packed);
+    const NetLayout& L = *combo[c].L;
+    r.bias[c] = reinterpret_cast<const float*>(base) + L.off_bias_trunk;
+    r.wind[c] = reinterpret_cast<const float*>(base + L.res_bytes + L.panel_bytes);
+    r.emb_mask[c] = L.emb_mask; r.col[c] = combo[c].col;
+  }
+  for (int k = 0; k < 16; ++k) { r.freq[k] = emb_ind[k]; r.weight[k] = emb_ind[16 + k]; }
+  r.out = static_cast<float*>(out);
+  hipLaunchKernelGGL(nof_raybias_kernel, dim3((unsigned)((n_entries + kRbEntries - 1) / kRbEntries), n_combos), dim3(256), 0, st, r);
+}
+
 }  // namespace bf
 
-// combinations (network, index value) and embedded layers per network of a bf16 pass with NoF; 0 combos = no table
+// combinations (network, index column) and embedded layers per network of a bf16 pass with NoF; 0 combos = no table
 static void raybias_shape(const mf_render_args* a, int& combos, int& layers) {
   combos = layers = 0;
   if (!a->nof_bw) return;
-  combos = (a->flags & MF_F_CHAIN_GLOBAL) ? 4 : ((a->flags & MF_F_CHAIN_LOCAL) ? 2 : 1);
+  combos = chain_bias_rows(a->flags);
   layers = __builtin_popcount(1u | a->nof_bw->skip_mask);
 }
 
@@ -629,39 +583,26 @@ int64_t render_workspace_bytes_bf16(const mf_render_args* a) {
   return (int64_t)a->n_rays * combos * layers * 128 * 4;
 }
 
-// called by mf_render_pass / mf_render_prepare (mf_render.hip) after argument validation, precision == MF_PREC_BF16.
+// called by mf_render_pass / mf_render_prepare (mf_render.hip) after argument validation, precision MF_PREC_BF16 | MF_PREC_BF16X3.
 // prepare_only: fill the workspace (the per-ray NoF bias table) and return; else: the fused launch, which reads it.
 int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only) {
   using namespace bf;
   Params p{};
-  NetLayout Ln, Lb, Lf;
-  const int prec = a->precision;                // MF_PREC_BF16 | MF_PREC_BF16X3
-  const bool x3 = prec == MF_PREC_BF16X3;
-  if (!nerf_layout(*a->nerf, Ln, prec)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported NeRF configuration (bf16: W = 256)");
+  NetLayout L[3];
+  const NetLayout &Lb = L[1], &Lf = L[2];
+  const bool x3 = a->precision == MF_PREC_BF16X3;
   const bool moco = a->nof_bw != nullptr;
   const bool chains = a->flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL);
-  p.rays = a->rays; p.ray_stride = a->ray_stride; p.n_rays = a->n_rays; p.bg = a->background;
-  p.S = a->n_samples; p.z_vals = a->z_vals; p.z_steps = a->z_steps; p.use_disp = a->use_disp;
-  p.noise = a->noise; p.activation = a->activation; p.flags = a->flags;
-  p.extra_type = a->nerf->extra_feat_type;
-  p.pow2 = (emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16) ? 1 : 0) | (emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16) ? 2 : 0);
-  p.rgb = a->rgb; p.depth = a->depth; p.opacity = a->opacity; p.weights = a->weights; p.alphas = a->alphas;
-  p.disp_local = a->disp_local; p.disp_global = a->disp_global;
-
+  uint32_t lds;
+  if (int e = place_networks(p, &p.fw, a->precision, a->nerf, a->nerf_packed, {a->nof_bw, a->nof_bw_packed},
+                             {chains ? a->nof_fw : nullptr, a->nof_fw_packed}, &a->nof_emb_xyz, &a->nof_emb_ind, L, lds))
+    return fail(MF_E_UNSUPPORTED, e == 1 ? "mf_render_pass: unsupported NeRF configuration (bf16: W = 256)"
+                                         : (e == 2 ? "mf_render_pass: unsupported backward NoF configuration" : "mf_render_pass: unsupported forward NoF configuration"));
+  fill_render_io(p, a);
+  set_emb_table(p, 0, a->emb_xyz);
+  set_emb_table(p, 1, a->emb_extra);
   const int tile_samples = x3 ? 4 * bf::kWaveSamples : bf::kTile;      // x3: 4 waves per workgroup
-  uint32_t lds = 0;
-  p.nerf = net_at(Ln, a->nerf_packed, Ln.n_trunk - 1, Ln.extra_steps, lds);
-  int max_groups = x3 ? Ln.max_groups : fast_panel_groups(Ln, false, bf::kNerfTpp0, bf::kNerfTppH, bf::kNerfTppS);
   if (moco) {
-    if (!nof_layout(*a->nof_bw, Lb, prec)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported backward NoF configuration");
-    p.bw = net_at(Lb, a->nof_bw_packed, Lb.n_trunk, Lb.n_head, lds);
-    if (bf::nof_panel_groups(Lb, x3) > max_groups) max_groups = bf::nof_panel_groups(Lb, x3);
-    if (chains) {
-      if (!nof_layout(*a->nof_fw, Lf, prec)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported forward NoF configuration");
-      p.fw = net_at(Lf, a->nof_fw_packed, Lf.n_trunk, Lf.n_head, lds);
-      if (bf::nof_panel_groups(Lf, x3) > max_groups) max_groups = bf::nof_panel_groups(Lf, x3);
-    }
-    p.pow2 |= (emb_table(a->nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16) ? 4 : 0) | (emb_table(a->nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16) ? 8 : 0);
     // the per-ray bias table (image-index block of the NoFs' embedded-input layers), one small launch in front
     int combos, layers;
     raybias_shape(a, combos, layers);
@@ -674,25 +615,14 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
     if (a->n_rays > 0x7fffffffLL) return fail(MF_E_UNSUPPORTED, "mf_render_pass(bf16): too many rays for one launch");
     p.raybias = static_cast<const float*>(a->workspace);
     p.rb_combos = combos; p.rb_layers = layers;
-    if (a->n_rays > 0 && prepare_only) {
-      RayBiasParams r{};
-      r.ind = a->rays; r.ind_stride = a->ray_stride; r.n_entries = a->n_rays; r.n_combos = combos; r.n_layers = layers;
-      raybias_combo(r, 0, a->nof_bw_packed, Lb, 8);
-      if (chains) {
-        raybias_combo(r, 1, a->nof_fw_packed, Lf, 8);
-        raybias_combo(r, 2, a->nof_fw_packed, Lf, 9);
-        raybias_combo(r, 3, a->nof_bw_packed, Lb, 9);
-      }
-      for (int k = 0; k < 16; ++k) { r.freq[k] = p.emb_par[3][k]; r.weight[k] = p.emb_par[3][16 + k]; }
-      r.out = static_cast<float*>(a->workspace);
-      hipLaunchKernelGGL(nof_raybias_kernel, dim3((unsigned)((a->n_rays + kRbEntries - 1) / kRbEntries), combos), dim3(256), 0, st, r);
+    if (prepare_only) {
+      RbCombo cb[4];      // row c of the table is what chain role c reads
+      for (int c = 0; c < combos; ++c)
+        cb[c] = role_uses_fw(c) ? RbCombo{a->nof_fw_packed, &Lf, role_ind_column(c)} : RbCombo{a->nof_bw_packed, &Lb, role_ind_column(c)};
+      launch_raybias(cb, combos, layers, a->rays, a->ray_stride, 0.f, a->n_rays, p.emb_par[3], a->workspace, st);
     }
   }
   if (prepare_only) return moco ? check_launch("mf_render_prepare") : MF_OK;
-  p.par_off = lds; lds += 512;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
   if (moco) {
     // two buffers of per-ray bias rows: a tile of T samples touches at most ((T - 1) / S) + 2 rays
     const int r_max = (tile_samples - 1) / a->n_samples + 2;
@@ -705,20 +635,14 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
   }
 
   if (int e = plan_ray_groups(a->n_rays, a->n_samples, tile_samples, lds, p.G, p.n_groups)) return e;
-  p.sbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 16;
-  p.zbuf_off = lds; lds += (uint32_t)(p.G * p.S) * 4;
-  lds = (lds + 15u) & ~15u;
+  place_sample_buffers(p, lds);
 
-  const int grid = persistent_grid(p.n_groups);
   const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
   if (dump) {      // (validated by the caller: bf16x3)
-    if (a->dump_acts && a->dump_stride < (int64_t)Ln.n_trunk * Ln.W + Ln.W / 2)
-      return fail(MF_E_INVALID, "mf_render_pass: dump_stride %lld too small", (long long)a->dump_stride);
+    if (int e = check_dump_rows(a, L[0])) return e;
     if (a->dump_acts && ((a->dump_stride & 3) || (reinterpret_cast<uintptr_t>(a->dump_acts) & 15)))
       return fail(MF_E_INVALID, "mf_render_pass(bf16x3): dump_acts must be 16-byte aligned with a stride that is a multiple of 4 floats");
-    p.dump_acts = a->dump_acts; p.dump_stride = a->dump_stride; p.dump_rgbsigma = a->dump_rgbsigma; p.dump_xyz = a->dump_xyz;
-    if (int e = check_dump_mask(a, Ln.n_trunk)) return e;
-    p.dump_mask = a->dump_mask; p.dump_mask_stride = a->dump_mask_stride;
+    if (int e = check_dump_mask(a, L[0])) return e;
     if (a->dump_nof_acts) {
       // the chain's evaluations: rows [h_1 .. h_D | T padded to 16] (no ReLU bit words, no embedded-input plane: mf_nof_embed_rows)
       if (!moco || !a->dump_nof_out) return fail(MF_E_INVALID, "mf_render_pass(bf16x3): dump_nof_acts needs NoF models and dump_nof_out");
@@ -732,10 +656,7 @@ int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only)
   void (*kern)(const Params) = x3 ? (moco ? (dump ? render_kernel_bf16<true, true, true> : render_kernel_bf16<true, true>)
                                           : (dump ? render_kernel_bf16<false, true, true> : render_kernel_bf16<false, true>))
                                   : (moco ? render_kernel_bf16<true, false> : render_kernel_bf16<false, false>);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_render_pass: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(x3 ? 256 : kThreads), lds, st, p);
-  return check_launch("mf_render_pass(bf16)");
+  return launch_lds(kern, persistent_grid(p.n_groups), x3 ? 256 : kThreads, lds, st, p, "mf_render_pass", "mf_render_pass(bf16)");
 }
 
 // called by mf_points_sigma_p (mf_forward.hip) after argument validation, precision == MF_PREC_BF16
@@ -750,19 +671,15 @@ int points_sigma_bf16(int prec, const mf_nerf_desc* nerf, const void* nerf_packe
                       int64_t workspace_bytes, hipStream_t st) {
   using namespace bf;
   PointsParamsBf p{};
-  NetLayout Ln, Lb;
+  NetLayout L[3];
+  const NetLayout& Lb = L[1];
   const bool x3 = prec == MF_PREC_BF16X3;
   if (x3 && nof && ind) return fail(MF_E_UNSUPPORTED, "mf_points_sigma(bf16x3): per-point image indices are not built (use MF_PREC_F32 or MF_PREC_BF16)");
-  if (!nerf_layout(*nerf, Ln, prec)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NeRF configuration (bf16: W = 256)");
-  uint32_t lds = 0;
-  p.nerf = net_at(Ln, nerf_packed, Ln.n_trunk - 1, Ln.extra_steps, lds);
-  int max_groups = x3 ? Ln.max_groups : fast_panel_groups(Ln, false, bf::kNerfTpp0, bf::kNerfTppH, bf::kNerfTppS);
-  p.pow2 = emb_table(*emb_xyz, p.emb_par[0], p.emb_par[0] + 16) ? 1 : 0;
+  uint32_t lds;
+  if (int e = place_networks(p, nullptr, prec, nerf, nerf_packed, {nof, nof_packed}, {nullptr, nullptr}, nof_emb_xyz, nof_emb_ind, L, lds))
+    return fail(MF_E_UNSUPPORTED, e == 1 ? "mf_points_sigma: unsupported NeRF configuration (bf16: W = 256)" : "mf_points_sigma: unsupported NoF configuration");
+  set_emb_table(p, 0, *emb_xyz);
   if (nof) {
-    if (!nof_layout(*nof, Lb, prec)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NoF configuration");
-    p.bw = net_at(Lb, nof_packed, Lb.n_trunk, Lb.n_head, lds);
-    if (nof_panel_groups(Lb, x3) > max_groups) max_groups = nof_panel_groups(Lb, x3);
-    p.pow2 |= (emb_table(*nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16) ? 4 : 0) | (emb_table(*nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16) ? 8 : 0);
     // per-point (ind given) or single (ind_scalar) bias of the NoF's embedded-input layers, see nof_raybias_kernel
     const int64_t need = points_workspace_bytes_bf16(nof, ind != nullptr, B);
     if (!workspace || workspace_bytes < need)
@@ -773,29 +690,17 @@ int points_sigma_bf16(int prec, const mf_nerf_desc* nerf, const void* nerf_packe
     p.raybias = static_cast<const float*>(workspace);
     p.rb_layers = Lb.n_emb_layers;
     if (B > 0) {
-      RayBiasParams r{};
-      r.ind = ind; r.ind_stride = 1; r.ind_scalar = ind_scalar; r.n_entries = entries; r.n_combos = 1; r.n_layers = Lb.n_emb_layers;
-      raybias_combo(r, 0, nof_packed, Lb, 0);
-      for (int k = 0; k < 16; ++k) { r.freq[k] = p.emb_par[3][k]; r.weight[k] = p.emb_par[3][16 + k]; }
-      r.out = static_cast<float*>(workspace);
-      hipLaunchKernelGGL(nof_raybias_kernel, dim3((unsigned)((entries + kRbEntries - 1) / kRbEntries), 1), dim3(256), 0, st, r);
+      const RbCombo cb{nof_packed, &Lb, 0};
+      launch_raybias(&cb, 1, Lb.n_emb_layers, ind, 1, ind_scalar, entries, p.emb_par[3], workspace, st);
     }
+    p.rb_off = lds; lds += (uint32_t)round_up((int64_t)Lb.n_emb_layers * 512, 1024);
   }
-  p.par_off = lds; lds += 512;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
-  if (nof) { p.rb_off = lds; lds += (uint32_t)round_up((int64_t)Lb.n_emb_layers * 512, 1024); }
   p.xyz = xyz; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.sigma = sigma; p.canon = canon;
   const int tile = x3 ? 4 * bf::kWaveSamples : bf::kTile;
-  const int grid = persistent_grid((B + tile - 1) / tile);
   void (*kern)(const PointsParamsBf) = x3 ? (nof ? points_kernel_bf16<true, false, true> : points_kernel_bf16<false, false, true>)
                                           : (nof ? (ind ? points_kernel_bf16<true, true> : points_kernel_bf16<true, false>)
                                                  : points_kernel_bf16<false>);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(MF_E_LAUNCH, "mf_points_sigma: cannot reserve %u bytes of LDS", lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(x3 ? 256 : kThreads), lds, st, p);
-  return check_launch("mf_points_sigma(bf16)");
+  return launch_lds(kern, persistent_grid((B + tile - 1) / tile), x3 ? 256 : kThreads, lds, st, p, "mf_points_sigma", "mf_points_sigma(bf16)");
 }
 
 }  // namespace mf

@@ -800,9 +800,7 @@ extern "C" int32_t mf_weight_grads_p(int32_t precision, const mf_wgrad_item* ite
     if (const char* e = getenv("MF_DEBUG_FLAGS")) p.dbg = atoi(e);
     if (P > 0) {
       void (*kern)(WgParams) = k ? wgrad_kernel<true> : wgrad_kernel<false>;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_k[k]) != hipSuccess)
-        return fail(MF_E_LAUNCH, "mf_weight_grads: cannot reserve %d bytes of LDS", lds_k[k]);
-      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(kThreads), lds_k[k], st, p);
+      if (int e = launch_lds(kern, p.grid, kThreads, lds_k[k], st, p, "mf_weight_grads", nullptr)) return e;   // (checked below)
     }
     int maxf = 0;
     for (int i = 0; i < sp.n[k]; ++i) if (wg_out_floats(p.it[i].shape) > maxf) maxf = wg_out_floats(p.it[i].shape);
