@@ -559,6 +559,35 @@ int32_t mf_mc_count(const float* vol, int64_t n0, int64_t n1, int64_t n2, float 
 int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
                    const void* scratch, float* verts, int64_t* tris, void* stream);
 
+/* ---- validation metrics: models/metrics.py:4-22 (mse, psnr, ssim), called per validation image by val_step
+ * (trainer_moco_flow.py:453-473).  The reference's ssim is kornia 0.6.5's kornia.metrics.ssim.ssim(img1, img2, window_size,
+ * max_val=1.0, eps=1e-12); kornia is not available to this project: KORNIA RESTATED from the published algorithm (as
+ * oracle/kornia_restated.py does for the quaternion functions), unpinned against kornia itself.
+ *
+ * mf_ssim: a, b = fp32 (B, C, H, W) images, each addressed through four ELEMENT strides (host int64[4]: B, C, H, W), so a
+ * contiguous CHW tensor and the view rows.view(H, W, 3).permute(2, 0, 1)[None] of rendered (H W, 3) rows both work uncopied.
+ * Window g[i] = exp(-(i - ws/2)^2 / (2 1.5^2)) normalised to sum 1 (float64 on the host), 2-D window g x g,
+ * window_size odd in 3..11; border = reflect padding without repeating the edge by ws/2 (F.pad(mode='reflect'): needs
+ * ws/2 < min(H, W), else MF_E_INVALID).  Per pixel, f = the windowed sum: mu1 = f(a), mu2 = f(b), s1 = f(a^2) - mu1^2,
+ * s2 = f(b^2) - mu2^2, s12 = f(ab) - mu1 mu2, C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2,
+ *   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2) + eps)
+ * (the moments are accumulated in float64 and the map is rounded to fp32 once: the formula's own fp32 evaluation is
+ * 2e-4 .. 9e-4 off in flat regions through the cancellation in s1, s2).
+ * map_out: (B, C, H, W) contiguous fp32 or NULL; sums: device double[2] = [sum of ssim, sum of (a - b)^2] over all B C H W
+ * elements, reduced in a fixed order through scratch (mf_ssim_scratch_bytes bytes): bit-identical from run to run.
+ * B C H W = 0 launches nothing and writes zeros to sums.  One kernel launch plus the finishing workgroup. */
+int64_t mf_ssim_scratch_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int32_t mf_ssim(const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int64_t B, int64_t C,
+                int64_t H, int64_t W, int32_t window_size, float max_val, float eps, float* map_out, double* sums,
+                void* scratch, void* stream);
+/* mf_sqerr: the reduction behind mse / psnr (metrics.py:4-13).  a, b: n contiguous fp32 elements; mask: one uint8 per row of
+ * row_len elements (row_len = 1: elementwise; 3: the per-ray mask value[valid_mask] applies to (N, 3); row_len divides n), or
+ * NULL = all.  out2: device double[2] = [sum of (a - b)^2 over the selected elements, their count]; same fixed-order
+ * reduction through scratch (mf_sqerr_scratch_bytes(n) bytes).  n = 0 writes zeros. */
+int64_t mf_sqerr_scratch_bytes(int64_t n);
+int32_t mf_sqerr(const float* a, const float* b, int64_t n, const uint8_t* mask, int64_t row_len, double* out2,
+                 void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SYMBOLS = {
     "mf_mc_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_mc_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp]),
     "mf_mc_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
+    "mf_ssim_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mf_ssim": (C.c_int32, [_fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                            C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),
+    "mf_sqerr_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "mf_sqerr": (C.c_int32, [_fp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()
