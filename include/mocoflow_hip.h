@@ -588,6 +588,48 @@ int64_t mf_sqerr_scratch_bytes(int64_t n);
 int32_t mf_sqerr(const float* a, const float* b, int64_t n, const uint8_t* mask, int64_t row_len, double* out2,
                  void* scratch, void* stream);
 
+/* ---- pictures: utils/vis_utils.py:28-43 (visualize_depth), reached through decode_results (trainer_moco_flow.py:475-482) by
+ * val_step, visualize_frame, visualize_video and visualize_spherical_poses; and the sheet those assemble with torch.cat and
+ * hand to torchvision's save_image (trainer_moco_flow.py:609-623, 644-659).  The reference copies the depth plane to the
+ * host, normalises it with numpy, colours it with cv2.applyColorMap and copies it back; here everything stays on the device
+ * and nothing synchronises.
+ * The index arithmetic is vis_utils.py:34-40 in its own fp32, one rounding per operation:
+ *   v = nan_to_num(d)   (NaN -> nan_value, +inf -> FLT_MAX, -inf -> -FLT_MAX: numpy's defaults)
+ *   den = (ma - mi) + 1e-8     x = (v - mi) / den     i = (uint8) trunc(255 x)
+ * ONE DEVIATION: where astype(np.uint8) is undefined -- 255 x outside [0, 256) or NaN, which takes a caller-given range
+ * narrower than the data, or infinities in the data -- i is clamped to 0 .. 255 (NaN: 0).
+ * lut: 768 device bytes, (256, 3); entry i colours index i, column c becomes channel c of the result.  The package's Jet
+ * table (moco_flow_amd/vis.py: colormap_lut) is OPENCV RESTATED: cv2 is not available to this project, the table restates
+ * OpenCV's COLORMAP_JET from its closed form (with applyColorMap's BGR order read as RGB, as the reference does) and is
+ * UNPINNED AGAINST cv2 ITSELF; a caller who has cv2 passes its table.
+ *
+ * mf_depth_range: out2 = device fp32 [min, max] of nan_to_num(depth) over n contiguous fp32 elements, exact (min and max do
+ * not depend on the order); per-workgroup partials in scratch (mf_depth_range_scratch_bytes(n) bytes), one launch plus the
+ * finishing workgroup.  n = 0 writes [0, 0] and launches nothing else. */
+int64_t mf_depth_range_scratch_bytes(int64_t n);
+int32_t mf_depth_range(const float* depth, int64_t n, float nan_value, float* out2, void* scratch, void* stream);
+/* mf_depth_colormap (vis_utils.py:39-43): range2 = device fp32 [mi, ma], written by mf_depth_range or by the caller;
+ * out_planar[c n + p] = lut[3 i(p) + c] / 255.0f (fp32 division) for c = 0, 1, 2: the (3, H, W) tensor ToTensor returns. */
+int32_t mf_depth_colormap(const float* depth, int64_t n, const float* range2, float nan_value, const uint8_t* lut,
+                          float* out_planar, void* stream);
+/* mf_frame_sheet: up to 8 panels of H x W pixels side by side along the width, one launch (the torch.cat(..., dim=-1) of
+ * trainer_moco_flow.py:614-621, 650-655 and save_image's quantisation).
+ *   kind 0  rgb rows (H W, 3) as render_rays / render_image return them, or the ground-truth rgbs: pixel p, channel c at
+ *           rows[3 p + c]
+ *   kind 1  a depth plane (H W), colour-mapped as mf_depth_colormap does with the range range2s[2 k], range2s[2 k + 1] of
+ *           panel k and the panel's nan_value
+ * out_u8: (H, n_panels W, 3) bytes, u = (uint8) clamp(v 255 + 0.5, 0, 255) in fp32 as torchvision.utils.save_image
+ * quantises (NaN: 0); a colour-mapped pixel is its LUT byte.  out_planar: the float (3, H, n_panels W) stack (rgb values
+ * as they are, colour-mapped ones lut / 255).  Either output may be NULL, not both.  range2s and lut may be NULL without a
+ * depth panel.  32-bit indexing: H W n_panels 3 must be below 2^31, else MF_E_INVALID.  H W = 0 launches nothing. */
+typedef struct mf_sheet_panel {
+  const float* rows;
+  int32_t kind;
+  float nan_value;
+} mf_sheet_panel;
+int32_t mf_frame_sheet(const mf_sheet_panel* panels /* host */, int32_t n_panels, int64_t H, int64_t W, const float* range2s,
+                       const uint8_t* lut, uint8_t* out_u8, float* out_planar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

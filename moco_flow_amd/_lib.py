@@ -58,6 +58,14 @@ class mf_wgrad_item(C.Structure):
 MF_WG_MAX_ITEMS = 32
 
 
+class mf_sheet_panel(C.Structure):
+    _fields_ = [("rows", _fp), ("kind", C.c_int32), ("nan_value", C.c_float)]
+
+
+MF_SHEET_MAX_PANELS = 8
+MF_PANEL_RGB, MF_PANEL_DEPTH = 0, 1
+
+
 class mf_loss_pass(C.Structure):
     _fields_ = [("rgb", _fp), ("alphas", _fp), ("disp_local", _fp), ("disp_global", _fp), ("n_samples", C.c_int32)]
 
@@ -169,6 +177,10 @@ SYMBOLS = {
                             C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),
     "mf_sqerr_scratch_bytes": (C.c_int64, [C.c_int64]),
     "mf_sqerr": (C.c_int32, [_fp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp]),
+    "mf_depth_range_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "mf_depth_range": (C.c_int32, [_fp, C.c_int64, C.c_float, _fp, _fp, _fp]),
+    "mf_depth_colormap": (C.c_int32, [_fp, C.c_int64, _fp, C.c_float, _fp, _fp, _fp]),
+    "mf_frame_sheet": (C.c_int32, [C.POINTER(mf_sheet_panel), C.c_int32, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()
