@@ -41,7 +41,9 @@ extern "C" {
  *     mf_nof_pack_bwd3); ReLU bit rows: four panels per word, written for NoF evaluations (behind T) and under NoF; mf_sample_pdf_eps
  * 16: MF_PREC_BF16X3 packs the NoF as IEEE-half (hi, lo) pairs at 2^5 x (three products per k-step on the f16 matrix
  *     instruction, biases at 2^10 x); MF_PREC_BF16X3 training forward under NoF (mf_render_args.dump_nof_acts / dump_nof_out without
- *     dump_nof_emb) + mf_nof_embed_rows */
+ *     dump_nof_emb) + mf_nof_embed_rows
+ * additive entries since, version unchanged: mf_mc_scratch_bytes / mf_mc_count / mf_mc_emit; mf_ssim, mf_sqerr (+ their
+ *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -301,6 +303,27 @@ int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf, const voi
  * the image index does not go through the matrix pipe (see mf_render_args.workspace).  0 for MF_PREC_F32 / no NoF. */
 int64_t mf_points_sigma_workspace_bytes(int32_t precision, const mf_nof_desc* nof, int32_t per_point_ind, int64_t B);
 
+/* Fused point radiance query, fp32: the whole of NeRF.forward on free points in one launch -- xyz (B,3) -> [backward NoF at
+ * image index ind] -> positional encoding -> NeRF trunk -> sigma head, xyz_encoding_final, extra_encoding over the extra block
+ * embedded in registers, rgb sigmoid.  out (B,4) = [rgb | raw sigma], the column order of NeRF.forward (models/nerf.py:101;
+ * 16-byte aligned); canon (B,3), optional: the point after the backward flow (ignored without a NoF).  Replaces the module
+ * sequence NoF -> Embedding -> zero-pad -> Embedding of the extra block -> NeRF.forward and its padded (B, 63 + extra) rows.
+ * The extra block follows nerf_inference (models/rendering.py:133-142) by nerf->extra_feat_type:
+ *   MF_EXTRA_DIR : view_dirs (B,3) through emb_extra (3 channels, <= 4 frequencies), embedded AS GIVEN (nothing normalises
+ *                  it), zero-padded to extra_feat_dim;
+ *   MF_EXTRA_IND : the image index -- ind (B,) or, ind == NULL, ind_scalar: the value that also drives the NoF, as ray
+ *                  column 8 does in render_rays -- through emb_extra (1 channel, <= 2 frequencies);
+ *   MF_EXTRA_NONE: no extra block; emb_extra and view_dirs are not read.
+ * nof == NULL: canonical-space query.  Returns MF_E_INVALID for a null argument (emb_extra / view_dirs where the type needs
+ * them) and for an extra embedding of the wrong channel count, with more frequencies than above or wider than
+ * extra_feat_dim; MF_E_UNSUPPORTED for a NeRF the packed layout does not cover or with W != 256, an xyz embedding other than
+ * (3, <= 10 frequencies), a NoF the layout does not cover.  B == 0: MF_OK, nothing launched. */
+int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf_packed, const mf_embedding* emb_xyz,
+                           const mf_embedding* emb_extra, const mf_nof_desc* nof, const void* nof_packed,
+                           const mf_embedding* nof_emb_xyz, const mf_embedding* nof_emb_ind, const float* xyz,
+                           const float* view_dirs, const float* ind, float ind_scalar, int64_t B, float* out,
+                           float* canon, void* stream);
+
 /* ---- one rendering pass: nof_inference* + nerf_inference of models/rendering.py:49-192 as
  * called from render_rays (rendering.py:262-314 coarse, 329-373 fine) -------------------- */
 enum {
@@ -558,6 +581,15 @@ int32_t mf_mc_count(const float* vol, int64_t n0, int64_t n1, int64_t n2, float 
  * tris (T, 3) int64 vertex indices, sized by the counts pass 1 wrote (NULL only when that count is 0). */
 int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,
                    const void* scratch, float* verts, int64_t* tris, void* stream);
+/* Unit normals (V, 3) of vertices verts (V, 3) given in index coordinates of vol (mf_mc_emit's), from the volume's gradient;
+ * one thread per vertex (tests/mesh_color_oracle.py restates it in numpy).  v = vol, or max(vol, 0) with clamp_zero.
+ * Lattice gradient g(q): per axis the central difference (v(q + e_k) - v(q - e_k)) / 2, on a border face the one-sided
+ * difference.  Vertex p: i_k = min(floor(p_k), n_k - 1) (0 for p_k < 0 or NaN), t_k = p_k - i_k; a = the axis of the largest
+ * t_k (ties: the lowest axis), t = t_a; g(p) = (1 - t) g(i) + t g(i + e_a), or g(i) when t is 0 (a lattice point).  The
+ * normal is -g / ||g||: toward decreasing density, out of the body; the zero vector where ||g|| is 0 or g is not finite.
+ * fp32 throughout.  Shape rules of mf_mc_count; V == 0: MF_OK, nothing launched. */
+int32_t mf_mc_normals(const float* vol, int64_t n0, int64_t n1, int64_t n2, int32_t clamp_zero, const float* verts, int64_t V,
+                      float* normals, void* stream);
 
 /* ---- validation metrics: models/metrics.py:4-22 (mse, psnr, ssim), called per validation image by val_step
  * (trainer_moco_flow.py:453-473).  The reference's ssim is kornia 0.6.5's kornia.metrics.ssim.ssim(img1, img2, window_size,

@@ -14,8 +14,8 @@ from .factory import get_loss, get_model
 from .losses import MSELoss
 from .nerf import NeRF
 from .nof import NoF
-from .points import query_sigma
-from .mesh import export_obj, extract_mesh, marching_cubes
+from .points import query_radiance, query_sigma
+from .mesh import export_obj, export_ply, extract_colored_mesh, extract_mesh, marching_cubes, vertex_normals
 from . import metrics
 from .metrics import image_metrics
 from . import vis
@@ -25,5 +25,5 @@ from .rendering import render_rays, resample_merge, sample_pdf, set_precision, s
 
 __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "sample_pdf",
            "resample_merge", "set_precision", "set_wgrad_precision", "set_dx_precision", "set_train_forward_precision", "query_sigma", "MSELoss",
-           "marching_cubes", "extract_mesh", "export_obj", "metrics", "image_metrics",
+           "marching_cubes", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
            "vis", "visualize_depth", "decode_results", "frame_sheet", "write_png"]

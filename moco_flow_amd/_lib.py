@@ -146,6 +146,9 @@ SYMBOLS = {
     "mf_points_sigma_p": (C.c_int32, [C.c_int32, C.POINTER(mf_nerf_desc), _fp, C.POINTER(mf_embedding), C.POINTER(mf_nof_desc), _fp,
                                       C.POINTER(mf_embedding), C.POINTER(mf_embedding), _fp, _fp, C.c_float, C.c_int64,
                                       _fp, _fp, _fp, C.c_int64, _fp]),
+    "mf_points_radiance": (C.c_int32, [C.POINTER(mf_nerf_desc), _fp, C.POINTER(mf_embedding), C.POINTER(mf_embedding),
+                                       C.POINTER(mf_nof_desc), _fp, C.POINTER(mf_embedding), C.POINTER(mf_embedding), _fp, _fp,
+                                       _fp, C.c_float, C.c_int64, _fp, _fp, _fp]),
     "mf_sample_pdf_merge": (C.c_int32, [_fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
     "mf_sample_pdf": (C.c_int32, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64,
                                   _fp, _fp, _fp, _fp, _fp]),
@@ -172,6 +175,7 @@ SYMBOLS = {
     "mf_mc_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_mc_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp]),
     "mf_mc_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
+    "mf_mc_normals": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp]),
     "mf_ssim_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mf_ssim": (C.c_int32, [_fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),

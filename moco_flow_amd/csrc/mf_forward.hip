@@ -9,6 +9,7 @@
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_raypass.hpp"
 
 namespace mf {
 
@@ -220,6 +221,90 @@ __global__ __launch_bounds__(kThreads, 2) void points_kernel(PointsParams p) {
   wait_vm0();
 }
 
+// ------------------------------------------------------------------ fused point radiance query
+// The whole of NeRF.forward on free points -- what colouring a mesh vertex or filling an RGBA lattice spells as NoF ->
+// Embedding -> zero-pad -> Embedding of the extra block -> NeRF.forward with padded (B, 63 + extra) temporaries -- as one
+// launch: xyz -> [bw NoF(ind)] -> encode in registers -> NeRF trunk -> sigma head, xyz_encoding_final, extra_encoding over
+// the extra block embedded in registers (nerf_inference, rendering.py:133-142: the view direction as given, or the image
+// index), rgb sigmoid.  A sibling of points_kernel (same persistent tile loop), so that kernel's code stays what it was.
+struct RadianceParams {
+  NetDev nerf, nof;
+  float emb_par[4][32];    // [nerf xyz, nerf extra, nof xyz, nof ind] x (freq[16], weight[16]) -> LDS at par_off as in the render
+  uint32_t par_off;        // pass (emb_eval_lds): read from the kernarg, four tables cost the NoF variant 16 bytes of scratch
+  int extra_type;          // MF_EXTRA_*
+  const float* xyz;        // (B,3)
+  const float* dirs;       // (B,3) view directions (MF_EXTRA_DIR)
+  const float* ind;        // (B,) per-point image index, or null -> ind_scalar
+  float ind_scalar;
+  long long B;
+  float* out;              // (B,4) [rgb | raw sigma]: the columns of NeRF.forward (nerf.py:101)
+  float* canon;            // (B,3) or null: the point after the backward flow
+  uint32_t ring_off, buf_bytes;
+};
+
+template <bool NOF>
+__global__ __launch_bounds__(kThreads, 2) void radiance_kernel(RadianceParams p) {
+  const LaneId id;
+  load_resident(p.nerf, id);
+  if (NOF) load_resident(p.nof, id);
+  emb_tables_to_lds(p);
+  const uint32_t par_nerf_xyz = p.par_off, par_nerf_ext = p.par_off + 128, par_nof_xyz = p.par_off + 256,
+                 par_nof_ind = p.par_off + 384;
+  Stream st;
+  CarryT<kPD> carry;
+  st.ring = p.ring_off;
+  st.buf_bytes = p.buf_bytes;
+  st.dbg = 0;
+  st.keep2 = 0;
+  const NextLayer prog_first = NOF ? follow_of(p.nof) : follow_of(p.nerf);
+  if (NOF) start_program(p.nof, st, carry, id);
+  else start_program(p.nerf, st, carry, id);
+  const long long ntiles = (p.B + kTile - 1) / kTile;
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    // (the point index is rebuilt from an opaque lane index at each use, as in nerf_forward_kernel: neither it nor the
+    //  64-bit addresses formed from it are carried across the MFMA sections)
+    auto where = [&](bool& valid) {
+      int jo = id.j;
+      asm volatile("" : "+v"(jo));
+      const long long b = tile * kTile + id.wave * kWaveSamples + jo;
+      valid = b < p.B;
+      return valid ? b : p.B - 1;
+    };
+    bool valid;
+    long long bb = where(valid);
+    float x[3] = {p.xyz[bb * 3 + 0], p.xyz[bb * 3 + 1], p.xyz[bb * 3 + 2]};
+    if (NOF) {
+      const float ind = p.ind ? p.ind[bb] : p.ind_scalar;
+      float emb[kStepsNofIn], out[3];
+      nof_embed_lds(emb, x, ind, par_nof_xyz, par_nof_ind, id.g);
+      nof_eval<>(p.nof, emb, x, st, carry, id, follow_of(p.nerf), out);
+      x[0] = out[0]; x[1] = out[1]; x[2] = out[2];
+      bb = where(valid);
+      if (valid && id.g == 0 && p.canon) {
+        p.canon[bb * 3 + 0] = x[0]; p.canon[bb * 3 + 1] = x[1]; p.canon[bb * 3 + 2] = x[2];
+      }
+    }
+    float embx[kStepsNerfXyz], ext[kStepsExtraMax];
+    emb_eval_lds<3, 10>(embx, x, par_nerf_xyz, id.g);
+#pragma unroll
+    for (int e = BlkXyz10::SLOTS; e < kStepsNerfXyz; ++e) embx[e] = 0.f;
+#pragma unroll
+    for (int e = 0; e < kStepsExtraMax; ++e) ext[e] = 0.f;
+    if (p.extra_type == MF_EXTRA_DIR) {
+      const float dd[3] = {p.dirs[bb * 3 + 0], p.dirs[bb * 3 + 1], p.dirs[bb * 3 + 2]};
+      emb_eval_lds<3, 4>(ext, dd, par_nerf_ext, id.g);                                        // rendering.py:138-142
+    } else if (p.extra_type == MF_EXTRA_IND) {
+      const float iv[1] = {p.ind ? p.ind[bb] : p.ind_scalar};
+      emb_eval_lds<1, 2>(ext, iv, par_nerf_ext, id.g);                                        // rendering.py:133-137
+    }
+    float sigma, rgb[3] = {0.f, 0.f, 0.f};
+    nerf_eval<16>(p.nerf, embx, ext, false, st, carry, id, prog_first, sigma, rgb);
+    bb = where(valid);
+    if (valid && id.g == 0) *reinterpret_cast<float4*>(p.out + bb * 4) = make_float4(rgb[0], rgb[1], rgb[2], sigma);
+  }
+  wait_vm0();
+}
+
 int device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -381,4 +466,58 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   lds += 3 * p.buf_bytes;
   void (*kern)(PointsParams) = nof ? points_kernel<true> : points_kernel<false>;
   return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_points_sigma", "mf_points_sigma");
+}
+
+extern "C" int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf_packed, const mf_embedding* emb_xyz,
+                                      const mf_embedding* emb_extra, const mf_nof_desc* nof, const void* nof_packed,
+                                      const mf_embedding* nof_emb_xyz, const mf_embedding* nof_emb_ind, const float* xyz,
+                                      const float* view_dirs, const float* ind, float ind_scalar, int64_t B, float* out,
+                                      float* canon, void* stream) {
+  if (!nerf || !nerf_packed || !emb_xyz || (B > 0 && (!xyz || !out)))
+    return fail(MF_E_INVALID, "mf_points_radiance: null argument");
+  if (B < 0) return fail(MF_E_INVALID, "mf_points_radiance: B=%lld", (long long)B);
+  if (reinterpret_cast<uintptr_t>(out) % 16) return fail(MF_E_INVALID, "mf_points_radiance: out must be 16-byte aligned");
+  RadianceParams p{};
+  if (!nerf_layout(*nerf, p.nerf.L) || p.nerf.L.NK != 16)
+    return fail(MF_E_UNSUPPORTED, "mf_points_radiance: unsupported NeRF configuration");
+  if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 10)
+    return fail(MF_E_UNSUPPORTED, "mf_points_radiance: xyz embedding must have 3 channels and <= 10 frequencies");
+  p.extra_type = nerf->extra_feat_type;
+  if (p.extra_type == MF_EXTRA_DIR) {
+    if (!emb_extra || (B > 0 && !view_dirs)) return fail(MF_E_INVALID, "mf_points_radiance: a \"dir\" NeRF needs emb_extra and view_dirs");
+    if (emb_extra->in_channels != 3 || emb_extra->n_freqs < 0 || emb_extra->n_freqs > 4 ||
+        3 * (2 * emb_extra->n_freqs + 1) > nerf->extra_feat_dim)
+      return fail(MF_E_INVALID, "mf_points_radiance: dir embedding must have 3 channels, <= 4 frequencies and fit extra_feat_dim");
+  } else if (p.extra_type == MF_EXTRA_IND) {
+    if (!emb_extra) return fail(MF_E_INVALID, "mf_points_radiance: an \"ind\" NeRF needs emb_extra");
+    if (emb_extra->in_channels != 1 || emb_extra->n_freqs < 0 || emb_extra->n_freqs > 2 ||
+        (2 * emb_extra->n_freqs + 1) > nerf->extra_feat_dim)
+      return fail(MF_E_INVALID, "mf_points_radiance: ind embedding must have 1 channel, <= 2 frequencies and fit extra_feat_dim");
+  }
+  uint32_t lds = 0;
+  p.nerf.packed = static_cast<const char*>(nerf_packed);
+  p.nerf.res_lds = lds; lds += (uint32_t)p.nerf.L.res_bytes;
+  int max_groups = p.nerf.L.max_groups;
+  emb_table(*emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
+  if (p.extra_type != MF_EXTRA_NONE) emb_table(*emb_extra, p.emb_par[1], p.emb_par[1] + 16);
+  if (nof) {
+    if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_radiance: NoF arguments missing");
+    if (!nof_layout(*nof, p.nof.L)) return fail(MF_E_UNSUPPORTED, "mf_points_radiance: unsupported NoF configuration");
+    if (nof_emb_xyz->in_channels != 3 || nof_emb_xyz->n_freqs > 5 || nof_emb_ind->in_channels != 1 || nof_emb_ind->n_freqs > 16)
+      return fail(MF_E_UNSUPPORTED, "mf_points_radiance: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
+    p.nof.packed = static_cast<const char*>(nof_packed);
+    p.nof.res_lds = lds; lds += (uint32_t)p.nof.L.res_bytes;
+    if (p.nof.L.max_groups > max_groups) max_groups = p.nof.L.max_groups;
+    emb_table(*nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16);
+    emb_table(*nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16);
+  }
+  if (B == 0) return MF_OK;
+  p.par_off = lds; lds += 512;
+  p.xyz = xyz; p.dirs = view_dirs; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.out = out; p.canon = nof ? canon : nullptr;
+  p.ring_off = lds;
+  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
+  lds += 3 * p.buf_bytes;
+  void (*kern)(RadianceParams) = nof ? radiance_kernel<true> : radiance_kernel<false>;
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_points_radiance",
+                    "mf_points_radiance");
 }

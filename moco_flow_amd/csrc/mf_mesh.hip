@@ -259,6 +259,73 @@ void mc_bind(McParams& p, void* scratch) {
   p.map = reinterpret_cast<int*>(base + 24LL * p.nblocks);
 }
 
+// ---- vertex normals from the volume (mf_mc_normals): one thread per vertex, a gather of at most 12 values
+struct NormalsParams {
+  const float* vol;
+  int n0, n1, n2;
+  long long S;                  // n1 n2
+  int clamp_zero;
+  const float* verts;           // (V, 3) index coordinates
+  long long V;
+  float* normals;               // (V, 3)
+};
+
+__device__ __forceinline__ float vol_at(const NormalsParams& p, int i, int j, int k) {
+  const float v = p.vol[i * p.S + (long long)j * p.n2 + k];
+  return (p.clamp_zero && v < 0.f) ? 0.f : v;
+}
+
+// gradient at the lattice point (i, j, k): central differences, one-sided on a border face (every side >= 2)
+__device__ __forceinline__ void lattice_gradient(const NormalsParams& p, int i, int j, int k, float g[3]) {
+  const int i0 = i > 0 ? i - 1 : i, i1 = i < p.n0 - 1 ? i + 1 : i;
+  const int j0 = j > 0 ? j - 1 : j, j1 = j < p.n1 - 1 ? j + 1 : j;
+  const int k0 = k > 0 ? k - 1 : k, k1 = k < p.n2 - 1 ? k + 1 : k;
+  const float d0 = vol_at(p, i1, j, k) - vol_at(p, i0, j, k);
+  const float d1 = vol_at(p, i, j1, k) - vol_at(p, i, j0, k);
+  const float d2 = vol_at(p, i, j, k1) - vol_at(p, i, j, k0);
+  g[0] = i1 - i0 == 2 ? d0 * 0.5f : d0;
+  g[1] = j1 - j0 == 2 ? d1 * 0.5f : d1;
+  g[2] = k1 - k0 == 2 ? d2 * 0.5f : d2;
+}
+
+// lattice cell index of a coordinate: min(floor(x), n - 1), and 0 for anything below 0 or not a number (never out of bounds)
+__device__ __forceinline__ int cell_of(float x, int n) {
+  if (!(x >= 0.f)) return 0;
+  const float f = floorf(x);
+  return f >= (float)(n - 1) ? n - 1 : (int)f;
+}
+
+__global__ __launch_bounds__(kThreads) void mc_normals_kernel(const NormalsParams p) {
+  const long long v = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (v >= p.V) return;
+  const float x0 = p.verts[v * 3 + 0], x1 = p.verts[v * 3 + 1], x2 = p.verts[v * 3 + 2];
+  const int i = cell_of(x0, p.n0), j = cell_of(x1, p.n1), k = cell_of(x2, p.n2);
+  const float t0 = x0 - (float)i, t1 = x1 - (float)j, t2 = x2 - (float)k;
+  int a = 0;                                                    // the axis of the vertex's edge: largest t, ties to the lowest
+  float t = t0;
+  if (t1 > t) { a = 1; t = t1; }
+  if (t2 > t) { a = 2; t = t2; }
+  float g[3];
+  lattice_gradient(p, i, j, k, g);
+  if (t > 0.f) {                                                // (t == 0: a lattice point; NaN: the gradient at the cell index)
+    const int i2 = a == 0 && i < p.n0 - 1 ? i + 1 : i, j2 = a == 1 && j < p.n1 - 1 ? j + 1 : j, k2 = a == 2 && k < p.n2 - 1 ? k + 1 : k;
+    float h[3];
+    lattice_gradient(p, i2, j2, k2, h);
+    const float s = 1.f - t;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] = s * g[c] + t * h[c];
+  }
+  const float len2 = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+  float n[3] = {0.f, 0.f, 0.f};
+  if (len2 > 0.f && len2 < __builtin_inff()) {                  // ||g|| == 0 or g not finite: the zero vector
+    const float inv = 1.f / sqrtf(len2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) n[c] = -(g[c] * inv);
+  }
+  float* o = p.normals + v * 3;
+  o[0] = n[0]; o[1] = n[1]; o[2] = n[2];
+}
+
 bool vec_rows(const McParams& p) { return p.n2 % 4 == 0 && reinterpret_cast<uintptr_t>(p.vol) % 16 == 0; }
 
 }  // namespace mc
@@ -300,4 +367,18 @@ extern "C" int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t 
   if (vec_rows(p)) hipLaunchKernelGGL(mc_emit_kernel<true>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
   else hipLaunchKernelGGL(mc_emit_kernel<false>, dim3(p.nblocks), dim3(kThreads), 0, s, p);
   return check_launch("mf_mc_emit");
+}
+
+extern "C" int32_t mf_mc_normals(const float* vol, int64_t n0, int64_t n1, int64_t n2, int32_t clamp_zero, const float* verts,
+                                 int64_t V, float* normals, void* stream) {
+  McParams shape{};
+  const int rc = mc_shape("mf_mc_normals", n0, n1, n2, shape);
+  if (rc != MF_OK) return rc;
+  if (V < 0 || V > (int64_t)INT_MAX * kThreads) return fail(MF_E_INVALID, "mf_mc_normals: V=%lld", (long long)V);
+  if (V == 0) return MF_OK;
+  if (!vol || !verts || !normals) return fail(MF_E_INVALID, "mf_mc_normals: null argument");
+  NormalsParams p{vol, shape.n0, shape.n1, shape.n2, shape.S, clamp_zero ? 1 : 0, verts, V, normals};
+  hipLaunchKernelGGL(mc_normals_kernel, dim3((unsigned)((V + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), p);
+  return check_launch("mf_mc_normals");
 }

@@ -1,6 +1,7 @@
 """Fused point queries: what the trainers spell as forward_nof -> embed ->
 zero-pad -> NeRF(sigma_only=True) per 10 000-point chunk (trainer_moco_flow.py:146-187, 500-526;
-trainer_nerf.py:215-245) as ONE launch over all points (mf_points_sigma)."""
+trainer_nerf.py:215-245) as ONE launch over all points (mf_points_sigma), and the same for the whole of
+NeRF.forward -- colour and density of free points (mf_points_radiance)."""
 import ctypes as C
 
 import torch
@@ -52,3 +53,70 @@ def query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof=None, nof_embeddings=None,
                                           C.byref(fi) if fi is not None else None, L.ptr(x), L.ptr(ind_t), ind_s, B,
                                           L.ptr(sigma), L.ptr(canon), L.ptr(ws), need, L.current_stream(dev)), "mf_points_sigma")
     return (sigma, canon) if return_canonical else sigma
+
+
+def _point_index(ind, B, dev, who):
+    """``ind`` as query_sigma takes it -> (per-point (B,) tensor | None, scalar)."""
+    if torch.is_tensor(ind):
+        ind_t = ind.detach().float().reshape(-1).contiguous().to(dev)
+        if ind_t.numel() == 1:
+            return None, float(ind_t.item())
+        if ind_t.numel() != B:
+            raise RuntimeError(f"{who}: ind must have 1 or {B} elements")
+        return ind_t, 0.0
+    return None, float(ind)
+
+
+def query_radiance(xyz, nerf, nerf_embeddings, view_dirs=None, ind=None, bw_nof=None, nof_embeddings=None,
+                   return_canonical=False):
+    """xyz (B,3) observation-space points -> (B,4) [rgb | raw sigma] of the canonical NeRF, the columns of NeRF.forward
+    (models/nerf.py:101), fp32, one launch (mf_points_radiance).  Inference only.
+
+    nerf_embeddings = [xyz, ind | None, dir | None] as render_rays takes it; the extra block follows nerf_inference
+    (models/rendering.py:133-142): a "dir" NeRF embeds ``view_dirs`` (B,3) as given (nothing normalises it), an "ind" NeRF
+    the image index ``ind``, a "none" NeRF nothing.  bw_nof / nof_embeddings=[xyz, ind] / ind: optional backward flow at
+    image index ``ind`` -- a python float in [-1,1) for all points, or a (1,) / (B,) / (B,1) tensor -- the same value an
+    "ind" NeRF embeds (render_rays reads ray column 8 for both).  ``return_canonical``: also the (B,3) points after the
+    flow (None without a NoF)."""
+    if nerf.extra_feat_type == "latent_code":
+        raise NotImplementedError("NeRF model does not support latent code yet!!!")
+    L.require_gpu(xyz, "query_radiance")
+    x = xyz.detach().float().contiguous()
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise RuntimeError(f"query_radiance: xyz must be (B, 3), got {tuple(xyz.shape)}")
+    B = x.shape[0]
+    dev = x.device
+    kind = nerf.extra_feat_type
+    dirs = eext = None
+    if kind == "dir":
+        if view_dirs is None:
+            raise RuntimeError('query_radiance: a "dir" NeRF needs view_dirs (B, 3)')
+        if tuple(view_dirs.shape) != (B, 3):
+            raise RuntimeError(f"query_radiance: view_dirs must be ({B}, 3), got {tuple(view_dirs.shape)}")
+        if len(nerf_embeddings) < 3 or nerf_embeddings[2] is None:
+            raise RuntimeError('query_radiance: a "dir" NeRF needs nerf_embeddings[2], the dir embedding')
+        dirs = view_dirs.detach().float().contiguous().to(dev)
+        eext = nerf_embeddings[2].descriptor()
+    elif kind == "ind":
+        if len(nerf_embeddings) < 2 or nerf_embeddings[1] is None:
+            raise RuntimeError('query_radiance: an "ind" NeRF needs nerf_embeddings[1], the ind embedding')
+        eext = nerf_embeddings[1].descriptor()
+    if (kind == "ind" or bw_nof is not None) and ind is None:
+        raise RuntimeError('query_radiance: an "ind" NeRF and a NoF need the image index ind')
+    ind_t, ind_s = _point_index(ind, B, dev, "query_radiance") if ind is not None else (None, 0.0)
+    out = torch.empty((B, 4), device=dev, dtype=torch.float32)
+    canon = torch.empty((B, 3), device=dev, dtype=torch.float32) if (return_canonical and bw_nof is not None) else None
+    nd, nb = nerf.packed(L.MF_PREC_F32)
+    ex = nerf_embeddings[0].descriptor()
+    fd = fb = fx = fi = None
+    if bw_nof is not None:
+        if nof_embeddings is None or len(nof_embeddings) < 2:
+            raise RuntimeError("query_radiance: a NoF needs nof_embeddings = [xyz, ind]")
+        fd, fb = bw_nof.packed(L.MF_PREC_F32)
+        fx, fi = nof_embeddings[0].descriptor(), nof_embeddings[1].descriptor()
+    ref = lambda d: C.byref(d) if d is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().mf_points_radiance(nd, nb.data_ptr(), C.byref(ex), ref(eext), fd, L.ptr(fb), ref(fx), ref(fi), L.ptr(x),
+                                           L.ptr(dirs), L.ptr(ind_t), ind_s, B, L.ptr(out), L.ptr(canon),
+                                           L.current_stream(dev)), "mf_points_radiance")
+    return (out, canon) if return_canonical else out
