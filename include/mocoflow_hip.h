@@ -43,7 +43,8 @@ extern "C" {
  *     instruction, biases at 2^10 x); MF_PREC_BF16X3 training forward under NoF (mf_render_args.dump_nof_acts / dump_nof_out without
  *     dump_nof_emb) + mf_nof_embed_rows
  * additive entries since, version unchanged: mf_mc_scratch_bytes / mf_mc_count / mf_mc_emit; mf_ssim, mf_sqerr (+ their
- *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals */
+ *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals;
+ *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -661,6 +662,59 @@ typedef struct mf_sheet_panel {
 } mf_sheet_panel;
 int32_t mf_frame_sheet(const mf_sheet_panel* panels /* host */, int32_t n_panels, int64_t H, int64_t W, const float* range2s,
                        const uint8_t* lut, uint8_t* out_u8, float* out_planar, void* stream);
+
+/* ---- the ray batch of a training step (trainer/trainer_moco_flow.py:407-417, the same lines of trainer/trainer_nerf.py; fed by
+ * datasets/moco_flow_dataset.py:166-176, 190-196; the chain_global column of _shared_step, trainer_moco_flow.py:308-312).
+ * The reference keeps per frame the (H W, 9) ray table, the composited (H W, 3) image and the (H W, 3) background, and draws
+ * a batch with torch.nonzero, torch.randperm and three gathers.  The batch is a pure function of the camera, the hull mask,
+ * the image and a permutation: these two entries build it from those, and none of the tables exists.
+ *
+ * mf_mask_compact (trainer_moco_flow.py:414: val_inds = torch.nonzero(rays_msk).squeeze(1)): inds_out[0 .. count) = the
+ * positions of the non-zero bytes of mask (n bytes), ascending; count (device int64[1]) = how many.  inds_out has room for n
+ * entries; entries from count on are not written.  mask == NULL: the identity, count = n (scratch may be NULL).  Per-workgroup
+ * counts into scratch (mf_mask_compact_scratch_bytes(n) bytes), then every workgroup sums the counts in front of it and
+ * scatters its share with wavefront ballots: no atomics, pixel order, bit-identical from run to run.  Two launches (one for the
+ * identity), no host read; n = 0 only zeroes count. */
+int64_t mf_mask_compact_scratch_bytes(int64_t n);
+int32_t mf_mask_compact(const uint8_t* mask, int64_t n, int64_t* inds_out, int64_t* count, void* scratch, void* stream);
+
+/* mf_ray_batch (trainer_moco_flow.py:415-416 with datasets/moco_flow_dataset.py:169-176, 196 and _shared_step :308-312): one
+ * launch, one thread per row k < n_rows.  pixel = val_inds[perm[k]] (both device int64; the reference's
+ * val_inds[torch.randperm(n_valid)[:N_rand]]), written to sel_out[k] when sel_out is given.
+ *   rays_out (n_rows, 9), or (n_rows, 10) with has_chain: columns 0-8 are row `pixel` of mf_make_rays for the same H, W, focal,
+ *       cx, cy, c2w, nearv, farv, idx, bit for bit (the same per-pixel device function); column 9 = chain_idx.  c2w travels BY
+ *       VALUE (3x4 row-major, read when has_c2w).  Rows are stored in float4 pieces where rays_out is 16-byte aligned.
+ *   rgbs_out (n_rows, 3), by image_kind:
+ *       MF_IMAGE_NONE    nothing is written (rgbs_out may be NULL)
+ *       MF_IMAGE_ROWS    image = fp32 (H W, 3): the row is gathered
+ *       MF_IMAGE_U8_RGB  image = bytes (H, W, 3): v = u8 * (1.0f / 255.0f), which is what u8.float().div(255) (torchvision's
+ *                        ToTensor) gives ON THE DEVICE, where torch multiplies by the fp32 reciprocal of a host scalar.  For
+ *                        126 of the 256 byte values that is one ulp from the fp32 quotient the host computes.
+ *       MF_IMAGE_U8_RGBA image = bytes (H, W, 4), 4-byte aligned: v_c a + bg_c (1 - a) with a = alpha * (1.0f / 255.0f) and bg the
+ *                        pixel's background (moco_flow_dataset.py:174); the reciprocal, every product, difference and sum
+ *                        rounded once, no fused multiply-add: bit-identical to the torch expression evaluated on the device.
+ *                        Needs a background.
+ *   background_out (n_rows, 3), optional, by background_kind:
+ *       MF_BACKGROUND_NONE    none      MF_BACKGROUND_ROWS  background = fp32 (H W, 3): the row is gathered
+ *       MF_BACKGROUND_COLOUR  background = 3 device floats, one colour for every pixel (bkgd_img, moco_flow_dataset.py:176)
+ * perm[k] outside [0, n_valid), or a val_inds entry outside [0, H W), is NOT dereferenced: the row's outputs are NaN and
+ * sel_out[k] = -1 (the caller cannot check a device permutation without a synchronisation).
+ * 32-bit pixel indexing: H W and n_rows below 2^31, else MF_E_INVALID.  n_rows = 0 launches nothing. */
+enum { MF_IMAGE_NONE = 0, MF_IMAGE_ROWS = 1, MF_IMAGE_U8_RGB = 2, MF_IMAGE_U8_RGBA = 3 };
+enum { MF_BACKGROUND_NONE = 0, MF_BACKGROUND_ROWS = 1, MF_BACKGROUND_COLOUR = 2 };
+typedef struct mf_ray_batch_args {
+  int32_t H, W;
+  float focal, cx, cy;             /* as mf_make_rays */
+  int32_t has_c2w; float c2w[12];
+  float nearv, farv, idx;
+  int32_t has_chain; float chain_idx;
+  const int64_t* val_inds; int64_t n_valid;     /* mf_mask_compact's output */
+  const int64_t* perm; int64_t n_rows;          /* n_rows entries are read */
+  const void* image; int32_t image_kind;
+  const float* background; int32_t background_kind;
+  float* rays_out; float* rgbs_out; float* background_out; int64_t* sel_out;
+} mf_ray_batch_args;
+int32_t mf_ray_batch(const mf_ray_batch_args* a /* host */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,19 @@ MF_SHEET_MAX_PANELS = 8
 MF_PANEL_RGB, MF_PANEL_DEPTH = 0, 1
 
 
+MF_IMAGE_NONE, MF_IMAGE_ROWS, MF_IMAGE_U8_RGB, MF_IMAGE_U8_RGBA = 0, 1, 2, 3
+MF_BACKGROUND_NONE, MF_BACKGROUND_ROWS, MF_BACKGROUND_COLOUR = 0, 1, 2
+
+
+class mf_ray_batch_args(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("focal", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("has_c2w", C.c_int32), ("c2w", C.c_float * 12), ("nearv", C.c_float), ("farv", C.c_float), ("idx", C.c_float),
+                ("has_chain", C.c_int32), ("chain_idx", C.c_float),
+                ("val_inds", _fp), ("n_valid", C.c_int64), ("perm", _fp), ("n_rows", C.c_int64),
+                ("image", _fp), ("image_kind", C.c_int32), ("background", _fp), ("background_kind", C.c_int32),
+                ("rays_out", _fp), ("rgbs_out", _fp), ("background_out", _fp), ("sel_out", _fp)]
+
+
 class mf_loss_pass(C.Structure):
     _fields_ = [("rgb", _fp), ("alphas", _fp), ("disp_local", _fp), ("disp_global", _fp), ("n_samples", C.c_int32)]
 
@@ -185,6 +198,9 @@ SYMBOLS = {
     "mf_depth_range": (C.c_int32, [_fp, C.c_int64, C.c_float, _fp, _fp, _fp]),
     "mf_depth_colormap": (C.c_int32, [_fp, C.c_int64, _fp, C.c_float, _fp, _fp, _fp]),
     "mf_frame_sheet": (C.c_int32, [C.POINTER(mf_sheet_panel), C.c_int32, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
+    "mf_mask_compact_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "mf_mask_compact": (C.c_int32, [_fp, C.c_int64, _fp, _fp, _fp, _fp]),
+    "mf_ray_batch": (C.c_int32, [C.POINTER(mf_ray_batch_args), _fp]),
 }
 
 _lock = threading.Lock()

@@ -5,42 +5,25 @@
 //   mf_valid_rays_mask : Camera.get_valid_rays_mask  utils/camera.py:119-132 (hull + fill of the projected AABB)
 //   mf_knn1      : knn_cuda.KNN(k=1)  (vendored wheel docker/KNN_CUDA-0.2: knn_cuda/csrc/cuda/knn.cu:29-183)
 #include "mf_host.hpp"
+#include "mf_rays.hpp"
 
 namespace mf {
 
 struct RaysParams {
-  int H, W;
-  float fx, cx, cy;
-  float R[9], t[3];
-  int has_c2w;
-  float nearv, farv, idx;
+  RayCam cam;
   float* out;
 };
 
-// one thread per pixel; row-major pixel order (row j, column i), 9 floats per ray
+// one thread per pixel; row-major pixel order (row j, column i), 9 floats per ray (mf_rays.hpp: pixel_ray)
 __global__ void make_rays_kernel(RaysParams p) {
   const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= (long long)p.H * p.W) return;
-  const int j = (int)(n / p.W), i = (int)(n - (long long)j * p.W);
-  // camera.py:47-48: ((i - cx)/f0, -(j - cy)/f0, -1); both axes use focal[0]
-  const float dx = ((float)i - p.cx) / p.fx;
-  const float dy = -(((float)j - p.cy) / p.fx);
-  const float dz = -1.f;
-  float wx, wy, wz, ox = 0.f, oy = 0.f, oz = 0.f;
-  if (p.has_c2w) {
-    // camera.py:73: directions @ c2w[:, :3].T  (dot over the camera axes, in order)
-    wx = dx * p.R[0] + dy * p.R[1] + dz * p.R[2];
-    wy = dx * p.R[3] + dy * p.R[4] + dz * p.R[5];
-    wz = dx * p.R[6] + dy * p.R[7] + dz * p.R[8];
-    ox = p.t[0]; oy = p.t[1]; oz = p.t[2];
-  } else {
-    wx = dx; wy = dy; wz = dz;
-  }
-  const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);      // camera.py:68/74
+  if (n >= (long long)p.cam.H * p.cam.W) return;
+  const int j = (int)(n / p.cam.W), i = (int)(n - (long long)j * p.cam.W);
+  float r[9];
+  pixel_ray(p.cam, j, i, r);
   float* o = p.out + n * 9;
-  o[0] = ox; o[1] = oy; o[2] = oz;
-  o[3] = wx / nrm; o[4] = wy / nrm; o[5] = wz / nrm;
-  o[6] = p.nearv; o[7] = p.farv; o[8] = p.idx;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) o[c] = r[c];
 }
 
 struct ComposeParams {
@@ -275,15 +258,9 @@ extern "C" int32_t mf_make_rays(int32_t H, int32_t W, float focal, float cx, flo
   if ((long long)H * W == 0) return MF_OK;
   if (!rays_out) return fail(MF_E_INVALID, "mf_make_rays: null output");
   RaysParams p{};
-  p.H = H; p.W = W; p.fx = focal; p.cx = cx; p.cy = cy;
-  p.has_c2w = c2w_host != nullptr;
-  if (c2w_host) {
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) p.R[a * 3 + b] = c2w_host[a * 4 + b];
-      p.t[a] = c2w_host[a * 4 + 3];
-    }
-  }
-  p.nearv = nearv; p.farv = farv; p.idx = idx; p.out = rays_out;
+  p.cam.H = H; p.cam.W = W; p.cam.fx = focal; p.cam.cx = cx; p.cam.cy = cy;
+  ray_cam_set_c2w(p.cam, c2w_host);
+  p.cam.nearv = nearv; p.cam.farv = farv; p.cam.idx = idx; p.out = rays_out;
   const long long n = (long long)H * W;
   hipLaunchKernelGGL(make_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_make_rays");
