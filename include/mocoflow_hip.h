@@ -44,7 +44,8 @@ extern "C" {
  *     dump_nof_emb) + mf_nof_embed_rows
  * additive entries since, version unchanged: mf_mc_scratch_bytes / mf_mc_count / mf_mc_emit; mf_ssim, mf_sqerr (+ their
  *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals;
- *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch */
+ *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch; mf_point_correspond, mf_point_loss_partials
+ *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -715,6 +716,67 @@ typedef struct mf_ray_batch_args {
   float* rays_out; float* rgbs_out; float* background_out; int64_t* sel_out;
 } mf_ray_batch_args;
 int32_t mf_ray_batch(const mf_ray_batch_args* a /* host */, void* stream);
+
+/* ---- SMPL point supervision of a training step (datasets/moco_flow_dataset.py:101-132; trainer/trainer_moco_flow.py:146-157,
+ * 330-363; trainer/trainer_nof.py:115-125; csrc/mf_supervise.hip).  The reference compacts the query points into an inside and
+ * an outside set (two host reads of data-dependent lengths) and takes three losses of them.  Here every tensor keeps all Q rows
+ * in the queries' order, the split is the byte mask `inside`, and the losses are (sum, count) pairs: no compaction, no host read.
+ *
+ * mf_point_correspond: one launch.  Q = q_given + q_near queries: rows [0, q_given) are `query` (q_given, 3) as given; row
+ * q_given + j is verts[pick[j]] + noise[j] * thickness (pick: q_near int64 in [0, V), clamped; noise (q_near, 3), a randn
+ * draw), the product and the sum rounded once each -- near_surface_pts of moco_flow_dataset.py:110-111 without its gather.
+ * verts (V, 3): the source-pose vertices; trans (V, 4, 4): mf_smpl_frame_transforms' output.
+ *   pairs (Q, 6)  = [query | trans[ind] @ (query, 1)], mf_apply_vertex_transforms' expression
+ *   inside (Q)    = dist < thickness ? 1 : 0 (strict, :123)
+ *   dist (Q), ind (Q): the nearest vertex's distance and index; each may be NULL
+ * The search is mf_knn1's arithmetic per candidate (fma(az, az, fma(ay, ay, ax ax)) on ref - query, sqrtf of the minimum) and
+ * its tie rule (the lowest index among equal minima): dist, ind and pairs are bit-identical to mf_knn1 followed by
+ * mf_apply_vertex_transforms.  lanes_per_query lanes of a wave share a query -- each takes the vertices v = lane (mod
+ * lanes_per_query) of every tile, then the lanes take the lexicographic minimum of (d, index) -- so that a few thousand queries
+ * still fill the chip; the result does not depend on it.  0 = chosen from Q (the fewest lanes that give every SIMD two waves);
+ * anything but 0, 1, 4, 16, 64 is MF_E_INVALID, as are V < 1, V or Q >= 2^31 - 1, a negative count and a NULL that is needed.
+ * Q = 0 launches nothing. */
+int32_t mf_point_correspond(const float* verts, const float* trans, int64_t V, const float* query, int64_t q_given,
+                            const int64_t* pick, const float* noise, int64_t q_near, float thickness, int32_t lanes_per_query,
+                            float* pairs, uint8_t* inside, float* dist, int64_t* ind, void* stream);
+
+/* mf_point_loss_partials: out6 (device, 6 doubles) = [sum, count] of
+ *   nof_bw       sum |pred_bw - pairs[:, 3:6]| over the rows with inside = 1; count = 3 x those rows   (nn.L1Loss, :337-338)
+ *   nof_fw       sum |pred_fw - pairs[:, 0:3]| over the same rows                                        (:340-341)
+ *   alphas_mask  sum over the rows with inside = 0 and the n_nerfs (<= 2) NeRFs of -max(logf(1 - alpha), -100), alpha = 1 -
+ *                expf(-delta softplus(sigma)), softplus(s) = s > 20 ? s : log1pf(expf(s)): nn.BCELoss against zeros of
+ *                forwarf_nerf's alphas (:146-157, :348-363), every operation rounded where torch rounds it; count = outside
+ *                rows x n_nerfs, the length of the reference's torch.cat (:359)
+ * each |.| taken in fp32 and summed in float64.  inside == NULL or use_all != 0: the L1 terms take every row (stage 2,
+ * trainer_nof.py:115-125); inside == NULL leaves no outside row.  pred_bw / pred_fw NULL: that term is (0, 0).
+ * means3 (device, 3 floats, optional): sum / count in fp32, 0 where the count is 0 (the reference would give NaN).
+ * Deterministic: per-workgroup partials in scratch (mf_point_loss_partials_scratch_bytes(Q) bytes), summed in a fixed order by
+ * a second launch; no atomics.  Q = 0 writes zeros. */
+typedef struct mf_point_loss_args {
+  int64_t Q;
+  const float* pairs;             /* (Q, 6) */
+  const uint8_t* inside;          /* (Q) or NULL */
+  int32_t use_all;
+  const float* pred_bw;           /* (Q, 3) or NULL */
+  const float* pred_fw;           /* (Q, 3) or NULL */
+  int32_t n_nerfs;                /* 0 .. 2 */
+  const float* sigma[2];          /* (Q) raw densities of each NeRF */
+  float delta[2];
+} mf_point_loss_args;
+int64_t mf_point_loss_partials_scratch_bytes(int64_t Q);
+int32_t mf_point_loss_partials(const mf_point_loss_args* a /* host */, double* out6, float* means3, void* scratch, void* stream);
+
+/* Backward of the three means: seeds3 (device, 3 floats) = dL / d (sum / count) of each term, out6 the forward's partials (the
+ * counts are read on the device).  Written whole, exact zeros on rows the mask drops and everywhere in a term whose count is 0:
+ *   g_pred_bw, g_pred_fw (Q, 3) = seed / count * sign(pred - target), sign(0) = 0                      (nn.L1Loss)
+ *   g_sigma0, g_sigma1 (Q)      = seed * alpha / max((1 - alpha) alpha, 1e-12) / count                  (nn.BCELoss)
+ *                                 * expf(-delta softplus(sigma)) * delta, then (sigma > 20 ? a : a z / (z + 1)), z = expf(sigma)
+ * Every product and quotient is rounded in the order of torch's device kernels for the same chain (binary_cross_entropy_backward,
+ * exp, mul, softplus_backward, mean), `/ count` being their multiplication by the rounded reciprocal 1.f / count: the seeds are
+ * bit-identical to the ones autograd hands the compacted rows.
+ * Each output may be NULL.  One launch. */
+int32_t mf_point_loss_partials_backward(const mf_point_loss_args* a /* host */, const double* out6, const float* seeds3,
+                                        float* g_pred_bw, float* g_pred_fw, float* g_sigma0, float* g_sigma1, void* stream);
 
 #ifdef __cplusplus
 }

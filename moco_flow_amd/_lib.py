@@ -79,6 +79,11 @@ class mf_ray_batch_args(C.Structure):
                 ("rays_out", _fp), ("rgbs_out", _fp), ("background_out", _fp), ("sel_out", _fp)]
 
 
+class mf_point_loss_args(C.Structure):
+    _fields_ = [("Q", C.c_int64), ("pairs", _fp), ("inside", _fp), ("use_all", C.c_int32), ("pred_bw", _fp), ("pred_fw", _fp),
+                ("n_nerfs", C.c_int32), ("sigma", _fp * 2), ("delta", C.c_float * 2)]
+
+
 class mf_loss_pass(C.Structure):
     _fields_ = [("rgb", _fp), ("alphas", _fp), ("disp_local", _fp), ("disp_global", _fp), ("n_samples", C.c_int32)]
 
@@ -201,6 +206,11 @@ SYMBOLS = {
     "mf_mask_compact_scratch_bytes": (C.c_int64, [C.c_int64]),
     "mf_mask_compact": (C.c_int32, [_fp, C.c_int64, _fp, _fp, _fp, _fp]),
     "mf_ray_batch": (C.c_int32, [C.POINTER(mf_ray_batch_args), _fp]),
+    "mf_point_correspond": (C.c_int32, [_fp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int64, C.c_float, C.c_int32,
+                                        _fp, _fp, _fp, _fp, _fp]),
+    "mf_point_loss_partials_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "mf_point_loss_partials": (C.c_int32, [C.POINTER(mf_point_loss_args), _fp, _fp, _fp, _fp]),
+    "mf_point_loss_partials_backward": (C.c_int32, [C.POINTER(mf_point_loss_args), _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()
