@@ -17,8 +17,8 @@
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_plan.hpp"
 #include "mf_bwd.hpp"
-#include <cstdlib>
 
 namespace mf {
 
@@ -75,10 +75,7 @@ __global__ __launch_bounds__(kThreads, 2) void nerf_backward_kernel(BwdParams p)
   load_resident(net, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = MF_TIMING_FLAGS ? p.dbg : 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes, MF_TIMING_FLAGS ? p.dbg : 0);
   const uint32_t zero_bias = net.res_lds + net.L.off_bias_trunk * 4;
   const char* first = net.packed + net.L.res_bytes;
   st.start(first, bwd_groups(net.L, 0), id);
@@ -285,14 +282,11 @@ extern "C" int32_t mf_nerf_backward_x(const mf_nerf_desc* d, const void* packed_
   if (stride < (int64_t)(d->D + 1) * d->W + d->W / 2 || (stride & 3))
     return fail(MF_E_INVALID, "mf_nerf_backward: stride %lld too small or not a multiple of 4", (long long)stride);
   if (P == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed_bwd);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed_bwd);
   p.D = d->D; p.P = P; p.stride = stride;
   p.g_out = g_out; p.acts = acts; p.rgbsigma = rgbsigma; p.gpre = gpre; p.ghead = ghead;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  p.dbg = 0;
-  if (const char* e = getenv("MF_DEBUG_FLAGS")) p.dbg = atoi(e);   // timing ablations only
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  return launch_lds(nerf_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nerf_backward", "mf_nerf_backward");
+  plan.ring(p.ring_off, p.buf_bytes);
+  p.dbg = debug_flags();
+  return launch_lds(nerf_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_nerf_backward", "mf_nerf_backward");
 }

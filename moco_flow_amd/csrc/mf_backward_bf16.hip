@@ -15,6 +15,7 @@
 #include "mf_bwd3.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
+#include "mf_plan.hpp"
 
 namespace mf {
 
@@ -234,7 +235,7 @@ extern "C" int32_t mf_nerf_backward3(const mf_nerf_desc* d, const void* packed_b
   p.net.res_lds = 0; p.net.res_bytes = bf::kB3ResBytes; p.net.D = d->D; p.net.emb_mask = 0; p.net.aux = 0;
   p.P = P; p.stride = stride; p.g_out = g_out; p.acts = acts; p.rgbsigma = rgbsigma; p.gpre = gpre; p.ghead = ghead;
   uint32_t lds = bf::kB3ResBytes;
-  p.ring_off = lds; p.buf_bytes = 32 * kGroupBytes; lds += 3 * p.buf_bytes;
+  place_ring(lds, 32, p.ring_off, p.buf_bytes);
   const int grid = persistent_grid((P + 127) / 128);
   void (*kern)(const bf::Bwd3Params) = mask ? bf::nerf_backward_kernel_x3<true> : bf::nerf_backward_kernel_x3<false>;
   return launch_lds(kern, grid, 256, lds, static_cast<hipStream_t>(stream), p, "mf_nerf_backward3", "mf_nerf_backward3");

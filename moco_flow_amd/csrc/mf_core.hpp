@@ -387,6 +387,10 @@ struct Stream {
   int dbg;                // timing-ablation switches (MF_DEBUG_FLAGS; 0 in production)
   int keep2;              // KEEP2 instantiations only: VM stores this wave issued at the end of the panel (0, 2: the dump rows, 3: + the mask word)
 
+  // over the ring the launch planned (LdsPlan::ring, mf_plan.hpp); dbg: the launch's MF_DEBUG_FLAGS where the kernel honours them
+  MF_D void open(uint32_t ring_off, uint32_t slot_bytes, int dbg_flags = 0) {
+    ring = ring_off; buf_bytes = slot_bytes; dbg = dbg_flags; keep2 = 0;
+  }
   MF_D uint32_t slot_off(uint32_t k) const {
     uint32_t s = cur + k;
     s = s >= 3u ? s - 3u : s;

@@ -9,6 +9,7 @@
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_plan.hpp"
 #include "mf_raypass.hpp"
 
 namespace mf {
@@ -66,10 +67,7 @@ __global__ __launch_bounds__(kThreads, 2) void nerf_forward_kernel(NerfFwdParams
   load_resident(net, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes);
   start_program(net, st, carry, id);                    // also drains the resident-block DMA
   const long long ntiles = (p.B + kTile - 1) / kTile;
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -131,10 +129,7 @@ __global__ __launch_bounds__(kThreads, 2) void nof_forward_kernel(NofFwdParams p
   load_resident(net, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes);
   start_program(net, st, carry, id);
   const long long ntiles = (p.B + kTile - 1) / kTile;
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -185,10 +180,7 @@ __global__ __launch_bounds__(kThreads, 2) void points_kernel(PointsParams p) {
   if (NOF) load_resident(p.nof, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes);
   const NextLayer prog_first = NOF ? follow_of(p.nof) : follow_of(p.nerf);
   if (NOF) start_program(p.nof, st, carry, id);
   else start_program(p.nerf, st, carry, id);
@@ -252,10 +244,7 @@ __global__ __launch_bounds__(kThreads, 2) void radiance_kernel(RadianceParams p)
                  par_nof_ind = p.par_off + 384;
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes);
   const NextLayer prog_first = NOF ? follow_of(p.nof) : follow_of(p.nerf);
   if (NOF) start_program(p.nof, st, carry, id);
   else start_program(p.nerf, st, carry, id);
@@ -356,18 +345,16 @@ static int32_t nerf_forward_launch(const char* who, const mf_nerf_desc* d, const
   if (dump && dump_stride < (int64_t)p.net.L.n_trunk * p.net.L.W + p.net.L.W / 2)
     return fail(MF_E_INVALID, "%s: dump_stride %lld too small", who, (long long)dump_stride);
   if (B == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed);
   p.in = inputs; p.in_stride = in_stride; p.B = B; p.sigma_only = sigma_only; p.out = out;
   p.dump = dump; p.dump_stride = dump_stride;
   p.extra_kind = d->extra_feat_type == MF_EXTRA_DIR ? kEmbDir : (d->extra_feat_type == MF_EXTRA_IND ? kEmbInd : kEmbNone);
   p.extra_cols = d->extra_feat_type == MF_EXTRA_NONE ? 0 : d->extra_feat_dim;
   p.xyz_cols = d->in_channels_xyz;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
+  plan.ring(p.ring_off, p.buf_bytes);
   void (*kern)(NerfFwdParams) = dump ? nerf_forward_kernel<true> : nerf_forward_kernel<false>;
-  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, who, who);
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, who, who);
 }
 
 extern "C" int32_t mf_nerf_forward(const mf_nerf_desc* d, const void* packed, const float* inputs, int64_t in_stride,
@@ -387,15 +374,13 @@ extern "C" int32_t mf_nof_forward(const mf_nof_desc* d, const void* packed, cons
   NofFwdParams p{};
   if (!nof_layout(*d, p.net.L, 0, true)) return fail(MF_E_UNSUPPORTED, "mf_nof_forward: unsupported NoF configuration");
   if (B == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed);
   p.in = inputs; p.in_stride = in_stride; p.B = B; p.xyz = xyz; p.out = out;
   p.xyz_cols = d->in_channels_xyz; p.in_cols = d->in_channels_xyz + d->extra_feat_dim;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
+  plan.ring(p.ring_off, p.buf_bytes);
   void (*kern)(NofFwdParams) = p.net.L.NK == 16 ? nof_forward_kernel<16> : nof_forward_kernel<8>;     // W = 256: the bare NoF() default
-  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward", "mf_nof_forward");
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward", "mf_nof_forward");
 }
 
 namespace mf {
@@ -426,14 +411,12 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   if (!nerf || !nerf_packed || !emb_xyz || (B > 0 && (!xyz || !sigma)))
     return fail(MF_E_INVALID, "mf_points_sigma: null argument");
   if (precision < MF_PREC_F32 || precision > MF_PREC_BF16X3) return fail(MF_E_INVALID, "mf_points_sigma: precision %d", precision);
+  if (int e = check_xyz_embedding("mf_points_sigma", *emb_xyz, 10)) return e;
+  if (nof) {
+    if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_sigma: NoF arguments missing");
+    if (int e = check_nof_embeddings("mf_points_sigma", *nof_emb_xyz, *nof_emb_ind)) return e;
+  }
   if (precision != MF_PREC_F32) {
-    if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 10)
-      return fail(MF_E_UNSUPPORTED, "mf_points_sigma: xyz embedding must have 3 channels and <= 10 frequencies");
-    if (nof) {
-      if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_sigma: NoF arguments missing");
-      if (nof_emb_xyz->in_channels != 3 || nof_emb_xyz->n_freqs > 5 || nof_emb_ind->in_channels != 1 || nof_emb_ind->n_freqs > 16)
-        return fail(MF_E_UNSUPPORTED, "mf_points_sigma: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
-    }
     if (B == 0) return MF_OK;
     return points_sigma_bf16(precision, nerf, nerf_packed, emb_xyz, nof, nof_packed, nof_emb_xyz, nof_emb_ind, xyz, ind, ind_scalar, B, sigma, canon,
                              workspace, workspace_bytes, static_cast<hipStream_t>(stream));
@@ -441,31 +424,20 @@ extern "C" int32_t mf_points_sigma_p(int32_t precision, const mf_nerf_desc* nerf
   PointsParams p{};
   if (!nerf_layout(*nerf, p.nerf.L) || p.nerf.L.NK != 16)
     return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NeRF configuration");
-  if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 10)
-    return fail(MF_E_UNSUPPORTED, "mf_points_sigma: xyz embedding must have 3 channels and <= 10 frequencies");
   if (B == 0) return MF_OK;
-  uint32_t lds = 0;
-  p.nerf.packed = static_cast<const char*>(nerf_packed);
-  p.nerf.res_lds = lds; lds += (uint32_t)p.nerf.L.res_bytes;
-  int max_groups = p.nerf.L.max_groups;
+  LdsPlan plan;
+  plan.place(p.nerf, nerf_packed);
   emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
   if (nof) {
-    if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_sigma: NoF arguments missing");
     if (!nof_layout(*nof, p.nof.L)) return fail(MF_E_UNSUPPORTED, "mf_points_sigma: unsupported NoF configuration");
-    if (nof_emb_xyz->in_channels != 3 || nof_emb_xyz->n_freqs > 5 || nof_emb_ind->in_channels != 1 || nof_emb_ind->n_freqs > 16)
-      return fail(MF_E_UNSUPPORTED, "mf_points_sigma: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
-    p.nof.packed = static_cast<const char*>(nof_packed);
-    p.nof.res_lds = lds; lds += (uint32_t)p.nof.L.res_bytes;
-    if (p.nof.L.max_groups > max_groups) max_groups = p.nof.L.max_groups;
+    plan.place(p.nof, nof_packed);
     emb_table(*nof_emb_xyz, p.nxyz.freq, p.nxyz.weight);
     emb_table(*nof_emb_ind, p.nind.freq, p.nind.weight);
   }
   p.xyz = xyz; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.sigma = sigma; p.canon = canon;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
+  plan.ring(p.ring_off, p.buf_bytes);
   void (*kern)(PointsParams) = nof ? points_kernel<true> : points_kernel<false>;
-  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_points_sigma", "mf_points_sigma");
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_points_sigma", "mf_points_sigma");
 }
 
 extern "C" int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf_packed, const mf_embedding* emb_xyz,
@@ -480,9 +452,9 @@ extern "C" int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf
   RadianceParams p{};
   if (!nerf_layout(*nerf, p.nerf.L) || p.nerf.L.NK != 16)
     return fail(MF_E_UNSUPPORTED, "mf_points_radiance: unsupported NeRF configuration");
-  if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 10)
-    return fail(MF_E_UNSUPPORTED, "mf_points_radiance: xyz embedding must have 3 channels and <= 10 frequencies");
+  if (int e = check_xyz_embedding("mf_points_radiance", *emb_xyz, 10)) return e;
   p.extra_type = nerf->extra_feat_type;
+  // (the extra block's check stays here: MF_E_INVALID and n_freqs < 0 a fault, unlike the render pass's -- mf_plan.hpp)
   if (p.extra_type == MF_EXTRA_DIR) {
     if (!emb_extra || (B > 0 && !view_dirs)) return fail(MF_E_INVALID, "mf_points_radiance: a \"dir\" NeRF needs emb_extra and view_dirs");
     if (emb_extra->in_channels != 3 || emb_extra->n_freqs < 0 || emb_extra->n_freqs > 4 ||
@@ -494,30 +466,23 @@ extern "C" int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf
         (2 * emb_extra->n_freqs + 1) > nerf->extra_feat_dim)
       return fail(MF_E_INVALID, "mf_points_radiance: ind embedding must have 1 channel, <= 2 frequencies and fit extra_feat_dim");
   }
-  uint32_t lds = 0;
-  p.nerf.packed = static_cast<const char*>(nerf_packed);
-  p.nerf.res_lds = lds; lds += (uint32_t)p.nerf.L.res_bytes;
-  int max_groups = p.nerf.L.max_groups;
+  LdsPlan plan;
+  plan.place(p.nerf, nerf_packed);
   emb_table(*emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
   if (p.extra_type != MF_EXTRA_NONE) emb_table(*emb_extra, p.emb_par[1], p.emb_par[1] + 16);
   if (nof) {
     if (!nof_packed || !nof_emb_xyz || !nof_emb_ind) return fail(MF_E_INVALID, "mf_points_radiance: NoF arguments missing");
     if (!nof_layout(*nof, p.nof.L)) return fail(MF_E_UNSUPPORTED, "mf_points_radiance: unsupported NoF configuration");
-    if (nof_emb_xyz->in_channels != 3 || nof_emb_xyz->n_freqs > 5 || nof_emb_ind->in_channels != 1 || nof_emb_ind->n_freqs > 16)
-      return fail(MF_E_UNSUPPORTED, "mf_points_radiance: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
-    p.nof.packed = static_cast<const char*>(nof_packed);
-    p.nof.res_lds = lds; lds += (uint32_t)p.nof.L.res_bytes;
-    if (p.nof.L.max_groups > max_groups) max_groups = p.nof.L.max_groups;
+    if (int e = check_nof_embeddings("mf_points_radiance", *nof_emb_xyz, *nof_emb_ind)) return e;
+    plan.place(p.nof, nof_packed);
     emb_table(*nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16);
     emb_table(*nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16);
   }
   if (B == 0) return MF_OK;
-  p.par_off = lds; lds += 512;
+  p.par_off = plan.place_tables();
   p.xyz = xyz; p.dirs = view_dirs; p.ind = ind; p.ind_scalar = ind_scalar; p.B = B; p.out = out; p.canon = nof ? canon : nullptr;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
+  plan.ring(p.ring_off, p.buf_bytes);
   void (*kern)(RadianceParams) = nof ? radiance_kernel<true> : radiance_kernel<false>;
-  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_points_radiance",
+  return launch_lds(kern, persistent_grid((B + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_points_radiance",
                     "mf_points_radiance");
 }

@@ -4,8 +4,8 @@
 //   consensus means over the alpha >= 0.01 mask    models/rendering.py:306-314 + trainer/trainer_moco_flow.py:317-328
 // Output = 12 doubles, one (sum, count) pair per term the reference averages separately (the layout of
 // moco_flow_amd/dist.py::loss_partials): [mse_c | mse_f | local_c | local_f | global_c | global_f].
-// The mean-only caller divides; the multi-GPU caller all-reduces the 96 bytes first.  Deterministic: fixed-order
-// partial sums through `scratch`, no atomics.
+// The mean-only caller divides; the multi-GPU caller all-reduces the 96 bytes first.  Deterministic: the fixed-order
+// reduction of mf_reduce.hpp through `scratch`, no atomics.
 #include "mf_host.hpp"
 #include "mf_reduce.hpp"
 
@@ -29,7 +29,6 @@ struct LossParams {
 };
 
 __global__ __launch_bounds__(kLossThreads) void loss_partials_kernel(LossParams p) {
-  __shared__ double red[kLossThreads / 64][kLossSlots];
   double acc[kLossSlots];
 #pragma unroll
   for (int k = 0; k < kLossSlots; ++k) acc[k] = 0.0;
@@ -52,41 +51,14 @@ __global__ __launch_bounds__(kLossThreads) void loss_partials_kernel(LossParams 
       acc[6 * q + 5] += g;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kLossSlots; ++k) {
-    const double s = wave_sum_d(acc[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossSlots) {
-    double s = 0.0;
-    for (int w = 0; w < kLossThreads / 64; ++w) s += red[w][threadIdx.x];
-    p.scratch[(long long)blockIdx.x * kLossSlots + threadIdx.x] = s;
-  }
+  block_sum_d<kLossThreads, kLossSlots>(acc, p.scratch + (long long)blockIdx.x * kLossSlots);
 }
 
-// One workgroup of kLossBlocks threads: thread b holds block b's 12 partials (independent loads), then a fixed tree --
-// wave_sum_d (DPP row shifts / broadcasts) inside a wave, the waves' sums in wave order -- so the result is the same in every run.  (Twelve
-// threads walking the blocks one dependent load at a time took 24 us, longer than the partials kernel itself.)
+// One workgroup of kLossBlocks threads gathers the blocks' partials (thread b: block b's 12), then the per-pass fallback and
+// the means.
 __global__ __launch_bounds__(kLossBlocks) void loss_finish_kernel(LossParams p, int n_blocks) {
   __shared__ double tot[kLossSlots];
-  __shared__ double red[kLossBlocks / 64][kLossSlots];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[kLossSlots];
-#pragma unroll
-  for (int k = 0; k < kLossSlots; ++k) v[k] = (int)threadIdx.x < n_blocks ? p.scratch[(long long)threadIdx.x * kLossSlots + k] : 0.0;
-#pragma unroll
-  for (int k = 0; k < kLossSlots; ++k) {
-    const double s = wave_sum_d(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossSlots) {
-    double s = 0.0;
-    for (int w = 0; w < kLossBlocks / 64; ++w) s += red[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
+  gather_sum_d<kLossBlocks, kLossSlots>(p.scratch, n_blocks, tot);
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int q = 0; q < 2; ++q) {

@@ -4,7 +4,7 @@
 //             for the quaternion functions) and is unpinned against kornia itself -- plus the squared error of the same
 //             frame pair, in ONE launch over strided images: no permute copy, no padded copy, no intermediate planes.
 //   mf_sqerr  sum and count behind mse / psnr, with the optional per-element or per-row mask.
-// Both reduce in a fixed order (per-workgroup float64 partials in `scratch`, one finishing workgroup in index order): two
+// Both reduce in the fixed order of mf_reduce.hpp (per-workgroup float64 partials in `scratch`, one finishing workgroup): two
 // runs are bit-identical, no atomics.
 #include <cmath>
 
@@ -17,38 +17,7 @@ namespace mf {
 constexpr int kFinishThreads = 256;
 
 __global__ __launch_bounds__(kFinishThreads) void metrics_finish_kernel(const double* parts, long long n_parts, double* out) {
-  __shared__ double red[kFinishThreads / 64][2];
-  double s0 = 0.0, s1 = 0.0;
-  for (long long i = threadIdx.x; i < n_parts; i += kFinishThreads) {   // thread t: partials t, t + 256, ... in that order
-    s0 += parts[2 * i];
-    s1 += parts[2 * i + 1];
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s0 = wave_sum_d(s0);
-  s1 = wave_sum_d(s1);
-  if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = 0.0;
-    for (int w = 0; w < kFinishThreads / 64; ++w) s += red[w][threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-}
-
-// the workgroup's two float64 partials -> parts[2 * blockIdx.x ..]; every thread of the workgroup calls it
-template <int THREADS>
-__device__ inline void store_partials(double s0, double s1, double* parts) {
-  __shared__ double red[THREADS / 64][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s0 = wave_sum_d(s0);
-  s1 = wave_sum_d(s1);
-  if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = 0.0;
-    for (int w = 0; w < THREADS / 64; ++w) s += red[w][threadIdx.x];
-    parts[2 * (long long)blockIdx.x + threadIdx.x] = s;
-  }
+  gather_sum_d<kFinishThreads, 2>(parts, n_parts, out);
 }
 
 // ---- SSIM ----
@@ -146,7 +115,8 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_kernel(SsimParams p) {
     const double d = (double)sA[oy + R][ox + R] - (double)sB[oy + R][ox + R];
     sq_sum += d * d;
   }
-  store_partials<kSsimThreads>(ssim_sum, sq_sum, p.parts);
+  const double sums[2] = {ssim_sum, sq_sum};
+  block_sum_d<kSsimThreads, 2>(sums, p.parts + 2 * (long long)blockIdx.x);
 }
 
 // ---- squared error ----
@@ -162,7 +132,8 @@ __global__ __launch_bounds__(kSqerrThreads) void sqerr_kernel(const float* a, co
     sq += m ? d * d : 0.0;
     cnt += m ? 1.0 : 0.0;
   }
-  store_partials<kSqerrThreads>(sq, cnt, parts);
+  const double sums[2] = {sq, cnt};
+  block_sum_d<kSqerrThreads, 2>(sums, parts + 2 * (long long)blockIdx.x);
 }
 
 inline long long ssim_workgroups(long long B, long long C, long long H, long long W) {

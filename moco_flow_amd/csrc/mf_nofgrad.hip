@@ -15,9 +15,9 @@
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_plan.hpp"
 #include "mf_bwd.hpp"
 #include "mf_nofbwd.hpp"
-#include <cstdlib>
 
 namespace mf {
 
@@ -49,10 +49,7 @@ __global__ __launch_bounds__(kThreads, 2) void nof_points_dump_kernel(NofDumpPar
   load_resident(net, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes);
   start_program(net, st, carry, id);
   const int D = net.L.n_trunk;
   const long long ntiles = (p.P + kTile - 1) / kTile;
@@ -164,10 +161,7 @@ __global__ __launch_bounds__(kThreads, 2) void nof_backward_kernel(NofBwdParams 
   load_resident(net, id);
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = MF_TIMING_FLAGS ? p.dbg : 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes, MF_TIMING_FLAGS ? p.dbg : 0);
   const uint32_t zero_bias = net.res_lds + net.L.off_bias_trunk * 4;
   const uint32_t headw = net.res_lds + net.L.off_head_w * 4;
   const char* first = net.packed + net.L.res_bytes;
@@ -311,20 +305,19 @@ extern "C" int32_t mf_nof_points_dump(const mf_nof_desc* d, const void* packed, 
     return fail(MF_E_INVALID, "mf_nof_points_dump: null argument");
   NofDumpParams p{};
   if (!nof_layout(*d, p.net.L)) return fail(MF_E_UNSUPPORTED, "mf_nof_points_dump: unsupported NoF configuration");
+  // (not check_nof_embeddings: the dump's embedded rows are [xyz 33 | ind 33], so the index embedding must have EXACTLY 16 frequencies)
   if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 5 || emb_ind->in_channels != 1 || emb_ind->n_freqs != 16)
     return fail(MF_E_UNSUPPORTED, "mf_nof_points_dump: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, 16 freqs)");
   if (S < 1 || stride < (int64_t)d->D * kNofW + kNofHeadPad || (stride & 3))
     return fail(MF_E_INVALID, "mf_nof_points_dump: S=%d / stride=%lld invalid", S, (long long)stride);
   if (P == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed);
   emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
   emb_table(*emb_ind, p.eind.freq, p.eind.weight);
   p.pts = pts; p.inputs = nullptr; p.in_stride = 0; p.ind = ind; p.ind_stride = ind_stride; p.P = P; p.S = S; p.out = out; p.acts = acts; p.stride = stride; p.emb = emb;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  return launch_lds(nof_points_dump_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_points_dump", "mf_nof_points_dump");
+  plan.ring(p.ring_off, p.buf_bytes);
+  return launch_lds(nof_points_dump_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_nof_points_dump", "mf_nof_points_dump");
 }
 
 extern "C" int32_t mf_nof_forward_dump(const mf_nof_desc* d, const void* packed, const float* inputs, int64_t in_stride,
@@ -336,14 +329,12 @@ extern "C" int32_t mf_nof_forward_dump(const mf_nof_desc* d, const void* packed,
   if (stride < (int64_t)d->D * kNofW + kNofHeadPad || (stride & 3))
     return fail(MF_E_INVALID, "mf_nof_forward_dump: stride=%lld invalid", (long long)stride);
   if (B == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed);
   p.pts = xyz; p.inputs = inputs; p.in_stride = in_stride; p.ind = nullptr; p.ind_stride = 0; p.P = B; p.S = 1;
   p.out = out; p.acts = acts; p.stride = stride; p.emb = nullptr;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  return launch_lds(nof_points_dump_kernel, persistent_grid((B + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward_dump", "mf_nof_forward_dump");
+  plan.ring(p.ring_off, p.buf_bytes);
+  return launch_lds(nof_points_dump_kernel, persistent_grid((B + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_nof_forward_dump", "mf_nof_forward_dump");
 }
 
 extern "C" int64_t mf_nof_bwd_packed_bytes(const mf_nof_desc* d) {
@@ -386,20 +377,16 @@ extern "C" int32_t mf_nof_backward(const mf_nof_desc* d, const void* packed_bwd,
     return fail(MF_E_INVALID, "mf_nof_backward: null argument");
   NofBwdParams p{};
   if (!nof_bwd_layout(*d, p.net.L, p.skip)) return fail(MF_E_UNSUPPORTED, "mf_nof_backward: unsupported NoF configuration");
-  if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 5)
-    return fail(MF_E_UNSUPPORTED, "mf_nof_backward: xyz embedding must have 3 channels and <= 5 frequencies");
+  if (int e = check_xyz_embedding("mf_nof_backward", *emb_xyz, 5)) return e;
   if (stride < (int64_t)d->D * kNofW + kNofHeadPad || (stride & 3))
     return fail(MF_E_INVALID, "mf_nof_backward: stride %lld invalid", (long long)stride);
   if (P == 0) return MF_OK;
-  p.net.packed = static_cast<const char*>(packed_bwd);
-  p.net.res_lds = 0;
+  LdsPlan plan;
+  plan.place(p.net, packed_bwd);
   emb_table(*emb_xyz, p.exyz.freq, p.exyz.weight);
   p.D = d->D; p.P = P; p.stride = stride;
   p.pts = pts; p.acts = acts; p.g_out = g_out; p.gpre = gpre; p.g_pts = g_pts;
-  p.ring_off = (uint32_t)p.net.L.res_bytes;
-  p.buf_bytes = (uint32_t)p.net.L.max_groups * kGroupBytes;
-  p.dbg = 0;
-  if (const char* e = getenv("MF_DEBUG_FLAGS")) p.dbg = atoi(e);   // timing ablations only
-  const size_t lds = p.ring_off + 3 * (size_t)p.buf_bytes;
-  return launch_lds(nof_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, lds, static_cast<hipStream_t>(stream), p, "mf_nof_backward", "mf_nof_backward");
+  plan.ring(p.ring_off, p.buf_bytes);
+  p.dbg = debug_flags();
+  return launch_lds(nof_backward_kernel, persistent_grid((P + kTile - 1) / kTile), kThreads, plan.lds, static_cast<hipStream_t>(stream), p, "mf_nof_backward", "mf_nof_backward");
 }

@@ -17,6 +17,7 @@
 #include "mf_bwd3.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
+#include "mf_plan.hpp"
 #include "mf_nofbwd.hpp"
 
 namespace mf {
@@ -280,8 +281,7 @@ extern "C" int32_t mf_nof_backward3(const mf_nof_desc* d, const void* packed_bwd
   if (!d || !packed_bwd3 || !emb_xyz || (P > 0 && (!pts || !acts || !g_out || !gpre)))
     return fail(MF_E_INVALID, "mf_nof_backward3: null argument");
   if (!nof_bwd3_shape(d, skip)) return fail(MF_E_UNSUPPORTED, "mf_nof_backward3: unsupported NoF configuration");
-  if (emb_xyz->in_channels != 3 || emb_xyz->n_freqs > 5)
-    return fail(MF_E_UNSUPPORTED, "mf_nof_backward3: xyz embedding must have 3 channels and <= 5 frequencies");
+  if (int e = check_xyz_embedding("mf_nof_backward3", *emb_xyz, 5)) return e;
   if (stride < (int64_t)d->D * bf::kNW + 16 || (stride & 3) || (reinterpret_cast<uintptr_t>(acts) & 15) || (reinterpret_cast<uintptr_t>(gpre) & 15))
     return fail(MF_E_INVALID, "mf_nof_backward3: dump rows must be 16-byte aligned with a stride >= D W + 16 that is a multiple of 4 floats");
   if (P == 0) return MF_OK;
@@ -301,7 +301,7 @@ extern "C" int32_t mf_nof_backward3(const mf_nof_desc* d, const void* packed_bwd
   uint32_t lds = p.net.res_bytes;
   p.par_off = lds; lds += 128;
   lds = (lds + 1023u) & ~1023u;
-  p.ring_off = lds; p.buf_bytes = 16 * kGroupBytes; lds += 3 * p.buf_bytes;
+  place_ring(lds, 16, p.ring_off, p.buf_bytes);
   const long long ntiles = (P + 127) / 128;
   // 207 VGPRs + 48 AGPRs and 53 KiB of LDS per workgroup: TWO workgroups fit a CU (two waves per SIMD, each other's cover
   // during the VALU phases around the chain), so the persistent grid is two per CU

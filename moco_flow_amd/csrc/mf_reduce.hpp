@@ -1,5 +1,14 @@
-// mf_reduce.hpp -- float64 sum over the 64 lanes of a wave: the last step before a workgroup stores its partial of a
-// fixed-order reduction (mf_loss.hip, mf_metrics.hip).
+// mf_reduce.hpp -- the fixed-order float64 reduction of the library, written once.  Users:
+//   mf_loss.hip       loss_partials_kernel / loss_finish_kernel               12 slots
+//   mf_supervise.hip  point_loss_partials_kernel / point_loss_finish_kernel    5 slots
+//   mf_metrics.hip    ssim_kernel, sqerr_kernel / metrics_finish_kernel        2 slots
+// THE CONTRACT IS THE ORDER OF THE ADDITIONS; "two runs are bit-identical, no atomics"  rests on it:
+//   a thread      adds its own elements (or, in a finish, the partial rows t, t + THREADS, t + 2 THREADS, ...) in ascending order
+//   wave_sum_d    adds the 64 lanes of a wave in the fixed tree below
+//   block_sum_d   adds the waves' sums from 0.0 in wave order 0, 1, 2, ...
+//   a launch      stores one row of SLOTS partials per workgroup (block_sum_d -> parts + blockIdx.x * SLOTS); ONE finishing
+//                 workgroup gathers the rows (gather_sum_d) -- into the result, or into LDS in front of an epilogue of its own
+// Every chain starts at +0.0, so no partial is ever -0.0 and `0.0 + x` is `x`.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +40,41 @@ __device__ inline double wave_sum_d(double v) {
   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
   return __builtin_bit_cast(double, (unsigned long long)lo | ((unsigned long long)hi << 32));
+}
+
+// The workgroup's sums of SLOTS per-thread values -> dst[0 .. SLOTS), written by threads 0 .. SLOTS - 1.  Every one of the
+// THREADS threads calls it, once per kernel.  dst: the workgroup's row of the partials, or LDS that the caller reads after a
+// __syncthreads() of its own.
+template <int THREADS, int SLOTS>
+__device__ inline void block_sum_d(const double (&v)[SLOTS], double* dst) {
+  static_assert(THREADS % 64 == 0 && SLOTS <= THREADS, "whole waves, one thread per slot");
+  __shared__ double red[THREADS / 64][SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    const double s = wave_sum_d(v[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < SLOTS) {
+    double s = 0.0;
+    for (int w = 0; w < THREADS / 64; ++w) s += red[w][threadIdx.x];
+    dst[threadIdx.x] = s;
+  }
+}
+
+// The finishing workgroup: the sums of the (n_parts, SLOTS) partial rows -> dst[0 .. SLOTS).  Thread t adds rows t, t + THREADS,
+// ... from 0.0 in that order (independent loads: one thread per slot walking the rows took longer than the partials kernel).
+template <int THREADS, int SLOTS>
+__device__ inline void gather_sum_d(const double* parts, long long n_parts, double* dst) {
+  double v[SLOTS];
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) v[k] = 0.0;
+  for (long long i = threadIdx.x; i < n_parts; i += THREADS) {
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) v[k] += parts[i * SLOTS + k];
+  }
+  block_sum_d<THREADS, SLOTS>(v, dst);
 }
 
 }  // namespace mf

@@ -16,11 +16,11 @@
 // group's rays are composited by one wave per ray with a wavefront product-scan.  Workgroups
 // are persistent (grid = #CUs) so the weight stream never drains between tiles.
 #include <cstddef>
-#include <cstdlib>
 
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
 #include "mf_nets.hpp"
+#include "mf_plan.hpp"
 #include "mf_raypass.hpp"
 
 namespace mf {
@@ -63,10 +63,7 @@ __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
                  par_nof_ind = p.par_off + 384;
   Stream st;
   CarryT<kPD> carry;
-  st.ring = p.ring_off;
-  st.buf_bytes = p.buf_bytes;
-  st.dbg = MF_TIMING_FLAGS ? p.dbg : 0;
-  st.keep2 = 0;
+  st.open(p.ring_off, p.buf_bytes, MF_TIMING_FLAGS ? p.dbg : 0);
   st.tl.start(p.alphas, id);
   // the panel program of a tile: [bw NoF, fw NoF chains,] NeRF, then around again
   const NextLayer prog_first = MOCO ? follow_of(p.bw) : follow_of(nerf);
@@ -266,8 +263,8 @@ static int32_t check_render_args(const mf_render_args* a, NetLayout (&L)[3]) {
   const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
   if (dump && a->precision == MF_PREC_BF16)
     return fail(MF_E_UNSUPPORTED, "mf_render_pass: the activation dump (training forward) exists in fp32 and in bf16x3");
-  if (a->emb_xyz.in_channels != 3 || a->emb_xyz.n_freqs > 10)
-    return fail(MF_E_UNSUPPORTED, "mf_render_pass: xyz embedding must have 3 channels and <= 10 frequencies");
+  if (int e = check_xyz_embedding("mf_render_pass", a->emb_xyz, 10)) return e;
+  // (the extra block's check stays here: MF_E_UNSUPPORTED and n_freqs < 0 read as no frequencies, unlike mf_points_radiance's -- mf_plan.hpp)
   const bool sigma_only = a->flags & MF_F_SIGMA_ONLY;
   if (!sigma_only && a->nerf->extra_feat_type == MF_EXTRA_DIR &&
       (a->emb_extra.in_channels != 3 || a->emb_extra.n_freqs > 4 ||
@@ -291,9 +288,7 @@ static int32_t check_render_args(const mf_render_args* a, NetLayout (&L)[3]) {
       if (!a->nof_fw || !a->nof_fw_packed) return fail(MF_E_INVALID, "mf_render_pass: chain flags need the forward NoF");
       if (!nof_layout(*a->nof_fw, L[2], 0)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: unsupported forward NoF configuration");
     }
-    if (a->nof_emb_xyz.in_channels != 3 || a->nof_emb_xyz.n_freqs > 5 || a->nof_emb_ind.in_channels != 1 ||
-        a->nof_emb_ind.n_freqs > 16)
-      return fail(MF_E_UNSUPPORTED, "mf_render_pass: NoF embeddings must be xyz(3, <=5 freqs) and ind(1, <=16 freqs)");
+    if (int e = check_nof_embeddings("mf_render_pass", a->nof_emb_xyz, a->nof_emb_ind)) return e;
   }
   return MF_OK;
 }
@@ -304,14 +299,9 @@ static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3],
   const bool chains = a->flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL);
   RenderParams p{};
   fill_render_io(p, a);
-  { const char* e = getenv("MF_DEBUG_FLAGS"); p.dbg = e ? atoi(e) : 0; }   // timing ablations only
-  uint32_t lds = 0;
-  int max_groups = 0;
-  auto place = [&](NetDev& n, const NetLayout& l, const void* packed) {     // resident block at `lds`, largest panel so far
-    n.L = l; n.packed = static_cast<const char*>(packed);
-    n.res_lds = lds; lds += (uint32_t)l.res_bytes;
-    if (l.max_groups > max_groups) max_groups = l.max_groups;
-  };
+  p.dbg = debug_flags();
+  LdsPlan plan;
+  auto place = [&](NetDev& n, const NetLayout& l, const void* packed) { n.L = l; plan.place(n, packed); };
   place(p.nerf, L[0], a->nerf_packed);
   emb_table(a->emb_xyz, p.emb_par[0], p.emb_par[0] + 16);
   emb_table(a->emb_extra, p.emb_par[1], p.emb_par[1] + 16);
@@ -321,10 +311,9 @@ static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3],
     emb_table(a->nof_emb_xyz, p.emb_par[2], p.emb_par[2] + 16);
     emb_table(a->nof_emb_ind, p.emb_par[3], p.emb_par[3] + 16);
   }
-  p.par_off = lds; lds += 512;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
+  p.par_off = plan.place_tables();
+  plan.ring(p.ring_off, p.buf_bytes);
+  uint32_t lds = plan.lds;                 // the group's sample buffers go behind the ring
 
   if (int e = plan_ray_groups(a->n_rays, a->n_samples, kTile, lds, p.G, p.n_groups)) return e;
   place_sample_buffers(p, lds);

@@ -9,6 +9,7 @@
 #include "mf_bf16.hpp"
 #include "mf_host.hpp"
 #include "mf_layout.hpp"
+#include "mf_plan.hpp"
 #include "mf_raypass.hpp"
 
 namespace mf {
@@ -543,9 +544,7 @@ static int place_networks(P& p, Net* fw_net, int prec, const mf_nerf_desc* nerf,
     set_emb_table(p, 3, *nof_emb_ind);
   }
   p.par_off = lds; lds += 512;
-  p.ring_off = lds;
-  p.buf_bytes = (uint32_t)max_groups * kGroupBytes;
-  lds += 3 * p.buf_bytes;
+  place_ring(lds, max_groups, p.ring_off, p.buf_bytes);
   return MF_OK;
 }
 

@@ -4,8 +4,8 @@
 //                                     inside = dist < thickness                    datasets/moco_flow_dataset.py:107-132
 //   mf_point_loss_partials          : the three point losses as (sum, count) pairs  trainer/trainer_moco_flow.py:146-157, 330-363
 //   mf_point_loss_partials_backward : their seeds, written whole (zeros where the mask is off)
-// Outputs are full length and keep the queries' order; the inside / outside split is a mask.  The reductions are fixed-order
-// partial sums through `scratch`: no atomics, bit-identical from run to run.
+// Outputs are full length and keep the queries' order; the inside / outside split is a mask.  The reductions are the fixed-order
+// sums of mf_reduce.hpp through `scratch`: no atomics, bit-identical from run to run.
 #include "mf_host.hpp"
 #include "mf_reduce.hpp"
 
@@ -117,7 +117,6 @@ struct PointLossParams {
 __device__ __forceinline__ float softplus_torch(float s) { return s > 20.f ? s : log1pf(expf(s)); }
 
 __global__ __launch_bounds__(kPtLossThreads) void point_loss_partials_kernel(const PointLossParams p) {
-  __shared__ double red[kPtLossThreads / 64][kPtLossSlots];
   double acc[kPtLossSlots];
 #pragma unroll
   for (int k = 0; k < kPtLossSlots; ++k) acc[k] = 0.0;
@@ -143,39 +142,13 @@ __global__ __launch_bounds__(kPtLossThreads) void point_loss_partials_kernel(con
       }
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kPtLossSlots; ++k) {
-    const double s = wave_sum_d(acc[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPtLossSlots) {
-    double s = 0.0;
-    for (int w = 0; w < kPtLossThreads / 64; ++w) s += red[w][threadIdx.x];
-    p.scratch[(long long)blockIdx.x * kPtLossSlots + threadIdx.x] = s;
-  }
+  block_sum_d<kPtLossThreads, kPtLossSlots>(acc, p.scratch + (long long)blockIdx.x * kPtLossSlots);
 }
 
-// one workgroup: thread b holds block b's partials, then the fixed tree of mf_loss.hip's finish kernel
+// one workgroup gathers the blocks' partials (thread b: block b's; none when Q = 0), then the pairs and the means
 __global__ __launch_bounds__(kPtLossMaxBlocks) void point_loss_finish_kernel(const PointLossParams p, int n_blocks) {
   __shared__ double tot[kPtLossSlots];
-  __shared__ double red[kPtLossMaxBlocks / 64][kPtLossSlots];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[kPtLossSlots];
-#pragma unroll
-  for (int k = 0; k < kPtLossSlots; ++k) v[k] = (int)threadIdx.x < n_blocks ? p.scratch[(long long)threadIdx.x * kPtLossSlots + k] : 0.0;
-#pragma unroll
-  for (int k = 0; k < kPtLossSlots; ++k) {
-    const double s = wave_sum_d(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPtLossSlots) {
-    double s = 0.0;
-    for (int w = 0; w < kPtLossMaxBlocks / 64; ++w) s += red[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
+  gather_sum_d<kPtLossMaxBlocks, kPtLossSlots>(p.scratch, n_blocks, tot);
   __syncthreads();
   if (threadIdx.x == 0) {
     p.out6[0] = p.pred_bw ? tot[0] : 0.0; p.out6[1] = p.pred_bw ? 3.0 * tot[3] : 0.0;

@@ -17,7 +17,11 @@ pytestmark = pytest.mark.gpu
 TILE_H, TILE_W = 16, 32          # mf_metrics.hip: kSsimTileH, kSsimTileW
 SQERR_SHARE = 256 * 8            # mf_metrics.hip: elements of one sqerr workgroup before the grid stops growing
 
-MAP_SHAPES = [(1, 3, 37, 53), (2, 3, 6, 7), (1, 3, TILE_H + 1, 2 * TILE_W + 1), (1, 1, TILE_H, TILE_W), (1, 3, 11, 300)]
+SQERR_MAX_BLOCKS = 1024          # mf_metrics.hip: kSqerrMaxBlocks
+FINISH_THREADS = 256             # mf_metrics.hip: kFinishThreads -- the finishing workgroup takes ceil(partial rows / 256) trips
+
+# (1, 3, 160, 320): 10 x 10 x 3 = 300 workgroups, so the finish takes two trips; every other shape finishes in one
+MAP_SHAPES = [(1, 3, 37, 53), (2, 3, 6, 7), (1, 3, TILE_H + 1, 2 * TILE_W + 1), (1, 1, TILE_H, TILE_W), (1, 3, 11, 300), (1, 3, 160, 320)]
 MAP_CASES = [(s, ws) for s in MAP_SHAPES for ws in (3, 7, 11) if ws // 2 < min(s[2], s[3])]
 
 
@@ -150,6 +154,46 @@ def test_mse_psnr_unmasked_and_elementwise_mask(M, n):
     assert out[1].item() == int(mask.sum())
     assert abs(out[0].item() - sq[mask].sum().item()) <= 1e-6 * sq[mask].sum().item()
     assert M.mse(ga, gb, mask.cuda()).item() == pytest.approx(O.mse(a.double(), b.double(), mask).item(), rel=1e-6)
+
+
+# ---- exact sums: inputs that are multiples of 1/16 in [0, 1].  Every fp32 difference is a multiple of 1/16, every square a multiple
+# of 2^-8 below 1, and a sum of up to 2^22 of them has at most 30 significant bits: exact in float64 WHATEVER the order of the
+# additions, so `==` holds for any correct reduction and a lost, doubled or misplaced partial row shows as a wrong integer.
+
+def sixteenths(shape, seed):
+    return torch.randint(0, 17, shape, generator=torch.Generator().manual_seed(seed)).float() / 16
+
+
+def exact_sqerr(a, b, mask=None):
+    d = (a * 16).long() - (b * 16).long()
+    sq = d * d
+    return int((sq if mask is None else sq[mask]).sum()) / 256
+
+
+def test_sqerr_exact_block_cap_binds_finish_takes_four_trips(M):
+    n = SQERR_MAX_BLOCKS * SQERR_SHARE + 1                               # one element more than 1024 workgroups' first trip
+    assert -(-n // SQERR_SHARE) > SQERR_MAX_BLOCKS and SQERR_MAX_BLOCKS // FINISH_THREADS == 4
+    a, b = sixteenths((n,), 31), sixteenths((n,), 32)
+    ga, gb = a.cuda(), b.cuda()
+    out = M._sqerr(ga, gb, None, "mse").cpu()
+    print(f"\nsqerr n={n}: sum {out[0].item()!r} exact {exact_sqerr(a, b)!r} count {out[1].item()!r}")
+    assert out[0].item() == exact_sqerr(a, b)
+    assert out[1].item() == n
+    mask = torch.rand(n, generator=torch.Generator().manual_seed(33)) < 0.4
+    out = M._sqerr(ga, gb, mask.cuda(), "mse").cpu()
+    print(f"masked: sum {out[0].item()!r} exact {exact_sqerr(a, b, mask)!r} count {out[1].item()!r} of {int(mask.sum())}")
+    assert out[0].item() == exact_sqerr(a, b, mask)
+    assert out[1].item() == int(mask.sum())
+
+
+def test_ssim_squared_error_exact_finish_takes_two_trips(M):
+    shape = (1, 3, 160, 320)
+    wgs = shape[1] * -(-shape[2] // TILE_H) * -(-shape[3] // TILE_W)
+    assert wgs == 300 and FINISH_THREADS < wgs <= 2 * FINISH_THREADS
+    a, b = sixteenths(shape, 41), sixteenths(shape, 42)
+    _, sums = ssim_raw(M, a.cuda(), b.cuda(), 3, want_map=False)
+    print(f"\nssim {shape}: squared error {sums[1].item()!r} exact {exact_sqerr(a, b)!r}")
+    assert sums[1].item() == exact_sqerr(a, b)
 
 
 @pytest.mark.parametrize("N", [1, 21, 683, 540 * 540])

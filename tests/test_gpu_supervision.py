@@ -182,12 +182,15 @@ def test_fused_query_generation(M):
 DELTAS = (1 / 128, 1 / 256)
 
 
+PT_LOSS_THREADS, PT_LOSS_MAX_BLOCKS = 256, 256       # mf_supervise.hip: kPtLossThreads, kPtLossMaxBlocks
+Q_CAPPED = PT_LOSS_THREADS * PT_LOSS_MAX_BLOCKS + 300  # the 256-block cap binds; the first 300 threads take a second grid-stride trip
+
+
 @functools.lru_cache(maxsize=None)
-def loss_case():
-    """Q = 300 rows, about half inside, two sigma planes drawn from [-6, 6] (alpha <= 0.5 there: delta softplus(6) < 0.05) with
+def loss_case(Q=300):
+    """Q rows (300 unless said), about half inside, two sigma planes drawn from [-6, 6] (alpha <= 0.5 there: delta softplus(6) < 0.05) with
     25 and -40 planted on outside rows, and one prediction equal to its target."""
     g = torch.Generator().manual_seed(21)
-    Q = 300
     pairs = torch.randn((Q, 6), generator=g)
     inside = torch.rand(Q, generator=g) < 0.5
     inside[:4] = torch.tensor([False, False, True, False])
@@ -258,6 +261,45 @@ def test_point_loss_partials_values(M):
     every, _ = _partials(M, c, inside, use_all=True)
     assert torch.equal(no_mask[:4], all_in[:4]) and no_mask[5] == 0
     assert torch.equal(every[:4], all_in[:4]) and torch.equal(every[4:], out6[4:])
+    again, means2 = _partials(M, c, inside)
+    assert torch.equal(again, out6) and torch.equal(means2, means)                                     # bit-identical runs
+
+
+def test_point_loss_partials_block_cap_binds_values(M):
+    """loss_case()'s recipe at Q_CAPPED against the oracle, with test_point_loss_partials_values' bars."""
+    c = loss_case(Q_CAPPED)
+    inside = c["inside"]
+    assert -(-c["Q"] // PT_LOSS_THREADS) > PT_LOSS_MAX_BLOCKS
+    out6, means = _partials(M, c, inside)
+    want = O.point_losses(c["pairs"], inside, c["pred_bw"], c["pred_fw"], c["sig"], DELTAS)
+    for k, key in enumerate(("nof_bw", "nof_fw", "alphas_mask")):
+        print(f"{key}: {float(means[k]):.9g} vs the oracle's {float(want[key][0]):.9g}, difference "
+              f"{abs(float(means[k]) - float(want[key][0])):.3e}; count {float(out6[2 * k + 1])!r} vs {want[key][1]}")
+        assert out6[2 * k + 1] == want[key][1]
+    mean_bce = float(out6[4] / out6[5])
+    assert abs(float(means[2]) - float(want["alphas_mask"][0])) <= 1e-6                                # the BCE mean's bar
+    assert abs(mean_bce - float(want["alphas_mask"][0])) <= 1e-6
+
+
+def test_point_loss_partials_block_cap_binds_exact_l1(M):
+    """Predictions and targets that are multiples of 1/16 in [0, 1]: every fp32 |a - b| is one too, and a sum of 3 Q of them has
+    fewer than 30 significant bits -- exact in float64 whatever the order of the additions, so the L1 sums must EQUAL the integer
+    arithmetic's, and a row lost or taken twice on the second grid-stride trip shows in them and in the counts."""
+    Q = Q_CAPPED
+    g = torch.Generator().manual_seed(77)
+    k16 = lambda *shape: torch.randint(0, 17, shape, generator=g)
+    pairs, bw, fw = k16(Q, 6), k16(Q, 3), k16(Q, 3)
+    inside = torch.rand(Q, generator=g) < 0.5
+    sig = [torch.rand(Q, generator=g) * 12 - 6 for _ in DELTAS]
+    c = dict(Q=Q, pairs=pairs.float() / 16, pred_bw=bw.float() / 16, pred_fw=fw.float() / 16, sig=sig)
+    out6, means = _partials(M, c, inside)
+    n_in, n_out = int(inside.sum()), int((~inside).sum())
+    want_bw = int((bw - pairs[:, 3:]).abs()[inside].sum()) / 16
+    want_fw = int((fw - pairs[:, :3]).abs()[inside].sum()) / 16
+    print(f"Q={Q}: L1 sums {float(out6[0])!r} {float(out6[2])!r} exact {want_bw!r} {want_fw!r}; counts {out6[1::2].tolist()} "
+          f"for {n_in} inside, {n_out} outside")
+    assert float(out6[0]) == want_bw and float(out6[2]) == want_fw
+    assert out6[1] == 3 * n_in and out6[3] == 3 * n_in and out6[5] == 2 * n_out
     again, means2 = _partials(M, c, inside)
     assert torch.equal(again, out6) and torch.equal(means2, means)                                     # bit-identical runs
 
