@@ -563,7 +563,8 @@ int32_t mf_smpl_lbs(const mf_smpl_model* m, const float* pose, int32_t pose_is_r
 int32_t mf_smpl_frame_transforms(const float* T_src, const float* T_tgt, int64_t V, float* trans, void* stream);
 
 /* datasets/moco_flow_dataset.py:127-129: cano (Q,3) = (trans[ind] @ [query, 1])[:3]; ind (Q,) int64 into the V
- * transforms (mf_knn1's output). */
+ * transforms (mf_knn1's output).  An index outside [0, V - 1] is clamped to that range before any address is formed:
+ * a negative one reads transform 0, one >= V reads transform V - 1. */
 int32_t mf_apply_vertex_transforms(const float* trans, const int64_t* ind, int64_t V, const float* query, int64_t Q,
                                    float* cano, void* stream);
 

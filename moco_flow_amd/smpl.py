@@ -61,14 +61,18 @@ class SMPL(nn.Module):
         self._packed = None
 
     def _model(self, dev):
-        """(descriptor, tensors kept alive): contiguous device copies in the layout the kernels read."""
-        key = (str(dev), self.shapedirs.data_ptr(), self.posedirs.data_ptr())
+        """(descriptor, tensors kept alive): contiguous device copies in the layout the kernels read.  Rebuilt when the
+        device or any model buffer changes -- reassigned (another data_ptr) or edited in place (another _version); both are
+        host-side reads, so an unchanged model costs no copy and no sync.  The source tensors are kept alive with the
+        copies: a freed buffer's address cannot come back under a new tensor and match the key."""
+        src = (self.v_template, self.shapedirs, self.posedirs, self.J_regressor, self.weights, self.parent)
+        key = (str(dev),) + tuple((t.data_ptr(), t._version) for t in src)
         if self._packed is None or self._packed[0] != key:
             V = self.vert_num
             keep = dict(vt=self.v_template.to(dev).contiguous(),
                         sd=self.shapedirs[:, :, :10].to(dev).reshape(V * 3, 10).contiguous(),       # :99
                         pd=self.posedirs.to(dev).reshape(V * 3, 207).contiguous(),                  # :119
-                        jr=self.J_regressor.to(dev).contiguous(), w=self.weights.to(dev).contiguous())
+                        jr=self.J_regressor.to(dev).contiguous(), w=self.weights.to(dev).contiguous(), src=src)
             d = L.mf_smpl_model()
             d.n_verts = V
             d.v_template, d.shapedirs, d.posedirs = keep["vt"].data_ptr(), keep["sd"].data_ptr(), keep["pd"].data_ptr()
