@@ -17,6 +17,7 @@ import torch
 
 from . import _lib as L
 from . import autograd as A
+from .packing import BuildOrder
 
 # Arithmetic of the hidden (256-/128-wide) GEMMs of the fused pass: "f32" = exact-fp32 MFMA (the
 # reference's arithmetic, BASELINE configs C1-C2; default); "bf16" = bf16 operands with fp32
@@ -74,12 +75,16 @@ _LINSPACE = {}
 
 
 def _linspace01(S, dev):
-    """torch.linspace(0, 1, S) on the device, built once per (S, device): a launch per render_rays call otherwise."""
+    """torch.linspace(0, 1, S) on the device, built once per (S, device): a launch per render_rays call otherwise.
+    A caller under another stream than the first one's waits for that fill (packing.BuildOrder)."""
     key = (S, str(dev))
-    t = _LINSPACE.get(key)
-    if t is None:
-        t = _LINSPACE[key] = torch.linspace(0, 1, S, device=dev)
-    return t
+    hit = _LINSPACE.get(key)
+    if hit is None:
+        order = BuildOrder(dev)
+        hit = _LINSPACE[key] = (torch.linspace(0, 1, S, device=dev), order)      # one store: table and its build stream
+    else:
+        hit[1].order(dev)
+    return hit[0]
 
 
 def _emb_desc(e):

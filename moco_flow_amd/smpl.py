@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from .packing import BuildOrder
 
 
 def _load_model(model):
@@ -67,8 +68,10 @@ class SMPL(nn.Module):
         copies: a freed buffer's address cannot come back under a new tensor and match the key."""
         src = (self.v_template, self.shapedirs, self.posedirs, self.J_regressor, self.weights, self.parent)
         key = (str(dev),) + tuple((t.data_ptr(), t._version) for t in src)
-        if self._packed is None or self._packed[0] != key:
+        packed = self._packed
+        if packed is None or packed[0] != key:
             V = self.vert_num
+            order = BuildOrder(dev) if torch.device(dev).type == "cuda" else None
             keep = dict(vt=self.v_template.to(dev).contiguous(),
                         sd=self.shapedirs[:, :, :10].to(dev).reshape(V * 3, 10).contiguous(),       # :99
                         pd=self.posedirs.to(dev).reshape(V * 3, 207).contiguous(),                  # :119
@@ -80,8 +83,10 @@ class SMPL(nn.Module):
             d.parent[0] = 0
             for i, p in enumerate(self.parent.tolist()):
                 d.parent[i + 1] = int(p)
-            self._packed = (key, d, keep)
-        return self._packed[1]
+            self._packed = packed = (key, d, keep, order)
+        elif packed[3] is not None:
+            packed[3].order(dev)        # a caller under another stream than the copies' waits for them (packing.BuildOrder)
+        return packed[1]
 
     def _lbs(self, pose, beta, want_verts, want_T):
         L.require_gpu(pose, "SMPL")

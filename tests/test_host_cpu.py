@@ -780,7 +780,7 @@ def test_packed_cache_does_not_travel():
     import moco_flow_amd._lib as L
     for m in (M.NeRF(8, 256, 63, [4], "dir", 27), M.NoF(4, 128, 33, [2], "ind", 33, True)):
         for c in (m._packed, m._packed_bf16, m._packed_bwd):       # what a first forward leaves behind
-            c.key, c.desc, c.buf, c.keep = ("k",), (L.mf_nerf_desc(), ctypes.pointer(L.mf_nerf_desc())), object(), [1]
+            c.state = (("k",), (L.mf_nerf_desc(), ctypes.pointer(L.mf_nerf_desc())), object(), [1], None)   # published as one object
         m2 = copy.deepcopy(m)
         assert m2._packed.key is None and m2._packed.desc is None and m2._packed is not m._packed
         m3 = pickle.loads(pickle.dumps(m))
