@@ -45,7 +45,8 @@ extern "C" {
  * additive entries since, version unchanged: mf_mc_scratch_bytes / mf_mc_count / mf_mc_emit; mf_ssim, mf_sqerr (+ their
  *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals;
  *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch; mf_point_correspond, mf_point_loss_partials
- *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward */
+ *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward; mf_nerf_fold_packed_bytes / mf_nerf_pack_fold
+ *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -140,6 +141,18 @@ int64_t mf_nerf_packed_bytes_p(const mf_nerf_desc* d, int32_t precision);
 int64_t mf_nof_packed_bytes_p(const mf_nof_desc* d, int32_t precision);
 int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void* packed, void* stream);
 int32_t mf_nof_pack_p(const mf_nof_desc* d, int32_t precision, void* packed, void* stream);
+/* The fp32 INFERENCE stream of a NeRF with xyz_encoding_final folded into extra_encoding (nerf.py:96-98: the final layer has
+ * no activation and extra_encoding is its only consumer; sigma is read in front of it):
+ *   extra_encoding(h) = relu(W' h + W_e[:, W:] ext + b'),  W' = W_e[:, :W] W_f,  b' = b_e + W_e[:, :W] b_f
+ * for h = the last trunk layer's output.  The stream is mf_nerf_pack's without the final layer's panels (256 of 2320 groups for
+ * the default NeRF); the resident block has the same size and offsets, its extra bias is b' and the final layer's bias slot is
+ * unused.  A small kernel in front of the pack computes W' and b' -- float64 sums over ascending k, rounded to fp32 once, no
+ * atomics: packs are bit-identical -- into a scratch area of round_up((W/2 * W + W/2) * 4, 1024) bytes (129 KiB) that is
+ * appended behind the panels and counted by mf_nerf_fold_packed_bytes.  fp32 and W = 256 only (0 / MF_E_UNSUPPORTED otherwise);
+ * extra_feat_type dir, ind or none.  Read by mf_render_pass with MF_F_FOLDED_FINAL; every other entry point takes the
+ * streams of mf_nerf_pack*.  Must be re-run whenever the parameters change. */
+int64_t mf_nerf_fold_packed_bytes(const mf_nerf_desc* d);
+int32_t mf_nerf_pack_fold(const mf_nerf_desc* d, void* packed, void* stream);
 
 /* Embedding.forward, models/embedding.py:30-47:  x (B, in_channels) -> out (B, C*(2F+1)). */
 int32_t mf_embedding_forward(const mf_embedding* e, const float* x, int64_t B, float* out, void* stream);
@@ -334,7 +347,10 @@ enum {
 enum {
   MF_F_SIGMA_ONLY   = 1 << 0,  /* weights_only=True: no rgb/depth (rendering.py:290-294)   */
   MF_F_CHAIN_LOCAL  = 1 << 1,  /* fw(bw(x,i),i) consensus (rendering.py:275-277)            */
-  MF_F_CHAIN_GLOBAL = 1 << 2   /* fw_i(bw_j(fw_j(bw_i(x)))) (rendering.py:279-282)          */
+  MF_F_CHAIN_GLOBAL = 1 << 2,  /* fw_i(bw_j(fw_j(bw_i(x)))) (rendering.py:279-282)          */
+  MF_F_FOLDED_FINAL = 1 << 3   /* nerf_packed is the stream of mf_nerf_pack_fold: MF_PREC_F32 only (bf16 / bf16x3:
+                                * MF_E_UNSUPPORTED), no dump_* pointer (MF_E_INVALID); results differ from the unfolded
+                                * pass by the rounding of W' alone (rgb ~2e-7 max-rel; sigma, depth, opacity, weights: none) */
 };
 
 typedef struct mf_render_args {

@@ -14,7 +14,7 @@ MF_MAX_FREQS = 16
 MF_MAX_LAYERS = 16
 MF_EXTRA_NONE, MF_EXTRA_IND, MF_EXTRA_DIR = 0, 1, 2
 MF_ACT_RELU, MF_ACT_SOFTPLUS = 0, 1
-MF_F_SIGMA_ONLY, MF_F_CHAIN_LOCAL, MF_F_CHAIN_GLOBAL = 1, 2, 4
+MF_F_SIGMA_ONLY, MF_F_CHAIN_LOCAL, MF_F_CHAIN_GLOBAL, MF_F_FOLDED_FINAL = 1, 2, 4, 8
 MF_PREC_F32, MF_PREC_BF16, MF_PREC_BF16X3 = 0, 1, 2
 PRECISIONS = {"f32": MF_PREC_F32, "bf16": MF_PREC_BF16, "bf16x3": MF_PREC_BF16X3}
 MF_ABI_VERSION = 16
@@ -132,6 +132,8 @@ SYMBOLS = {
     "mf_nof_forward": (C.c_int32, [C.POINTER(mf_nof_desc), _fp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp]),
     "mf_nerf_bwd_packed_bytes": (C.c_int64, [C.POINTER(mf_nerf_desc)]),
     "mf_nerf_pack_bwd": (C.c_int32, [C.POINTER(mf_nerf_desc), _fp, _fp]),
+    "mf_nerf_fold_packed_bytes": (C.c_int64, [C.POINTER(mf_nerf_desc)]),
+    "mf_nerf_pack_fold": (C.c_int32, [C.POINTER(mf_nerf_desc), _fp, _fp]),
     "mf_nof_points_dump": (C.c_int32, [C.POINTER(mf_nof_desc), _fp, C.POINTER(mf_embedding), C.POINTER(mf_embedding), _fp, _fp,
                                        C.c_int64, C.c_int32, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp]),
     "mf_nof_forward_dump": (C.c_int32, [C.POINTER(mf_nof_desc), _fp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp]),

@@ -129,6 +129,27 @@ inline bool nerf_layout(const mf_nerf_desc& d, NetLayout& L, int bf16 = 0) {
   return true;
 }
 
+// The folded fp32 stream (mf_nerf_pack_fold, MF_F_FOLDED_FINAL): xyz_encoding_final has no activation and extra_encoding is its
+// only consumer, so W' = W_e[:, :W] W_f and b' = b_e + W_e[:, :W] b_f replace the two layers' hidden part.  The stream is the
+// fp32 one without the final layer's NP panels -- trunk 0 .. D-1, then extra_encoding over [h_{D-1} ; extra block] -- and the
+// resident block keeps its size and offsets (the final layer's bias slot is unused, off_bias_extra holds b').  L stays the
+// unfolded layout: the kernels read the same offsets and panel sizes from it.  W' ((W/2) x W, row-major) and b' (W/2) live in
+// a scratch area behind the panels, padded to a whole group; it belongs to the packed buffer.  fp32 and W = 256 only.
+struct FoldLayout {
+  int64_t panel_bytes;       // the folded stream's panels
+  int64_t scratch_bytes;     // W' then b'
+  int64_t off_w, off_b;      // byte offsets of W' and b' in the packed buffer
+};
+inline bool nerf_fold_layout(const mf_nerf_desc& d, NetLayout& L, FoldLayout& F) {
+  F = FoldLayout{};
+  if (!nerf_layout(d, L, 0) || L.W != 256) return false;
+  F.panel_bytes = L.panel_bytes - (int64_t)trunk_groups(L, L.n_trunk - 1) * L.NP * kGroupBytes;
+  F.scratch_bytes = round_up(((int64_t)(L.W / 2) * L.W + L.W / 2) * 4, kGroupBytes);
+  F.off_w = L.res_bytes + F.panel_bytes;
+  F.off_b = F.off_w + (int64_t)(L.W / 2) * L.W * 4;
+  return true;
+}
+
 // wide_ok: W = 256 too (fp32 only) -- the reference's bare `NoF()` (models/nof.py:7-15: D = 8, W = 256, skips = [4]); built for the
 // module-level forward alone (mf_nof_forward and its packer): the fused passes keep three networks' resident blocks beside the ring
 // and have no room for 256-wide NoFs, every other entry point keeps rejecting them

@@ -25,6 +25,14 @@ MF_D NextLayer next_trunk(const NetDev& n, int layer) {   // trunk layer `layer`
   return f;
 }
 
+MF_D NextLayer next_extra(const NetDev& n) {              // the NeRF's extra_encoding, contiguous behind what runs in front of it
+  NextLayer f;
+  f.groups = extra_groups(n.L);
+  f.jump = nullptr;
+  f.bias_off = n.res_lds + n.L.off_bias_extra * 4;
+  return f;
+}
+
 // Copy a network's resident block (biases + VALU head weights) global -> LDS.
 MF_D void load_resident(const NetDev& n, const LaneId& id) {
   const int groups = (int)(n.L.res_bytes / kGroupBytes);
@@ -97,7 +105,9 @@ MF_D void extra_layer(const NetDev& net, const f32x4 (&act)[NK],
 // Canonical NeRF on this wave's 16 samples.  `follow`: the first layer of whatever the panel
 // program evaluates after this network (the stream jumps there behind the last panel used).
 // DUMP (training forward): `dump_row` = this lane's sample row [h_0 .. h_{D-1} | final | extra] (nullptr: skip).
-template <int NK, bool DUMP = false>
+// FOLD (fp32 inference, MF_F_FOLDED_FINAL): the stream of mf_nerf_pack_fold -- extra_encoding's panels (W' = W_e[:, :W] W_f in
+// their hidden block, b' as their bias) follow trunk layer D - 1 and read its output; xyz_encoding_final is not evaluated.
+template <int NK, bool DUMP = false, bool FOLD = false>
 MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const float (&ext)[kStepsExtraMax],
                     bool sigma_only, Stream& st, CarryT<kPD>& carry, const LaneId& id,
                     const NextLayer& follow, float& sigma, float (&rgb)[3], float* dump_row = nullptr,
@@ -107,10 +117,12 @@ MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const
   for (int t = 0; t < NK; ++t)
 #pragma unroll
     for (int i = 0; i < 4; ++i) act[t][i] = 0;
+  static_assert(!(FOLD && DUMP), "the dump rows hold xyz_encoding_final's output");
   const int D = net.L.n_trunk - 1;
   for (int l = 0; l < D; ++l) {
     const bool last = sigma_only && l == D - 1;
-    trunk_layer<NK, kStepsNerfXyz, DUMP>(net, l, act, embx, st, carry, id, last ? follow : next_trunk(net, l + 1),
+    trunk_layer<NK, kStepsNerfXyz, DUMP>(net, l, act, embx, st, carry, id,
+                                               last ? follow : ((FOLD && l == D - 1) ? next_extra(net) : next_trunk(net, l + 1)),
                                                dump_row ? dump_row + l * net.L.W : nullptr, mask_row ? mask_row + l * 8 : nullptr);
     st.tl.stamp(10 + l, id);
   }
@@ -119,12 +131,11 @@ MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const
   sigma = sg[0];
   st.tl.stamp(30, id);
   if (sigma_only) return;
-  NextLayer ex;
-  ex.groups = extra_groups(net.L);
-  ex.jump = nullptr;
-  ex.bias_off = net.res_lds + net.L.off_bias_extra * 4;
-  trunk_layer<NK, kStepsNerfXyz, DUMP>(net, D, act, embx, st, carry, id, ex,          // xyz_encoding_final
-                                             dump_row ? dump_row + D * net.L.W : nullptr);
+  if constexpr (!FOLD) {
+    const NextLayer ex = next_extra(net);
+    trunk_layer<NK, kStepsNerfXyz, DUMP>(net, D, act, embx, st, carry, id, ex,          // xyz_encoding_final
+                                               dump_row ? dump_row + D * net.L.W : nullptr);
+  }
   st.tl.stamp(31, id);
   f32x4 e[NK / 2];
   extra_layer<NK, DUMP>(net, act, ext, e, st, carry, id, follow, dump_row ? dump_row + (D + 1) * net.L.W : nullptr,

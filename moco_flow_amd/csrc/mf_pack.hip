@@ -3,7 +3,9 @@
 // Replaces nothing in the reference (it keeps (out,in) row-major tensors and calls addmm,
 // models/nerf.py:84-99, models/nof.py:70-75); this is the layout transform the fused kernels
 // need.  It is a pure permutation + zero padding: every packed float is either one source
-// weight or 0.  One kernel writes every stream from a region list (PackJob, mf_layout.hpp):
+// weight or 0 -- with ONE exception, the folded fp32 stream (mf_nerf_pack_fold): its extra_encoding
+// panels hold W' = W_e[:, :W] W_f and its extra bias b' = b_e + W_e[:, :W] b_f, which fold_final_kernel
+// computes in front of the pack (float64 sums in ascending k, rounded once).  One kernel writes every stream from a region list (PackJob, mf_layout.hpp):
 // the forward's here, each backward chain's -- the same layout of W^T -- next to the kernel
 // that reads it (mf_backward.hip, mf_nofgrad.hip, mf_backward_bf16.hip, mf_nofgrad_bf16.hip).
 #include <hip/hip_fp16.h>
@@ -135,6 +137,31 @@ __global__ void pack_ind_kernel(IndJob job) {
   job.dst[(e * kNofIndCols + c) * job.rows + r] = c < job.cols ? job.scale * job.W[e][(long long)r * job.n_in[e] + job.col0 + c] : 0.f;
 }
 
+// The fold of xyz_encoding_final into extra_encoding (mf_layout.hpp, FoldLayout): thread (n, k) writes
+// Wp[n][k] = sum_j We[n][j] Wf[j][k], the first W / 2 threads also bp[n] = be[n] + sum_j We[n][j] bf[j].  Every product of two
+// floats is exact in float64; the sums run over j ascending in float64 and are rounded to fp32 once.  No atomics: two packs of
+// the same weights are bit-identical.
+struct FoldJob { const float *We, *Wf, *be, *bf; int W, ld_e; float *Wp, *bp; };
+
+__global__ void fold_final_kernel(FoldJob job) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int half = job.W / 2;
+  if (idx >= half * job.W) return;
+  const int n = idx / job.W, k = idx % job.W;
+  const float* we = job.We + (long long)n * job.ld_e;
+  double acc = 0.0;
+  for (int j = 0; j < job.W; ++j) acc += (double)we[j] * (double)job.Wf[(long long)j * job.W + k];
+  job.Wp[idx] = (float)acc;
+  if (idx < half) {
+    const float* wb = job.We + (long long)idx * job.ld_e;
+    double b = 0.0;
+#ifndef MF_FOLD_BREAK_BIAS   // (-DMF_FOLD_BREAK_BIAS: the deliberately broken build the float64 test of the fold must reject: W_e b_f dropped)
+    for (int j = 0; j < job.W; ++j) b += (double)wb[j] * (double)job.bf[j];
+#endif
+    job.bp[idx] = (float)((double)job.be[idx] + b);
+  }
+}
+
 int launch_pack(const PackJob& job, hipStream_t st, const char* what) {
   const long long slots = job.total_groups * 64 > job.res_floats ? job.total_groups * 64 : job.res_floats;
   hipLaunchKernelGGL(pack_panels_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, job);
@@ -162,12 +189,19 @@ extern "C" int64_t mf_nof_packed_bytes_p(const mf_nof_desc* d, int32_t precision
   return L.res_bytes + L.panel_bytes + L.ind_bytes;
 }
 
-extern "C" int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void* packed, void* stream) {
+// fold (fp32): the folded stream of mf_nerf_pack_fold -- no panels and no bias for xyz_encoding_final, extra_encoding's hidden
+// block and bias from the scratch area behind the panels, which fold_final_kernel fills first
+static int32_t nerf_pack(const mf_nerf_desc* d, int32_t precision, void* packed, void* stream, bool fold) {
   NetLayout L;
+  FoldLayout F{};
   if (!d || !packed) return fail(MF_E_INVALID, "mf_nerf_pack: null argument");
   if (precision < MF_PREC_F32 || precision > MF_PREC_BF16X3) return fail(MF_E_INVALID, "mf_nerf_pack: precision %d", precision);
-  if (!nerf_layout(*d, L, precision)) return fail(MF_E_UNSUPPORTED, "mf_nerf_pack: unsupported NeRF configuration "
+  if (fold ? !nerf_fold_layout(*d, L, F) : !nerf_layout(*d, L, precision))
+    return fail(MF_E_UNSUPPORTED, "mf_nerf_pack: unsupported NeRF configuration "
                                        "(W=%d D=%d in_channels_xyz=%d)", d->W, d->D, d->in_channels_xyz);
+  const int64_t panel_bytes = fold ? F.panel_bytes : L.panel_bytes;
+  float* const fold_w = fold ? reinterpret_cast<float*>(static_cast<char*>(packed) + F.off_w) : nullptr;
+  float* const fold_b = fold ? reinterpret_cast<float*>(static_cast<char*>(packed) + F.off_b) : nullptr;
   PackJob job{};
   ResJob rj{};
   // fp32: embedded blocks in k-quads; bf16: 16-k steps, split into L.terms groups with emb_split
@@ -185,6 +219,7 @@ extern "C" int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void
     const bool has_emb = (L.emb_mask >> l) & 1;
     const float* W = l < d->D ? d->trunk_w[l] : d->final_w;
     if (!W) return fail(MF_E_INVALID, "mf_nerf_pack: missing weight pointer for layer %d", l);
+    if (fold && l == d->D) continue;
     const int hid0 = has_emb ? d->in_channels_xyz : 0, n_in = hid0 + (l > 0 ? L.W : 0);
     job.add(L.NP, trunk_groups(L, l),
             PackBlock{W, n_in, 1, kEmbNerfXyz, has_emb ? L.emb_steps / equad : 0, esplit, d->in_channels_xyz},
@@ -198,9 +233,11 @@ extern "C" int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void
     if (!W) return fail(MF_E_INVALID, "mf_nerf_pack: missing extra_encoding weight");
     const int kind = d->extra_feat_type == MF_EXTRA_DIR ? kEmbDir : (d->extra_feat_type == MF_EXTRA_IND ? kEmbInd : kEmbNone);
     job.add(L.NP / 2, extra_groups(L),
-            PackBlock{W, L.W + ext, 1, kPackHidden, hidden_batches(L), ((L.hsplit_mask >> L.n_trunk) & 1) ? L.terms : 1, L.W},
+            fold ? PackBlock{fold_w, L.W, 1, kPackHidden, hidden_batches(L), 1, L.W}
+                 : PackBlock{W, L.W + ext, 1, kPackHidden, hidden_batches(L), ((L.hsplit_mask >> L.n_trunk) & 1) ? L.terms : 1, L.W},
             PackBlock{W + L.W, L.W + ext, 1, kind, L.extra_steps / equad, esplit, ext});
-    rj.c[rj.n++] = ResCopy{d->extra_b, L.off_bias_extra, L.W / 2};
+    if (fold && (!d->extra_b || !d->final_b)) return fail(MF_E_INVALID, "mf_nerf_pack: missing bias pointer of the folded layers");
+    rj.c[rj.n++] = ResCopy{fold ? fold_b : d->extra_b, L.off_bias_extra, L.W / 2};
   }
   if (L.head_tiles) {
     if (!d->rgb_w) return fail(MF_E_INVALID, "mf_nerf_pack: missing rgb weight");
@@ -217,8 +254,29 @@ extern "C" int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void
   job.panels = reinterpret_cast<float*>(static_cast<char*>(packed) + L.res_bytes);
   rj.res = static_cast<float*>(packed);
   rj.total = (int)(L.res_bytes / 4);
-  if (job.total_groups * kGroupBytes != L.panel_bytes) return fail(MF_E_INVALID, "mf_nerf_pack: layout mismatch");
+  if (job.total_groups * kGroupBytes != panel_bytes) return fail(MF_E_INVALID, "mf_nerf_pack: layout mismatch");
+  if (fold) {
+    const int ext = d->extra_feat_type == MF_EXTRA_NONE ? 0 : d->extra_feat_dim;
+    const FoldJob fj{d->extra_w, d->final_w, d->extra_b, d->final_b, L.W, L.W + ext, fold_w, fold_b};
+    hipLaunchKernelGGL(fold_final_kernel, dim3((L.W / 2) * L.W / 256), dim3(256), 0, static_cast<hipStream_t>(stream), fj);
+    if (int e = check_launch("mf_nerf_pack_fold")) return e;
+  }
   return launch_pack(job, rj, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mf_nerf_pack_p(const mf_nerf_desc* d, int32_t precision, void* packed, void* stream) {
+  return nerf_pack(d, precision, packed, stream, false);
+}
+
+extern "C" int64_t mf_nerf_fold_packed_bytes(const mf_nerf_desc* d) {
+  NetLayout L;
+  FoldLayout F;
+  if (!d || !nerf_fold_layout(*d, L, F)) { fail(MF_E_UNSUPPORTED, "mf_nerf_fold_packed_bytes: unsupported NeRF configuration (fp32, W = 256)"); return 0; }
+  return L.res_bytes + F.panel_bytes + F.scratch_bytes;
+}
+
+extern "C" int32_t mf_nerf_pack_fold(const mf_nerf_desc* d, void* packed, void* stream) {
+  return nerf_pack(d, MF_PREC_F32, packed, stream, true);
 }
 
 extern "C" int32_t mf_nof_pack_p(const mf_nof_desc* d, int32_t precision, void* packed, void* stream) {

@@ -43,6 +43,7 @@ class NeRF(nn.Module):
         self._packed_x3 = PackedWeights()
         self._packed_bwd3 = PackedWeights()
         self._packed_bwd = PackedWeights()
+        self._packed_fold = PackedWeights()
 
     # ---- HIP plumbing -----------------------------------------------------
     def _build_desc(self):
@@ -83,8 +84,15 @@ class NeRF(nn.Module):
 
     def invalidate_packed(self):
         """Drop the packed-weight caches (needed only after in-place edits through ``param.data``)."""
-        for c in (self._packed, self._packed_bf16, self._packed_x3, self._packed_bwd, self._packed_bwd3):
+        for c in (self._packed, self._packed_bf16, self._packed_x3, self._packed_bwd, self._packed_bwd3, self._packed_fold):
             c.invalidate()
+
+    def packed_fold(self):
+        """(descriptor, folded fp32 fragment stream) for inference render passes (mf_render_pass with MF_F_FOLDED_FINAL):
+        xyz_encoding_final pre-multiplied into extra_encoding, once per weight version; fp32, W = 256."""
+        lib = L.lib()
+        return self._packed_fold.get(self, self._build_desc, lambda d, _p: lib.mf_nerf_fold_packed_bytes(d),
+                                     lambda d, _p, buf, st: lib.mf_nerf_pack_fold(d, buf, st), "NeRF (folded final layer)", "fold")
 
     def packed_bwd(self):
         """(descriptor, transposed fragment stream) for mf_nerf_backward; fp32 only."""

@@ -12,6 +12,7 @@ here with torch, in the reference's order, and handed to the kernels, which stay
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -33,6 +34,13 @@ PRECISION = "f32"
 # "f32" = the reference's; "bf16x3" = the three-product kernels writing the same activation dump (forward
 # values and dumped activations to ~1e-5; the dX chain on them stays fp32, the weight gradients follow set_wgrad_precision).
 TRAIN_FORWARD_PRECISION = "f32"
+
+
+# fp32 inference passes (no gradients recorded, no dump) read the NeRF's folded stream (NeRF.packed_fold, MF_F_FOLDED_FINAL):
+# xyz_encoding_final, which has no activation, pre-multiplied into extra_encoding once per weight version -- a ninth of the
+# pass's matrix work.  sigma, depth, opacity and the sample planes are bit-identical to the unfolded pass, rgb moves by the
+# rounding of the folded weights (~2e-7 max-rel).  False (environment: MF_FOLD_FINAL=0): every pass reads NeRF.packed().
+FOLD_FINAL = os.environ.get("MF_FOLD_FINAL", "1") != "0"
 
 
 def set_train_forward_precision(p: str):
@@ -127,10 +135,14 @@ def _render_pass(rays, background, z_vals, z_steps, use_disp, noise, activation,
         flags |= L.MF_F_CHAIN_LOCAL
     if chain_global:
         flags |= L.MF_F_CHAIN_GLOBAL
-    a.flags = flags
     prec = L.PRECISIONS[precision or PRECISION]
     a.precision = prec
-    desc, buf = nerf.packed(prec)
+    if FOLD_FINAL and prec == L.MF_PREC_F32 and not dump and nerf.W == 256:
+        flags |= L.MF_F_FOLDED_FINAL             # (sigma_only passes too: the trunk panels are the same bytes -- one stream per model)
+        desc, buf = nerf.packed_fold()
+    else:
+        desc, buf = nerf.packed(prec)
+    a.flags = flags
     a.nerf, a.nerf_packed = C.pointer(desc), buf.data_ptr()
     a.emb_xyz = _emb_desc(nerf_embs[0])
     if nerf.extra_feat_type == "ind":
