@@ -46,7 +46,8 @@ extern "C" {
  *     _scratch_bytes); mf_depth_range, mf_depth_colormap, mf_frame_sheet; mf_points_radiance, mf_mc_normals;
  *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch; mf_point_correspond, mf_point_loss_partials
  *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward; mf_nerf_fold_packed_bytes / mf_nerf_pack_fold
- *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding) */
+ *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding); mf_occ_build
+ *     (+ mf_occ_build_scratch_bytes), mf_ray_clip */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -794,6 +795,43 @@ int32_t mf_point_loss_partials(const mf_point_loss_args* a /* host */, double* o
  * Each output may be NULL.  One launch. */
 int32_t mf_point_loss_partials_backward(const mf_point_loss_args* a /* host */, const double* out6, const float* seeds3,
                                         float* g_pred_bw, float* g_pred_fw, float* g_sigma0, float* g_sigma1, void* stream);
+
+/* ---- occupancy grid: cull and clip test-time rays before the render pass.  The reference renders every ray of the projected
+ * AABB's hull (MoCoFlowTrainer.render, trainer_moco_flow.py:226-268) from the nearest to the farthest AABB corner
+ * (Camera.make_rays, utils/camera.py:134-148; the coarse z_vals of models/rendering.py:239-249 span that whole interval). ----
+ *
+ * mf_occ_build (serves trainer_moco_flow.py:226-268, utils/camera.py:134-148, rendering.py:239-249): sigma (nx, ny, nz) fp32,
+ * z fastest, raw densities of the lattice as mf_points_sigma returns them -> a grid of (nx-1, ny-1, nz-1) cells, one bit per
+ * cell, packed along z: row (i, j) holds ceil((nz-1) / 32) uint32 words, cell k is bit k % 32 of word k / 32, the unused bits
+ * of a row's last word are 0.  Cell (i, j, k) is set iff some lattice point of [i-r, i+1+r] x [j-r, j+1+r] x [k-r, k+1+r]
+ * (clipped to the lattice, r = dilate in {0, 1, 2}) has act(sigma) > tau -- strictly; a NaN counts as set.  act = MF_ACT_RELU
+ * (sigma < 0 ? 0 : sigma) or MF_ACT_SOFTPLUS (sigma > 20 ? sigma : log1pf(expf(sigma))), as the render pass and
+ * mf_point_loss_partials evaluate them.  count_out (device int64[1], optional): the number of set cells, through the fixed-order
+ * reduction (scratch: mf_occ_build_scratch_bytes bytes, needed only with count_out).  Every word is written by one lane with a
+ * plain store; no atomics; bit-identical from run to run.  Each side >= 2 and fewer than 2^31 cells, else MF_E_INVALID. */
+int64_t mf_occ_build_scratch_bytes(int64_t nx, int64_t ny, int64_t nz);
+int32_t mf_occ_build(const float* sigma, int64_t nx, int64_t ny, int64_t nz, int32_t activation, float tau, int32_t dilate,
+                     uint32_t* bits_out, int64_t* count_out, void* scratch, void* stream);
+
+/* mf_ray_clip (serves trainer_moco_flow.py:226-268, utils/camera.py:134-148, rendering.py:239-249): rays (n_rays, >= 8) fp32 with
+ * a row stride in floats ([o, d, near, far, ...]: the 9- and 10-column tables both work) marched through the bit grid of
+ * (gx, gy, gz) cells over the box lo .. hi (host float[3] each; inv_cell: host float[3], cells per world unit, passed so that the
+ * kernel and a restatement use the same constants) in steps of dt world units -> t_first, t_last (n_rays) fp32, hit (n_rays)
+ * uint8.  Per ray, every fp32 operation rounded once (no fused multiply-add):
+ *   1. o, d, near or far NaN / inf: hit = 1, t_first = near, t_last = far (nothing is hidden: the ray renders NaN as before)
+ *   2. tmin = near, tmax = far; per axis with d_a != 0: t1 = (lo_a - o_a) / d_a, t2 = (hi_a - o_a) / d_a, tmin = max(tmin,
+ *      min(t1, t2)), tmax = min(tmax, max(t1, t2)); with d_a == 0 the ray misses if o_a < lo_a or o_a > hi_a; tmin > tmax misses
+ *   3. t_k = tmin + float(k) * dt for k = 0, 1, .. while t_k <= tmax: p = o + d * t_k, cell c_a = clamp(int(floor((p_a - lo_a) *
+ *      inv_cell_a)), 0, g_a - 1), the cell's bit is tested
+ *   4. kf / kl the first / last k with a set bit: hit = 1, t_first = max(near, t_kf - dt), t_last = min(far, t_kl + dt)
+ *   5. otherwise hit = 0, t_first = near, t_last = far
+ * The march takes at most n = floor(|hi - lo| / dt) + 2 steps (float64, on the host), which covers every ray with |d| >= 1; n >
+ * 65536, dt <= 0 or a box with lo_a >= hi_a is MF_E_INVALID.  A ray still inside [tmin, tmax] after n steps (|d| < 1) is kept
+ * whole from there: hit = 1, t_last = far, t_first from step 4 if a bit was set, else near.  One lane per ray; the grid is read
+ * through the vector caches.  n_rays = 0 launches nothing. */
+int32_t mf_ray_clip(const float* rays, int64_t ray_stride, int64_t n_rays, const uint32_t* bits, int32_t gx, int32_t gy,
+                    int32_t gz, const float* lo /* host */, const float* hi /* host */, const float* inv_cell /* host */, float dt,
+                    float* t_first, float* t_last, uint8_t* hit, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@ Drop-in surface (same names / signatures as the reference's ``models`` package):
 and ``moco_flow_amd.metrics`` for the reference's ``models.metrics`` (mse, psnr, ssim; plus image_metrics),
 ``moco_flow_amd.vis`` for ``utils.vis_utils.visualize_depth`` (plus decode_results, frame_sheet, write_png),
 ``moco_flow_amd.batch`` for the ray batch of a training step (FrameRays: selection, rays and pixels in one launch),
-``moco_flow_amd.supervision`` for its SMPL point supervision (correspondence, point_losses: no compaction, no host read).
+``moco_flow_amd.supervision`` for its SMPL point supervision (correspondence, point_losses: no compaction, no host read),
+``moco_flow_amd.occupancy`` for a frame's occupancy grid (OccupancyGrid: culls and clips test-time rays in front of render_image).
 Every forward value comes from hand-written HIP kernels reached through the C ABI in include/mocoflow_hip.h
 (libmocoflow_hip.so); CPU tensors and a missing library raise.  The backward is HIP as well -- of render_rays passes
 (which record gradients in fp32 whatever set_precision says) and of module-level NeRF / NoF / Embedding calls; shapes it
@@ -26,6 +27,8 @@ from . import batch
 from .batch import FrameRays
 from . import supervision
 from .supervision import Correspondence, correspondence, point_correspond, point_losses
+from . import occupancy
+from .occupancy import OccupancyGrid
 from .autograd import set_dx_precision, set_wgrad_precision
 from .rendering import render_rays, resample_merge, sample_pdf, set_precision, set_train_forward_precision
 
@@ -33,4 +36,5 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "resample_merge", "set_precision", "set_wgrad_precision", "set_dx_precision", "set_train_forward_precision", "query_sigma", "MSELoss",
            "marching_cubes", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
            "vis", "visualize_depth", "decode_results", "frame_sheet", "write_png", "batch", "FrameRays",
-           "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses"]
+           "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
+           "occupancy", "OccupancyGrid"]

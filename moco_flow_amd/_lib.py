@@ -213,6 +213,10 @@ SYMBOLS = {
     "mf_point_loss_partials_scratch_bytes": (C.c_int64, [C.c_int64]),
     "mf_point_loss_partials": (C.c_int32, [C.POINTER(mf_point_loss_args), _fp, _fp, _fp, _fp]),
     "mf_point_loss_partials_backward": (C.c_int32, [C.POINTER(mf_point_loss_args), _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mf_occ_build_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_occ_build": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
+    "mf_ray_clip": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()

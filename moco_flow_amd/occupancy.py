@@ -1,0 +1,180 @@
+"""Occupancy grids: cull and clip test-time rays before the render pass (mf_occ_build, mf_ray_clip).
+
+The reference renders every ray inside the hull of the projected AABB (MoCoFlowTrainer.render, trainer_moco_flow.py:226-268)
+from the nearest to the farthest AABB corner (Camera.make_rays, utils/camera.py:134-148; rendering.py:239-249 spreads the
+coarse samples over that whole interval).  A body fills a fraction of the hull and of the interval.  An ``OccupancyGrid`` is
+one bit per cell of a lattice over the AABB, built from ONE ``query_sigma`` call at a frame's image index; ``clip_rays``
+marches rays through it, ``cull`` turns the result into a ray table, and ``image.render_image(..., occupancy=grid)`` renders
+only the rays that hit.  A grid belongs to one frame index: it serves that frame's overfit view, its novel view and every
+view of its orbit.  Opt-in: nothing changes for a caller that passes no grid."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .points import query_sigma
+
+__all__ = ["OccupancyGrid"]
+
+_ACT = {"relu": L.MF_ACT_RELU, "softplus": L.MF_ACT_SOFTPLUS}
+_TIGHTEN = ("none", "near", "both")
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+class OccupancyGrid:
+    """``bits`` uint32 (Gx, Gy, ceil(Gz / 32)) on ``device``: cell (i, j, k) is bit k % 32 of ``bits[i, j, k // 32]``, padding
+    bits zero; ``dims`` = (Gx, Gy, Gz) cells over the box ``lo`` .. ``hi`` (fp32 numpy (3,) each)."""
+
+    def __init__(self, bits, dims, lo, hi, count=None):
+        L.require_gpu(bits, "OccupancyGrid")
+        self.bits = bits
+        self.dims = tuple(int(g) for g in dims)
+        self.lo = np.asarray(lo, dtype=np.float32).reshape(3).copy()
+        self.hi = np.asarray(hi, dtype=np.float32).reshape(3).copy()
+        self.device = bits.device
+        self._count = count                       # device int64[1], written by the build
+        if tuple(bits.shape) != (self.dims[0], self.dims[1], (self.dims[2] + 31) // 32) or bits.dtype != torch.int32:
+            raise RuntimeError(f"OccupancyGrid: bits {tuple(bits.shape)} {bits.dtype} do not hold {self.dims} cells as int32 words")
+        if not (self.lo < self.hi).all():
+            raise RuntimeError(f"OccupancyGrid: empty or inverted box lo={self.lo.tolist()} hi={self.hi.tolist()}")
+        # the cell edge in float64 from the fp32 box; what the kernel multiplies by is its fp32 reciprocal
+        self.cell = (self.hi.astype(np.float64) - self.lo.astype(np.float64)) / np.asarray(self.dims, dtype=np.float64)
+        self.inv_cell = (1.0 / self.cell).astype(np.float32)
+
+    @classmethod
+    def from_sigma(cls, volume, lo, hi, sigma_threshold, activate_type="softplus", dilate=1):
+        """The grid of a raw-sigma lattice ``volume`` (Nx, Ny, Nz) on a 'cuda' device (z fastest, as ``query_sigma`` returns
+        the lattice of ``from_field``) whose corner points are ``lo`` and ``hi``: (Nx-1, Ny-1, Nz-1) cells.  Cell (i, j, k) is
+        occupied iff a lattice point of [i-r, i+1+r] x [j-r, j+1+r] x [k-r, k+1+r] (r = ``dilate`` in {0, 1, 2}, clipped to
+        the lattice) has activate(sigma) > ``sigma_threshold``, strictly; a NaN counts as occupied.  ``activate_type``:
+        "relu" | "softplus", as render_rays' nerf_activate_type.  No synchronisation."""
+        L.require_gpu(volume, "OccupancyGrid.from_sigma")
+        if volume.dim() != 3:
+            raise RuntimeError(f"OccupancyGrid.from_sigma: volume must be (Nx, Ny, Nz), got shape {tuple(volume.shape)}")
+        if activate_type not in _ACT:
+            raise RuntimeError(f"OccupancyGrid.from_sigma: activate_type {activate_type!r} (relu | softplus)")
+        nx, ny, nz = (int(n) for n in volume.shape)
+        lib = L.lib()
+        need = int(lib.mf_occ_build_scratch_bytes(nx, ny, nz))
+        if need < 0:                                 # bad shape: rejected before anything is allocated or copied
+            L.check(need, "mf_occ_build_scratch_bytes")
+        vol = volume.detach().float().contiguous()
+        dev = vol.device
+        bits = torch.empty((nx - 1, ny - 1, (nz - 1 + 31) // 32), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mf_occ_build(vol.data_ptr(), nx, ny, nz, _ACT[activate_type], float(np.float32(sigma_threshold)),
+                                     int(dilate), bits.data_ptr(), count.data_ptr(), scratch.data_ptr(),
+                                     L.current_stream(dev)), "mf_occ_build")
+        return cls(bits, (nx - 1, ny - 1, nz - 1), lo, hi, count)
+
+    @staticmethod
+    def lattice(N_grid, aabb, device):
+        """``from_field``'s query points (N, 3) and their (Nx, Ny, Nz): np.linspace(lo_a, hi_a, N_a) in float64 cast to fp32,
+        x slowest, z fastest -- NOT ``mesh.lattice``'s 'xy' order."""
+        n = (int(N_grid),) * 3 if np.isscalar(N_grid) else tuple(int(v) for v in N_grid)
+        box = np.asarray(aabb, dtype=np.float64)
+        if box.shape != (2, 3) or len(n) != 3:
+            raise RuntimeError(f"OccupancyGrid: aabb must be (2, 3) and N_grid an int or a 3-tuple, got {box.shape} and {N_grid!r}")
+        ax = [torch.from_numpy(np.linspace(box[0, a], box[1, a], n[a]).astype(np.float32)).to(device) for a in range(3)]
+        pts = torch.stack([ax[0].view(-1, 1, 1).expand(*n), ax[1].view(1, -1, 1).expand(*n), ax[2].view(1, 1, -1).expand(*n)], -1)
+        return pts.reshape(-1, 3), n
+
+    @classmethod
+    def from_field(cls, nerf, nerf_embedding_xyz, aabb, N_grid=128, sigma_threshold=1.0, activate_type="softplus", dilate=1,
+                   bw_nof=None, nof_embeddings=None, ind=None, precision=None):
+        """The grid of the networks over ``aabb`` ((2, 3): min and max corner, as ``rescale_AABB`` returns it): one
+        ``query_sigma`` call on the lattice -- with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow at
+        image index ``ind``, in ``precision`` -- then ``from_sigma``; bit-identical to those two steps by hand.
+
+        ``N_grid``: lattice points per axis, an int or (Nx, Ny, Nz).  The lattice is np.linspace(lo_a, hi_a, N_a) in float64
+        cast to fp32, laid out x slowest, z fastest.  This is NOT ``mesh.lattice``'s 'xy' order (there point (a, b, c) is
+        (x[b], y[a], z[c])).
+
+        ``sigma_threshold`` = 1.0 on the ACTIVATED density is a starting value: nobody has validated it on a trained
+        checkpoint.  Too high a threshold hides thin or faint parts of the body; check a few frames against a render
+        without the grid before relying on it."""
+        dev = next(nerf.parameters()).device
+        L.require_gpu(next(nerf.parameters()), "OccupancyGrid.from_field")
+        xyz, n = cls.lattice(N_grid, aabb, dev)
+        box = np.asarray(aabb, dtype=np.float64)
+        with torch.no_grad():
+            sigma = query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof, nof_embeddings, ind, precision=precision)
+            del xyz
+            return cls.from_sigma(sigma.view(*n), box[0], box[1], sigma_threshold, activate_type, dilate)
+
+    def step_length(self, step=0.5):
+        """dt of a march: fp32(step * the shortest cell edge), in world units."""
+        return float(np.float32(float(step) * float(self.cell.min())))
+
+    def clip_rays(self, rays, step=0.5):
+        """rays (R, >= 8) [o, d, near, far, ...] on the grid's device -> (t_first (R,), t_last (R,), hit (R,) uint8): the ray is
+        clipped to the box and to [near, far], then sampled every dt = fp32(step * min cell edge); with kf / kl the first / last
+        sample in an occupied cell, t_first = max(near, t_kf - dt), t_last = min(far, t_kl + dt), hit = 1.  No sample in an
+        occupied cell: hit = 0, (near, far) unchanged.  A ray with a NaN or inf in its first 8 columns is never hidden: hit = 1,
+        (near, far) unchanged.  Any row stride works (a view is not copied).
+
+        Guarantee: with ``dilate >= 1`` at the build, ``step <= 0.5`` and unit directions (``camera.make_rays`` gives them;
+        any length <= 1 will do), a ray that passes, inside [near, far], through a cell that was occupied before dilation is
+        never missed, and [t_first, t_last] contains every such crossing: a point of the crossing at parameter t has the sample
+        t_k <= t < t_k + dt in front of it, less than |d| dt <= half a cell edge away, hence at most one cell away along every
+        axis, and dilation has set that cell.  Outside that regime ``step`` is accepted and the guarantee is not given.  (The
+        march is bounded by the steps a unit direction needs through the box's diagonal; a shorter direction that runs out of
+        them inside the box keeps hit = 1 and its ``far``.)"""
+        L.require_gpu(rays, "OccupancyGrid.clip_rays")
+        if rays.dim() != 2 or rays.shape[1] < 8 or rays.dtype != torch.float32:
+            raise RuntimeError(f"OccupancyGrid.clip_rays: rays must be fp32 (R, >= 8), got {tuple(rays.shape)} {rays.dtype}")
+        if rays.device != self.device:
+            raise RuntimeError(f"OccupancyGrid.clip_rays: rays on {rays.device}, the grid on {self.device}")
+        r = rays.detach()
+        R = r.shape[0]
+        if R <= 1 or r.stride(1) != 1 or r.stride(0) < 8:
+            r = r.contiguous()
+        stride = r.stride(0) if R > 1 else int(r.shape[1])
+        dev = self.device
+        t_first = torch.empty(R, dtype=torch.float32, device=dev)
+        t_last = torch.empty(R, dtype=torch.float32, device=dev)
+        hit = torch.empty(R, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().mf_ray_clip(r.data_ptr() if R else None, stride, R, self.bits.data_ptr(), *self.dims, _f3(self.lo),
+                                        _f3(self.hi), _f3(self.inv_cell), self.step_length(step), L.ptr(t_first) if R else None,
+                                        L.ptr(t_last) if R else None, L.ptr(hit) if R else None, L.current_stream(dev)),
+                    "mf_ray_clip")
+        return t_first, t_last, hit
+
+    def cull(self, rays, tighten="none", step=0.5):
+        """(rays_out, hit): ``rays_out`` a copy of ``rays`` with column 6 replaced by t_first (``tighten`` "near" or "both")
+        and column 7 by t_last ("both"), ``hit`` (R,) uint8 as ``clip_rays`` returns it.  Rows that miss keep their near / far.
+
+        Caveat on "both": the reference's last sample of a ray carries a delta of 1e10 (models/rendering.py:159), so whatever
+        density sits at ``far`` is composited as opaque.  With the far AABB corner as ``far`` that sample lies in empty space;
+        a tightened ``far`` puts it just behind the body instead -- within one step plus one dilated cell of the last occupied
+        sample -- where a residual density shows up at full opacity.  "near" alone only moves samples out of the empty space
+        in front of the body.  Either changes where the samples fall, so the picture differs from the unclipped render in the
+        last places or more; "none" renders the kept rays exactly as before."""
+        if tighten not in _TIGHTEN:
+            raise RuntimeError(f"OccupancyGrid.cull: tighten {tighten!r} (none | near | both)")
+        t_first, t_last, hit = self.clip_rays(rays, step)
+        out = rays.detach().clone()
+        if tighten in ("near", "both"):
+            out[:, 6] = t_first
+        if tighten == "both":
+            out[:, 7] = t_last
+        return out, hit
+
+    def to_dense(self):
+        """bool (Gx, Gy, Gz) on the grid's device."""
+        shifts = torch.arange(32, device=self.device, dtype=torch.int32)
+        b = (self.bits.unsqueeze(-1) >> shifts) & 1
+        return b.reshape(self.dims[0], self.dims[1], -1)[:, :, :self.dims[2]].bool()
+
+    def occupied_fraction(self):
+        """Occupied cells / cells, a python float: the one call that synchronises (it reads the build's count)."""
+        if self._count is None:
+            self._count = self.to_dense().sum().reshape(1)
+        return int(self._count.item()) / float(self.dims[0] * self.dims[1] * self.dims[2])
