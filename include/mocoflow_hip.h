@@ -47,7 +47,8 @@ extern "C" {
  *     mf_mask_compact (+ mf_mask_compact_scratch_bytes), mf_ray_batch; mf_point_correspond, mf_point_loss_partials
  *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward; mf_nerf_fold_packed_bytes / mf_nerf_pack_fold
  *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding); mf_occ_build
- *     (+ mf_occ_build_scratch_bytes), mf_ray_clip */
+ *     (+ mf_occ_build_scratch_bytes), mf_ray_clip; mf_mesh_label, mf_mesh_table_count / mf_mesh_table_emit, mf_mesh_filter_plan /
+ *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -610,6 +611,62 @@ int32_t mf_mc_emit(const float* vol, int64_t n0, int64_t n1, int64_t n2, float i
  * fp32 throughout.  Shape rules of mf_mc_count; V == 0: MF_OK, nothing launched. */
 int32_t mf_mc_normals(const float* vol, int64_t n0, int64_t n1, int64_t n2, int32_t clamp_zero, const float* verts, int64_t V,
                       float* normals, void* stream);
+
+/* ---- mesh clean-up: connected components of an indexed triangle mesh, the table of the components, and the compaction of
+ * the mesh to the components a caller keeps -- what a user of visualize_mesh's output (trainer_moco_flow.py:485-548) does
+ * next, a fixed-threshold sigma isosurface being a body plus detached specks -- without the mesh leaving the device
+ * (tests/mesh_components_oracle.py restates the contract in numpy).
+ * tris: (T, 3) int64 over V vertices.  Two vertices are adjacent if some triangle names both; a triangle may name an index
+ * twice or three times and may be repeated.  The label of a vertex is the smallest vertex index of its connected
+ * component (a vertex in no triangle is its own component); a triangle belongs to the component of its column-0 vertex.
+ * Every output is a pure function of the input: bit-identical from run to run, whatever the launch geometry and the order
+ * in which atomics land.  32-bit internal indexing: V or T outside [0, 2^31) is MF_E_INVALID.  A triangle with an index
+ * outside [0, V) is never dereferenced: it joins nothing, belongs to nothing and is counted into the entry's `bad`
+ * counter -- the caller reads that counter with the counts it reads anyway and rejects the mesh.  Scratch is the caller's
+ * (the *_scratch_bytes queries; MF_E_INVALID on a bad shape); nothing is allocated, everything runs on `stream`, nothing
+ * synchronises.  V = 0 or T = 0 launches nothing that reads the missing array (which may be NULL).
+ *
+ * mf_mesh_label: labels (V) int64; bad (device int64[1]) = triangles with an index out of range.  Lock-free union-find on
+ * 32-bit parents in scratch (4 V bytes): parent[v] = v; one grid-stride pass over the triangles unites (t0, t1) and (t1, t2)
+ * -- find both roots (path splitting), hook the larger under the smaller with one compare-and-swap, and on a failed swap go
+ * on from the value it returned (another thread has hooked that root, under a smaller index); one pass writes the roots.
+ * A parent is never larger than its vertex, so the final root is the component's minimum whoever won which swap; no wave
+ * ever waits for another (no flags, no grid barrier, no cooperative launch).  Three launches. */
+int64_t mf_mesh_label_scratch_bytes(int64_t V, int64_t T);
+int32_t mf_mesh_label(const int64_t* tris, int64_t T, int64_t V, int64_t* labels, int64_t* bad, void* scratch, void* stream);
+/* The component table, in two steps around the caller's read of the component count.
+ * mf_mesh_table_count: per label the number of triangles and of vertices (integer atomic adds, first summed over the lanes
+ * of a wave that hit the same label and, for the label most of a wave shares, over the wave's whole share of the mesh: one
+ * big component does not send every add to one address) and the root flags labels[v] == v, all kept in scratch; counts
+ * (device int64[2]) =
+ * [C = number of components, bad = triangles whose column-0 index, and vertices whose label, is outside [0, V)].
+ * mf_mesh_table_emit, with the same V and scratch and the C read from counts: ids (C) = the labels in ascending order
+ * (mf_mask_compact on the root flags), tri_counts (C), vert_counts (C), all int64.  C == 0: nothing launched. */
+int64_t mf_mesh_table_scratch_bytes(int64_t V, int64_t T);
+int32_t mf_mesh_table_count(const int64_t* tris, int64_t T, int64_t V, const int64_t* labels, int64_t* counts, void* scratch,
+                            void* stream);
+int32_t mf_mesh_table_emit(int64_t V, int64_t C, void* scratch, int64_t* ids, int64_t* tri_counts, int64_t* vert_counts,
+                           void* stream);
+/* The filter, in two steps around the caller's read of the kept counts.
+ * mf_mesh_filter_plan: ids (C) and keep (C, uint8) are the table's labels and the caller's decision per component.  Flags
+ * per vertex (its label's component is kept) and per triangle (its column-0 vertex is kept) go to scratch; counts (device
+ * int64[3]) = [kept vertices, kept triangles, bad = triangles with an index, vertices with a label and ids entries
+ * outside [0, V)]; a bad triangle is dropped.
+ * mf_mesh_filter_emit, with the same tris / T / V / scratch and the two counts read: vert_inds (Vk) and tri_inds (Tk) = the
+ * kept vertices and triangles by their old indices, ascending (stable: mf_mask_compact on the flags); tris_out (Tk, 3) = the
+ * kept triangles with their indices rewritten through the old -> new vertex map (-1 for an index out of range, which the
+ * bad counter has reported).  A pointer whose count is 0 may be NULL. */
+int64_t mf_mesh_filter_scratch_bytes(int64_t V, int64_t T);
+int32_t mf_mesh_filter_plan(const int64_t* tris, int64_t T, int64_t V, const int64_t* labels, const int64_t* ids,
+                            const uint8_t* keep, int64_t C, int64_t* counts, void* scratch, void* stream);
+int32_t mf_mesh_filter_emit(const int64_t* tris, int64_t T, int64_t V, int64_t Vk, int64_t Tk, void* scratch,
+                            int64_t* vert_inds, int64_t* tri_inds, int64_t* tris_out, void* stream);
+/* dst row k = src row inds[k] for k < n: rows of row_bytes contiguous bytes, copied as they are (vertices and any
+ * per-vertex attribute of a filtered mesh stay bitwise equal); src has n_src rows, an index outside [0, n_src) gives a row
+ * of zero bytes.  4-byte words where row_bytes and both pointers allow it, bytes otherwise.  n row_bytes == 0: nothing
+ * launched. */
+int32_t mf_gather_rows(const void* src, int64_t n_src, int64_t row_bytes, const int64_t* inds, int64_t n, void* dst,
+                       void* stream);
 
 /* ---- validation metrics: models/metrics.py:4-22 (mse, psnr, ssim), called per validation image by val_step
  * (trainer_moco_flow.py:453-473).  The reference's ssim is kornia 0.6.5's kornia.metrics.ssim.ssim(img1, img2, window_size,

@@ -196,6 +196,15 @@ SYMBOLS = {
     "mf_mc_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp]),
     "mf_mc_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
     "mf_mc_normals": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp]),
+    "mf_mesh_label_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_mesh_label": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp]),
+    "mf_mesh_table_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_mesh_table_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp]),
+    "mf_mesh_table_emit": (C.c_int32, [C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
+    "mf_mesh_filter_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_mesh_filter_plan": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp]),
+    "mf_mesh_filter_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
+    "mf_gather_rows": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, _fp]),
     "mf_ssim_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mf_ssim": (C.c_int32, [_fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),

@@ -1,7 +1,9 @@
 """Mesh extraction on the device: marching cubes (mf_mc_count / mf_mc_emit) and visualize_mesh's pipeline around it
 (trainer_moco_flow.py:485-548, trainer_nerf.py:200-259) -- sigma lattice, isosurface and the reference's post-processing
 without the volume leaving the device -- and what a coloured mesh adds: vertex normals from the same volume
-(mf_mc_normals), vertex colours from the radiance field (query_radiance), a PLY writer that carries both."""
+(mf_mc_normals), vertex colours from the radiance field (query_radiance), a PLY writer that carries both; and the mesh
+clean-up that follows an isosurface at a fixed threshold: connected components (mf_mesh_label, mf_mesh_table_*) and the
+filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device."""
 import numpy as np
 import torch
 
@@ -70,6 +72,159 @@ def vertex_normals(volume, verts, clamp_zero=False):
     return normals
 
 
+def _check_tris(tris, what):
+    if tris.dim() != 2 or tris.shape[1] != 3:
+        raise RuntimeError(f"{what}: tris must be (T, 3), got shape {tuple(tris.shape)}")
+    if tris.dtype != torch.int64:
+        raise RuntimeError(f"{what}: tris must be int64, got {tris.dtype}")
+
+
+def _bytes(n, dev):
+    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+
+
+def _label(tris, V, bad):
+    """Launch the labelling of a checked, contiguous (T, 3) int64 device tensor: labels (V,); the bad-index counter goes to
+    ``bad`` (device int64 storage).  No host read."""
+    lib, dev, T = L.lib(), tris.device, tris.shape[0]
+    need = int(lib.mf_mesh_label_scratch_bytes(V, T))
+    if need < 0:                                     # V or T beyond 32-bit indexing: rejected before anything is allocated
+        L.check(need, "mf_mesh_label_scratch_bytes")
+    labels = torch.empty(V, dtype=torch.int64, device=dev)
+    scratch = _bytes(need, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mf_mesh_label(L.ptr(tris) if T else None, T, V, L.ptr(labels) if V else None, bad.data_ptr(),
+                                  scratch.data_ptr(), L.current_stream(dev)), "mf_mesh_label")
+    return labels
+
+
+def _table(tris, V, labels, counts, what):
+    """The component table of labelled triangles: (ids, tri_counts, vert_counts).  ``counts``: device int64[3] whose entry
+    0 a labelling on the same stream has filled; one device -> host read ([bad, C, bad])."""
+    lib, dev, T = L.lib(), tris.device, tris.shape[0]
+    scratch = _bytes(lib.mf_mesh_table_scratch_bytes(V, T), dev)
+    with torch.cuda.device(dev):
+        stream = L.current_stream(dev)
+        L.check(lib.mf_mesh_table_count(L.ptr(tris) if T else None, T, V, L.ptr(labels) if V else None, counts.data_ptr() + 8,
+                                        scratch.data_ptr(), stream), "mf_mesh_table_count")
+        bad, C, bad2 = (int(x) for x in counts.tolist())
+        if bad or bad2:
+            raise RuntimeError(f"{what}: {max(bad, bad2)} triangles name a vertex outside [0, {V})")
+        ids, tri_counts, vert_counts = (torch.empty(C, dtype=torch.int64, device=dev) for _ in range(3))
+        L.check(lib.mf_mesh_table_emit(V, C, scratch.data_ptr(), L.ptr(ids) if C else None, L.ptr(tri_counts) if C else None,
+                                       L.ptr(vert_counts) if C else None, stream), "mf_mesh_table_emit")
+    return ids, tri_counts, vert_counts
+
+
+def _components(tris, V, what):
+    """Labels and table of a checked, contiguous (T, 3) int64 device tensor; one device -> host read."""
+    counts = torch.empty(3, dtype=torch.int64, device=tris.device)      # [bad of the labelling, C, bad of the table]
+    labels = _label(tris, V, counts)
+    return (labels,) + _table(tris, V, labels, counts, what)
+
+
+def mesh_components(tris, n_verts):
+    """Connected components of an indexed mesh: tris (T, 3) int64 on a 'cuda' device over ``n_verts`` vertices ->
+    (labels (V,), ids (C,), tri_counts (C,), vert_counts (C,)), all int64 on that device.
+
+    Two vertices are adjacent if some triangle names both (a triangle may repeat an index, a mesh may repeat a triangle);
+    labels[v] is the smallest vertex index of v's component, a vertex in no triangle being a component of its own with no
+    triangles; ids are the distinct labels, ascending; a triangle counts for the component of its column-0 vertex.  Every
+    output is a pure function of the input, bit-identical from run to run (include/mocoflow_hip.h mf_mesh_label).  V and
+    T below 2^31.  An index outside [0, n_verts) is never dereferenced and raises RuntimeError.  One device -> host read
+    (the number of components with the bad-index counters)."""
+    _check_tris(tris, "mesh_components")
+    V = int(n_verts)
+    if V < 0:
+        raise RuntimeError(f"mesh_components: n_verts={V}")
+    L.require_gpu(tris, "mesh_components")
+    return _components(tris.detach().contiguous(), V, "mesh_components")
+
+
+def gather_rows(src, inds):
+    """src[inds] along dim 0 for a contiguous device tensor of any dtype, as a byte copy (mf_gather_rows)."""
+    lib, dev = L.lib(), src.device
+    n = inds.shape[0]
+    out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
+    row_bytes = int(np.prod(src.shape[1:], dtype=np.int64)) * src.element_size()
+    if n and row_bytes:
+        with torch.cuda.device(dev):
+            L.check(lib.mf_gather_rows(src.data_ptr(), src.shape[0], row_bytes, inds.data_ptr(), n, out.data_ptr(),
+                                       L.current_stream(dev)), "mf_gather_rows")
+    return out
+
+
+def filter_components(verts, tris, keep_largest=None, min_triangles=None, attrs=()):
+    """Keep whole connected components of a mesh: verts (V, ...) and tris (T, 3) int64 on a 'cuda' device ->
+    (verts, tris, *attrs) of the kept components, triangle indices rewritten to the kept vertices.
+
+    Components as mesh_components defines them, ranked by triangle count (descending), then label (ascending):
+    ``keep_largest=k`` keeps the first k in that order, ``min_triangles=m`` those with at least m triangles, both given
+    their intersection; neither is a ValueError, as is k < 1.  Every vertex of a dropped component goes, a vertex in no
+    triangle included (it is a component without triangles).  Kept vertices and triangles stay in their original order;
+    vertex rows and the rows of every tensor in ``attrs`` (each (V, ...), any dtype) are copied byte for byte.  Nothing
+    kept: (0, ...) tensors.  Two device -> host reads: the labelling's (the number of components) and one for the kept
+    counts with the bad-index counter."""
+    if keep_largest is None and min_triangles is None:
+        raise ValueError("filter_components: give keep_largest, min_triangles or both")
+    if keep_largest is not None and int(keep_largest) < 1:
+        raise ValueError(f"filter_components: keep_largest={keep_largest} (at least 1)")
+    _check_tris(tris, "filter_components")
+    if verts.dim() < 1:
+        raise RuntimeError("filter_components: verts must be (V, ...)")
+    V, T = verts.shape[0], tris.shape[0]
+    attrs = tuple(attrs)
+    for i, a in enumerate(attrs):
+        if a.dim() < 1 or a.shape[0] != V:
+            raise RuntimeError(f"filter_components: attrs[{i}] has shape {tuple(a.shape)} for {V} vertices")
+    for t in (tris, verts) + attrs:
+        L.require_gpu(t, "filter_components")
+    tris = tris.detach().contiguous()
+    labels, ids, tri_counts, _ = _components(tris, V, "filter_components")
+    keep = _keep(ids, tri_counts, V, T, keep_largest, min_triangles)
+    return _filter(verts, tris, labels, ids, keep, attrs)
+
+
+def _keep(ids, tri_counts, V, T, keep_largest, min_triangles):
+    """The per-component decision (C,) uint8 from the table, with torch ops on the table's device."""
+    C = ids.shape[0]
+    keep = torch.ones(C, dtype=torch.bool, device=ids.device)
+    if keep_largest is not None and int(keep_largest) < C:
+        # rank key (T - triangles) V' + label, V' = max(V, 1): distinct per component (labels are), below 2^62 -- no tie is
+        # left to the sort
+        order = torch.argsort((T - tri_counts) * max(V, 1) + ids)
+        keep = torch.zeros(C, dtype=torch.bool, device=ids.device)
+        keep[order[:int(keep_largest)]] = True
+    if min_triangles is not None:
+        keep &= tri_counts >= int(min_triangles)
+    return keep.to(torch.uint8)
+
+
+def _filter(verts, tris, labels, ids, keep, attrs=()):
+    """The mesh of the components whose ``keep`` (C,) uint8 is set; one device -> host read ([Vk, Tk, bad])."""
+    lib, dev = L.lib(), tris.device
+    V, T, C = verts.shape[0], tris.shape[0], ids.shape[0]
+    scratch = _bytes(lib.mf_mesh_filter_scratch_bytes(V, T), dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    tp = L.ptr(tris) if T else None
+    with torch.cuda.device(dev):
+        stream = L.current_stream(dev)
+        L.check(lib.mf_mesh_filter_plan(tp, T, V, L.ptr(labels) if V else None, L.ptr(ids) if C else None,
+                                        L.ptr(keep) if C else None, C, counts.data_ptr(), scratch.data_ptr(), stream),
+                "mf_mesh_filter_plan")
+        Vk, Tk, bad = (int(x) for x in counts.tolist())
+        if bad:
+            raise RuntimeError(f"filter_components: {bad} triangles name a vertex outside [0, {V})")
+        vert_inds = torch.empty(Vk, dtype=torch.int64, device=dev)
+        tri_inds = torch.empty(Tk, dtype=torch.int64, device=dev)
+        tris_out = torch.empty((Tk, 3), dtype=torch.int64, device=dev)
+        L.check(lib.mf_mesh_filter_emit(tp, T, V, Vk, Tk, scratch.data_ptr(), L.ptr(vert_inds) if Vk else None,
+                                        L.ptr(tri_inds) if Tk else None, L.ptr(tris_out) if Tk else None, stream),
+                "mf_mesh_filter_emit")
+    return (gather_rows(verts.detach().contiguous(), vert_inds), tris_out,
+            *(gather_rows(a.detach().contiguous(), vert_inds) for a in attrs))
+
+
 def lattice(N_grid, device):
     """visualize_mesh's query points (trainer_moco_flow.py:490-498): np.linspace(-1.5, 1.5, N) in float64 cast to fp32, laid
     out as np.stack(np.meshgrid(x, y, z), -1).reshape(-1, 3) ('xy' indexing: point (a, b, c) is (x[b], y[a], z[c]))."""
@@ -80,13 +235,14 @@ def lattice(N_grid, device):
 
 
 def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                 precision=None):
+                 precision=None, keep_largest=None, min_triangles=None):
     """visualize_mesh (trainer_moco_flow.py:490-538) up to the file: raw sigma of the NeRF on the N_grid^3 lattice over
     [-1.5, 1.5]^3 (query_sigma; with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow, ``ind`` =
     frame_idx * 2 / num_frames - 1), the isosurface of max(sigma, 0) at ``sigma_threshold``, then the reference's
     post-processing: vertex columns 0 and 1 swapped, triangle columns 1 and 2 swapped, vertices / N_grid * 3 - 1.5 (the
     reference divides by N_grid, not N_grid - 1).  Returns (verts (V, 3) float32, tris (T, 3) int64) on the NeRF's device;
-    ``export_obj`` writes them."""
+    ``export_obj`` writes them.  ``keep_largest`` / ``min_triangles`` (not in the reference): filter_components with these
+    on the raw isosurface, before the post-processing; both None leaves the path as it was."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_mesh")
     xyz = lattice(N_grid, dev)
@@ -94,13 +250,15 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
         sigma = query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof, nof_embeddings, ind, precision=precision)
         del xyz
         verts, tris = marching_cubes(sigma.view(N_grid, N_grid, N_grid), sigma_threshold, clamp_zero=True)
+        if keep_largest is not None or min_triangles is not None:
+            verts, tris = filter_components(verts, tris, keep_largest, min_triangles)
         verts = verts[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
     return verts, tris
 
 
 def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                         precision=None):
+                         precision=None, keep_largest=None, min_triangles=None):
     """extract_mesh with what a coloured mesh needs: (verts (V, 3), tris (T, 3), normals (V, 3), colors (V, 3)).
 
     verts / tris are extract_mesh's for the same arguments (``nerf_embeddings`` = [xyz, ind | None, dir | None] as
@@ -108,7 +266,9 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
     volume (max(sigma, 0)), in the axes of the returned vertices (columns [1, 0, 2] like them; the uniform scale leaves
     directions alone) -- they point out of the body.  colors: query_radiance(...)[:, :3] at the returned vertices in fp32,
     through the same NoF / ``ind``; a "dir" NeRF is looked at straight on, view_dirs = -normal ((0, 0, -1) where the
-    normal is zero).  An empty mesh gives four empty tensors."""
+    normal is zero).  An empty mesh gives four empty tensors.  ``keep_largest`` / ``min_triangles``: as in extract_mesh;
+    the filter runs before the radiance query, with the normals as a vertex attribute, so a dropped vertex is never
+    queried."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_colored_mesh")
     xyz = lattice(N_grid, dev)
@@ -119,6 +279,8 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
         raw, tris = marching_cubes(volume, sigma_threshold, clamp_zero=True)
         normals = vertex_normals(volume, raw, clamp_zero=True)[:, [1, 0, 2]].contiguous()
         del sigma, volume
+        if keep_largest is not None or min_triangles is not None:
+            raw, tris, normals = filter_components(raw, tris, keep_largest, min_triangles, attrs=(normals,))
         verts = raw[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
         if verts.shape[0] == 0:

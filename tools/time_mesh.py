@@ -8,7 +8,18 @@ V and T, the mesh bytes written (12 V + 24 T), and the volume bytes read (4 B x 
 any isosurface step must read) over that time, as a fraction of the 6.29 TB/s measured HBM copy rate
 (MI355X_MICROARCH.md).  marching_cubes includes its one device -> host read of the counts and the scratch / output
 allocations.  A smooth analytic field at each size shows the cost of the volume read when the mesh is small (the random
-NeRF's sigma makes ~10^8 triangles at 512^3).  Usage: time_mesh.py [N ...]  (default 256 512)"""
+NeRF's sigma makes ~10^8 triangles at 512^3).
+
+The components leg (mesh_components / filter_components: what follows an isosurface at a fixed threshold), on both fields of
+each size: the labelling (mf_mesh_label), the table (mf_mesh_table_count, its read, mf_mesh_table_emit) and the filter to the
+largest component (mf_mesh_filter_plan, its read, mf_mesh_filter_emit, the vertex gather) timed separately, then
+filter_components end to end, beside marching_cubes on the same volume and, for the NeRF, the sigma query.  Algorithmic
+bytes: 24 B per triangle read + 4 B per vertex of labels (the labelling), the compacted outputs 12 B per kept vertex + 24 B
+per kept triangle (the filter), each over its time as a fraction of the 4.69 TB/s device-to-device copy rate -- information
+only: the accesses to the parents are random and no share of a peak is claimed.  The host path these replace, in the same
+process where scipy is importable: the device -> host copy of the mesh, scipy.sparse.csgraph.connected_components, a numpy
+re-index to the largest component (once each; --no-host skips it).  Usage: time_mesh.py [--no-host] [--components-only]
+[N ...]  (default 256 512)"""
 import os
 import statistics
 import sys
@@ -22,7 +33,10 @@ import moco_flow_amd as M
 from moco_flow_amd import synth
 
 COPY_RATE = 6.29e12
-Ns = [int(a) for a in sys.argv[1:]] or [256, 512]
+D2D_COPY_RATE = 4.69e12
+HOST = "--no-host" not in sys.argv
+COMPONENTS_ONLY = "--components-only" in sys.argv
+Ns = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or [256, 512]
 dev = torch.device("cuda")
 sd = synth.nerf_state(0, regime="dense")
 sd["sigma.weight"] = sd["sigma.weight"] * np.float32(3.0)
@@ -53,13 +67,68 @@ def row(what, N, ms, out):
           f"= {gbs / COPY_RATE:.3f} of the copy rate; mesh written {out_gb:.2f} GB", flush=True)
 
 
-print("marching_cubes (clamp_zero, threshold 10) on the f32 sigma lattice")
+def host_path(verts, tris):
+    """The host round trip: copy, scipy's connected components, numpy re-index to the largest; each timed once."""
+    try:
+        from scipy import sparse
+        from scipy.sparse import csgraph
+    except ImportError:
+        print("    host path: scipy is not importable here, no comparison", flush=True)
+        return
+    t0 = time.perf_counter()
+    v, t = verts.cpu().numpy(), tris.cpu().numpy()
+    t1 = time.perf_counter()
+    V = len(v)
+    e0, e1 = np.concatenate([t[:, 0], t[:, 1]]).astype(np.int32), np.concatenate([t[:, 1], t[:, 2]]).astype(np.int32)
+    graph = sparse.coo_matrix((np.ones(len(e0), np.int8), (e0, e1)), shape=(V, V)).tocsr()
+    n, lab = csgraph.connected_components(graph, directed=False)
+    t2 = time.perf_counter()
+    del graph, e0, e1
+    big = np.bincount(lab[t[:, 0]], minlength=n).argmax()
+    vkeep = lab == big
+    remap = np.cumsum(vkeep) - 1
+    kv, kt = v[vkeep], remap[t[vkeep[t[:, 0]]]]
+    t3 = time.perf_counter()
+    print(f"    host path: device -> host copy {1e3 * (t1 - t0):10.1f} ms, scipy connected_components (graph build included) "
+          f"{1e3 * (t2 - t1):10.1f} ms, numpy re-index {1e3 * (t3 - t2):10.1f} ms: {n} components, kept V {len(kv)} T {len(kt)}",
+          flush=True)
+
+
+def components_leg(what, N, verts, tris, mc_ms, sigma_ms=None):
+    V, T = len(verts), len(tris)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    ms_label, labels = timeit(lambda: M.mesh._label(tris, V, counts))
+    ms_table, (ids, tri_counts, vert_counts) = timeit(lambda: M.mesh._table(tris, V, labels, counts, "time_mesh"))
+    keep = M.mesh._keep(ids, tri_counts, V, T, 1, None)
+    ms_filter, (kv, kt) = timeit(lambda: M.mesh._filter(verts, tris, labels, ids, keep))
+    ms_all, _ = timeit(lambda: M.filter_components(verts, tris, keep_largest=1))
+    b_label, b_out = 24 * T + 4 * V, 12 * len(kv) + 24 * len(kt)
+    frac = lambda b, ms: b / (ms * 1e-3) / D2D_COPY_RATE
+    beside = f"marching_cubes {mc_ms:.3f} ms" + (f", sigma query {sigma_ms:.1f} ms" if sigma_ms is not None else "")
+    print(f"  components, {what} {N}^3: V {V} T {T}, {len(ids)} components, largest {int(tri_counts.max()) if len(ids) else 0} "
+          f"triangles  ({beside})")
+    print(f"    labelling {ms_label:9.3f} ms  ({b_label / 1e9:.3f} GB algorithmic = {frac(b_label, ms_label):.3f} of the copy rate)")
+    print(f"    table     {ms_table:9.3f} ms  (with its read of the component count)")
+    print(f"    filter    {ms_filter:9.3f} ms  (keep_largest=1 -> V {len(kv)} T {len(kt)}; {b_out / 1e9:.3f} GB of compacted output = "
+          f"{frac(b_out, ms_filter):.3f} of the copy rate; with its read of the kept counts)")
+    print(f"    filter_components end to end {ms_all:9.3f} ms", flush=True)
+    del labels, kv, kt
+    if HOST:
+        host_path(verts, tris)
+
+
+print("marching_cubes (clamp_zero, threshold 10) on the f32 sigma lattice; the components leg on each mesh")
 for N in Ns:
     with torch.no_grad():
-        vol = M.query_sigma(M.mesh.lattice(N, dev), nerf, emb).view(N, N, N)
+        xyz = M.mesh.lattice(N, dev)
+        sigma_ms, sig = timeit(lambda: M.query_sigma(xyz, nerf, emb), warm=1, n=3)
+        vol = sig.view(N, N, N)
+        del xyz, sig
     ms, out = timeit(lambda: M.marching_cubes(vol, 10.0, clamp_zero=True))
     row("marching_cubes", N, ms, out)
-    del vol, out
+    del vol
+    components_leg("test NeRF sigma at 10", N, out[0], out[1], ms, sigma_ms)
+    del out
     # a smooth field with a far smaller surface than the random NeRF's: what reading the volume itself costs
     ax = torch.linspace(0, 1, N, device=dev)
     x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
@@ -67,8 +136,12 @@ for N in Ns:
     del x, y, z
     ms, out = timeit(lambda: M.marching_cubes(vol, 0.3))
     row("marching_cubes, smooth field", N, ms, out)
-    del vol, out
+    del vol
+    components_leg("smooth field", N, out[0], out[1], ms)
+    del out
     torch.cuda.empty_cache()
+if COMPONENTS_ONLY:
+    sys.exit(0)
 print("extract_mesh end to end (lattice + query_sigma + marching_cubes + post-processing)")
 for N in Ns:
     for prec in ("f32", "bf16", "bf16x3"):
