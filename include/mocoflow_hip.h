@@ -48,7 +48,8 @@ extern "C" {
  *     (+ mf_point_loss_partials_scratch_bytes), mf_point_loss_partials_backward; mf_nerf_fold_packed_bytes / mf_nerf_pack_fold
  *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding); mf_occ_build
  *     (+ mf_occ_build_scratch_bytes), mf_ray_clip; mf_mesh_label, mf_mesh_table_count / mf_mesh_table_emit, mf_mesh_filter_plan /
- *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows */
+ *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows; mf_project_vertices, mf_rasterize (+ mf_raster_scratch_bytes),
+ *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -889,6 +890,70 @@ int32_t mf_occ_build(const float* sigma, int64_t nx, int64_t ny, int64_t nz, int
 int32_t mf_ray_clip(const float* rays, int64_t ray_stride, int64_t n_rays, const uint32_t* bits, int32_t gx, int32_t gy,
                     int32_t gz, const float* lo /* host */, const float* hi /* host */, const float* inv_cell /* host */, float dt,
                     float* t_first, float* t_last, uint8_t* hit, void* stream);
+
+/* ---- triangle rasterizer (moco_flow_amd/csrc/mf_raster.hip, which writes out the fill rule and every operation order): the
+ * pictures the reference draws with pyrender -- the stage-1 views of the posed SMPL mesh and the SMPL overlay,
+ * scripts/data_utils.py:23-86, 273-336 -- through the camera of mf_make_rays (utils/camera.py:29-81): with p_cam = R^T (p - t)
+ * and z = -p_cam.z, column x = cx + f p_cam.x / z and row y = cy - f p_cam.y / z, one focal length for both axes.  The sample
+ * of pixel (row j, column i) sits at (x, y) = (i + pixel_offset, j + pixel_offset); pixel_offset = 0 is where mf_make_rays shoots
+ * that pixel's ray, 0.5 is OpenGL's sample position, anything else is MF_E_INVALID.
+ * PYRENDER NOT RESTATED: its metallic-roughness BRDF and the three point lights of data_utils.py:36-46 are third-party
+ * arithmetic this project does not restate and is UNPINNED against (as kornia and cv2 are); colours are the interpolated vertex
+ * colours, optionally times a headlight term.
+ * No entry allocates or synchronises; V, T in [0, 2^31), H, W >= 1 and H W < 2^31, else MF_E_INVALID. */
+
+/* mf_project_vertices (data_utils.py:23-86, 273-336; camera.py:29-81): verts (V, 3) fp32 world, c2w_host the 3x4 row-major
+ * camera-to-world matrix (host) -> screen (V, 2) int32 = (rintf(256 x), rintf(256 y)), saturated at +-2^30, and inv_z (V) = 1 / z.
+ * A vertex with z <= znear (znear > 0), or with a NaN position, gets screen = (INT32_MIN, INT32_MIN) and inv_z = 0.  xy (V, 2)
+ * fp32, optional: the unsnapped (x, y) (NaN for a flagged vertex).  fp32, every operation rounded once. */
+int32_t mf_project_vertices(const float* verts, int64_t V, const float* c2w_host, float focal, float cx, float cy, float znear,
+                            int32_t* screen, float* inv_z, float* xy, void* stream);
+/* Bytes of the scratch mf_rasterize fills and mf_raster_resolve / mf_raster_shade read: the (H W) plane of 64-bit keys and the
+ * 8-byte counter of dropped triangles (data_utils.py:23-86, 273-336; camera.py:29-81). */
+int64_t mf_raster_scratch_bytes(int64_t H, int64_t W);
+/* mf_rasterize (data_utils.py:23-86, 273-336; camera.py:29-81): clears the scratch, then one wave per 64 triangles of tris (T, 3)
+ * int64 writes min((bits(z) << 32) | triangle index) over the triangles covering each sample.  Coverage is decided in int64 on
+ * the snapped coordinates with a top-left fill rule; winding does not matter; zero-area triangles cover nothing; a triangle with
+ * a flagged vertex, a vertex beyond +-2^15 pixels or a vertex index outside [0, V) is dropped whole and counted (no clipping).
+ * Bit-identical from run to run and under any permutation of tris (up to the index itself); an exact depth tie goes to the
+ * lower index.  T = 0 only clears. */
+int32_t mf_rasterize(const int32_t* screen, const float* inv_z, int64_t V, const int64_t* tris, int64_t T, int64_t H, int64_t W,
+                     float pixel_offset, void* scratch, void* stream);
+/* mf_raster_resolve (data_utils.py:23-86, 273-336; camera.py:29-81): the scratch of mf_rasterize, with the arguments it was
+ * filled from -> face (H, W) int32 (-1 = none), depth (H, W) fp32 camera-axis z (+inf where none), bary (H, W, 3) fp32
+ * perspective-correct (zeros where none), dropped_out (device int64[1]).  Any output may be NULL, not all. */
+int32_t mf_raster_resolve(const void* scratch, const int32_t* screen, const float* inv_z, int64_t V, const int64_t* tris, int64_t T,
+                          int64_t H, int64_t W, float pixel_offset, int32_t* face, float* depth, float* bary, int64_t* dropped_out,
+                          void* stream);
+/* mf_raster_interpolate (data_utils.py:23-86, 273-336; camera.py:29-81): out (n_pix, C) = (bary_0 a_0 + bary_1 a_1) + bary_2 a_2
+ * of the rows a_k = attrs[tris[face][k]] of attrs (V, C) fp32, 1 <= C <= 16; zeros where face is outside [0, T) or names a
+ * vertex outside [0, V) (nothing is dereferenced). */
+int32_t mf_raster_interpolate(const float* attrs, int64_t V, int32_t C, const int64_t* tris, int64_t T, const int32_t* face,
+                              const float* bary, int64_t n_pix, float* out, void* stream);
+/* mf_raster_shade (data_utils.py:23-86, 273-336; camera.py:29-81): ONE launch from the scratch of mf_rasterize to a frame.
+ *   rgba  (H, W, 4) uint8, 4-byte aligned: covered: alpha 255 and (uint8) clamp(c 255 + 0.5, 0, 255) in fp32, truncated (the
+ *         rounding of mf_frame_sheet), of c = (bary_0 c_0 + bary_1 c_1) + bary_2 c_2 over colors (V, 3) fp32 (NULL: 1), times
+ *         ambient + (1 - ambient) |n . v| with MF_RASTER_SHADE_HEADLIGHT (n: unit normal of the triangle's world vertices verts
+ *         (V, 3), v: unit vector from the surface point to the camera); elsewhere alpha 0 and the background (none: 0, one
+ *         colour by value, or the (H, W, 3) uint8 image)
+ *   mask  (H W) bytes 1 / 0;  depth (H, W) fp32 z, +inf where none;  face (H, W) int32, -1 where none
+ *   ray_t (H, W) fp32 = z |((x - cx) / f, -(y - cy) / f, -1)| at the sample position: with pixel_offset 0 the point of that
+ *         pixel's mf_make_rays ray is o + ray_t d; +inf where none
+ * c2w travels by value (3x4 row-major).  Any output may be NULL, not all. */
+enum { MF_RASTER_SHADE_NONE = 0, MF_RASTER_SHADE_HEADLIGHT = 1 };
+enum { MF_RASTER_BG_NONE = 0, MF_RASTER_BG_COLOUR = 1, MF_RASTER_BG_IMAGE = 2 };
+typedef struct mf_raster_shade_args {
+  const void* scratch;
+  const int32_t* screen; const float* inv_z; const float* verts; const float* colors; int64_t V;
+  const int64_t* tris; int64_t T;
+  int64_t H, W;
+  float focal, cx, cy, pixel_offset;
+  float c2w[12];
+  int32_t shading; float ambient;
+  int32_t background_kind; uint8_t background_colour[4]; const uint8_t* background_image;
+  uint8_t* rgba; uint8_t* mask; float* depth; float* ray_t; int32_t* face;
+} mf_raster_shade_args;
+int32_t mf_raster_shade(const mf_raster_shade_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ and ``moco_flow_amd.metrics`` for the reference's ``models.metrics`` (mse, psnr,
 ``moco_flow_amd.vis`` for ``utils.vis_utils.visualize_depth`` (plus decode_results, frame_sheet, write_png),
 ``moco_flow_amd.batch`` for the ray batch of a training step (FrameRays: selection, rays and pixels in one launch),
 ``moco_flow_amd.supervision`` for its SMPL point supervision (correspondence, point_losses: no compaction, no host read),
-``moco_flow_amd.occupancy`` for a frame's occupancy grid (OccupancyGrid: culls and clips test-time rays in front of render_image).
+``moco_flow_amd.occupancy`` for a frame's occupancy grid (OccupancyGrid: culls and clips test-time rays in front of render_image),
+``moco_flow_amd.raster`` for the pictures the reference draws with pyrender (render_mesh, smpl_views: the stage-1 SMPL views).
 Every forward value comes from hand-written HIP kernels reached through the C ABI in include/mocoflow_hip.h
 (libmocoflow_hip.so); CPU tensors and a missing library raise.  The backward is HIP as well -- of render_rays passes
 (which record gradients in fp32 whatever set_precision says) and of module-level NeRF / NoF / Embedding calls; shapes it
@@ -30,6 +31,8 @@ from . import supervision
 from .supervision import Correspondence, correspondence, point_correspond, point_losses
 from . import occupancy
 from .occupancy import OccupancyGrid
+from . import raster
+from .raster import interpolate, project_vertices, rasterize, render_mesh, smpl_views
 from .autograd import set_dx_precision, set_wgrad_precision
 from .rendering import render_rays, resample_merge, sample_pdf, set_precision, set_train_forward_precision
 
@@ -38,4 +41,5 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "marching_cubes", "mesh_components", "filter_components", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
            "vis", "visualize_depth", "decode_results", "frame_sheet", "write_png", "batch", "FrameRays",
            "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
-           "occupancy", "OccupancyGrid"]
+           "occupancy", "OccupancyGrid",
+           "raster", "project_vertices", "rasterize", "interpolate", "render_mesh", "smpl_views"]

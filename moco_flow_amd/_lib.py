@@ -79,6 +79,19 @@ class mf_ray_batch_args(C.Structure):
                 ("rays_out", _fp), ("rgbs_out", _fp), ("background_out", _fp), ("sel_out", _fp)]
 
 
+MF_RASTER_SHADE_NONE, MF_RASTER_SHADE_HEADLIGHT = 0, 1
+MF_RASTER_BG_NONE, MF_RASTER_BG_COLOUR, MF_RASTER_BG_IMAGE = 0, 1, 2
+
+
+class mf_raster_shade_args(C.Structure):
+    _fields_ = [("scratch", _fp), ("screen", _fp), ("inv_z", _fp), ("verts", _fp), ("colors", _fp), ("V", C.c_int64),
+                ("tris", _fp), ("T", C.c_int64), ("H", C.c_int64), ("W", C.c_int64),
+                ("focal", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("pixel_offset", C.c_float), ("c2w", C.c_float * 12),
+                ("shading", C.c_int32), ("ambient", C.c_float),
+                ("background_kind", C.c_int32), ("background_colour", C.c_uint8 * 4), ("background_image", _fp),
+                ("rgba", _fp), ("mask", _fp), ("depth", _fp), ("ray_t", _fp), ("face", _fp)]
+
+
 class mf_point_loss_args(C.Structure):
     _fields_ = [("Q", C.c_int64), ("pairs", _fp), ("inside", _fp), ("use_all", C.c_int32), ("pred_bw", _fp), ("pred_fw", _fp),
                 ("n_nerfs", C.c_int32), ("sigma", _fp * 2), ("delta", C.c_float * 2)]
@@ -226,6 +239,14 @@ SYMBOLS = {
     "mf_occ_build": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
     "mf_ray_clip": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp, _fp]),
+    "mf_project_vertices": (C.c_int32, [_fp, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
+                                        _fp, _fp, _fp, _fp]),
+    "mf_raster_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_rasterize": (C.c_int32, [_fp, _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, _fp, _fp]),
+    "mf_raster_resolve": (C.c_int32, [_fp, _fp, _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_float, _fp, _fp, _fp,
+                                      _fp, _fp]),
+    "mf_raster_interpolate": (C.c_int32, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp]),
+    "mf_raster_shade": (C.c_int32, [C.POINTER(mf_raster_shade_args), _fp]),
 }
 
 _lock = threading.Lock()

@@ -10,6 +10,67 @@ import torch
 from . import _lib as L
 
 
+def sample_on_sphere(num, dist=1.0, half=False):
+    """Camera positions for the stage-1 views (scripts/data_utils.py:166-181): a golden-ratio spiral on the sphere of radius
+    ``dist``.  With N = 2 num if half else num and g = (sqrt(5) - 1) / 2, point n = 1 .. N has y = (2 n - 1) / N - 1 and the
+    angle 2 pi n g around the y axis: (cos(a) r, y, sin(a) r) dist with r = sqrt(1 - y^2); ``half`` keeps the points with
+    y >= 0.  Host numpy, float64, (num, 3)."""
+    n_all = int(num) * 2 if half else int(num)
+    n = np.arange(1, n_all + 1, dtype=np.float64)
+    y = (2.0 * n - 1) / n_all - 1.0
+    ang = 2 * np.pi * n * ((np.sqrt(5) - 1.0) / 2.0)
+    r = np.sqrt(1 - y * y)
+    pts = np.stack([np.cos(ang) * r * dist, y * dist, np.sin(ang) * r * dist], axis=1)
+    return pts[y >= 0] if half else pts
+
+
+def look_at_pose(position, target):
+    """The (4, 4) float64 camera-to-world pose at ``position`` whose -z axis passes through ``target``
+    (get_camera_pose, scripts/data_utils.py:184-200): z = unit(position - target), x = unit((0, 0, 1) x z) -- or (1, 0, 0)
+    where |z.z| >= 0.999 -- and y = z x x.  (Like the reference's, the pose of that pole branch is orthonormal only exactly at
+    the pole.)"""
+    position, target = np.asarray(position, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    z = position - target
+    z = z / np.linalg.norm(z)
+    if abs(z[2]) < 0.999:
+        x = np.cross(np.array([0.0, 0.0, 1.0]), z)
+        x = x / np.linalg.norm(x)
+    else:
+        x = np.array([1.0, 0.0, 0.0])
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = x, np.cross(z, x), z, position
+    return pose
+
+
+def spheric_poses(num=30, radius=2.0, center=(0, 0, 0), vec_up=None):
+    """The (3 num, 4, 4) float32 turntable of create_spheric_poses / pose_spherical (utils/vis_utils.py:46-119): ``num`` angles
+    theta = 360 k / num at each of the elevations phi = 0, -15, -30 degrees.  One pose is, in float32 matrices multiplied in
+    this order, A Ry(theta) Rx(phi) T(radius) -- T moves the camera along +z, Rx(phi) = [[1, 0, 0], [0, cos, -sin], [0, sin, cos]],
+    Ry(theta) = [[cos, 0, -sin], [0, 1, 0], [sin, 0, cos]], A swaps y and z and negates x -- then, with vec_up, the frame
+    (u1, u x u1, u) of the unit up vector u with u1 = (u.x, -u.z, u.y) in front of it; ``center`` is added to the position."""
+    def one(theta, phi):
+        th, ph = theta / 180.0 * np.pi, phi / 180.0 * np.pi
+        move = np.eye(4, dtype=np.float32)
+        move[2, 3] = radius
+        rx = np.eye(4, dtype=np.float32)
+        rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(ph), -np.sin(ph), np.sin(ph), np.cos(ph)
+        ry = np.eye(4, dtype=np.float32)
+        ry[0, 0], ry[0, 2], ry[2, 0], ry[2, 2] = np.cos(th), -np.sin(th), np.sin(th), np.cos(th)
+        axes = np.array([[-1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=np.float32)
+        m = axes @ (ry @ (rx @ move))
+        if vec_up is not None:
+            u = np.asarray(vec_up) / np.linalg.norm(vec_up)
+            u1 = np.array([u[0], -u[2], u[1]])
+            frame = np.eye(4, dtype=np.float32)
+            frame[:3, 0], frame[:3, 1], frame[:3, 2] = u1, np.cross(u, u1), u
+            m = frame @ m
+        if center is not None:
+            m[:3, 3] += center
+        return m
+    angles = np.linspace(0, 360, int(num) + 1)[:-1]
+    return np.stack([one(a, phi) for phi in (0.0, -15.0, -30.0) for a in angles], 0)
+
+
 def make_rays(H, W, focal, center, c2w, near, far, idx, device="cuda"):
     """rays (H*W, 9) = [o, unit d, near, far, idx] on ``device``; ``focal`` = K[0][0] (the reference uses
     focal[0] for both axes, camera.py:47), ``center`` = (K[0][2], K[1][2]), ``c2w`` (3|4, 4) array or None."""
