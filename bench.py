@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the MoCo-Flow volume-rendering hot path on MI355X.
 
-    python bench.py                                   # 1 GPU, headline (BASELINE config C2)
+    python bench.py                                   # 1 GPU, headline (BASELINE config C2) and nothing else: set-up,
+                                                      # warm-up, the timed steps, one short JSON line
+    python bench.py --full                            # + roofline, CPU baseline, error against the oracle, the legs of the
+                                                      # other configs, training and auxiliary legs, the detail record
     python bench.py --gpus N [--steps K --warmup W]   # N ranks on one node; run BARE it spawns its own
                                                       # N workers (one per GPU, RCCL), or run it under
                                                       # `python -m torch.distributed.run --nproc-per-node N`
@@ -20,7 +23,10 @@ BASELINE.json configs:
   C4   C3 ray-sharded, 4096 rays per rank, per-batch loss partials all-reduced over RCCL (N > 1)
   C5   coarse 64 + fine 128 with the inverse-CDF resample, MoCo local+global chains, bf16, 1024 rays per rank
        (8192 rays on 8 GPUs)
-The default run also measures the other configs as short extra legs and reports them in the same JSON line under
+A plain run (no --full) does what `value` needs and prints the contract keys, the workload's "config" and "rccl_ranks_seen";
+everything from here on is measured and reported with --full alone (--no-extra-legs / --no-cpu-baseline / --no-train-leg
+narrow it and mean nothing without it).
+The --full run also measures the other configs as short extra legs and reports them in the same JSON line under
 "configs" (N = 1: C3, C3g, C5 shard, and C2x / C3x / C5x = the same workloads in bf16x3, the fp32-class mode of the bf16
 matrix pipe -- every product as three bf16 products of (hi, lo) operand pairs; N > 1: C4, C5), each with its own
 roofline fraction and error against the CPU oracle, so every BASELINE config is driver-measured without changing what
@@ -739,7 +745,7 @@ def run_config(name, a, ctx, steps, warmup, main):
     # at every N, so the driver's 1 -> N curve compares like with like
     with_loss = bool(cfg.get("loss"))
     reducer = OverlappedLossReducer(N_PARTIALS, dev) if with_loss else None
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps if a.full else 0)]
 
     def step(i=None):
         if i is not None:
@@ -807,8 +813,8 @@ def run_config(name, a, ctx, steps, warmup, main):
             written = dump_outputs(out, a.dump_outputs)
             print("dump_outputs:", a.dump_outputs, json.dumps(written), file=sys.stderr)
         # per-call device span (step_span_ms), outside the timed region: the event pairs cost ~10 us of stream time each on
-        # this runtime, which is 3 % of a 0.33 ms step
-        for i in range(steps):
+        # this runtime, which is 3 % of a 0.33 ms step (--full: `steps` more calls that the headline does not need)
+        for i in range(len(ev)):
             out = step(i)
         if reducer is not None:
             reducer.finish()
@@ -827,10 +833,21 @@ def run_config(name, a, ctx, steps, warmup, main):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    kernel_ms = float(np.median([s.elapsed_time(e) for s, e in ev]))        # SURVEY.md 8(d): median of the timed calls
-
     spr = samples_per_ray(cfg)
     value = n * spr * world * steps / elapsed
+    res = {
+        "value": value, "ms_per_step": elapsed / steps * 1e3, "dtype": cfg["precision"],
+        "config": {"workload": cfg["what"] + f" [{cfg['precision']}]", "rays_per_gpu": n,
+                   "samples_per_ray": spr, "global_rays": n * world,
+                   "sharding": f"rays{world}" if world > 1 else "none",
+                   "loss_allreduce": bool(reducer is not None and world > 1),
+                   # (ADVICE r4) the C2 main line carries no loss path and no collective at any N -- its 1 -> N curve is N
+                   # independent launches by design; the configs that name a collective (C4, C5) are the legs
+                   "main_has_collective": bool(reducer is not None and world > 1)},
+    }
+    if not a.full:              # a plain run: the headline alone -- everything below takes launches or CPU passes of its own
+        return res
+    kernel_ms = float(np.median([s.elapsed_time(e) for s, e in ev]))        # SURVEY.md 8(d): median of the timed calls
     flops_step = n * spr * flops_per_sample(cfg)
     step_span_ms = kernel_ms
     kernel_ms, launch_samples, probe_how = kernel_probe(M, rendering, torch, cfg, models, rays, bg, kw)
@@ -856,15 +873,7 @@ def run_config(name, a, ctx, steps, warmup, main):
         step_us = (bp["coarse"]["avg_us"] + bp["fine"]["avg_us"]) if (bp and launches == 2) else launches * prof["rocprof_avg_us"]
         rp.update({"frac_rocprof_avg": flops_step / (step_us * 1e-6) / 1e12 / peak, "rocprof_avg_us": prof["rocprof_avg_us"],
                    "mfma_busy": prof.get("mfma_busy"), "ghz": prof.get("ghz"), "profile": prof.get("profile")})
-    res = {
-        "value": value, "ms_per_step": elapsed / steps * 1e3, "dtype": cfg["precision"],
-        "config": {"workload": cfg["what"] + f" [{cfg['precision']}]", "rays_per_gpu": n,
-                   "samples_per_ray": spr, "global_rays": n * world,
-                   "sharding": f"rays{world}" if world > 1 else "none",
-                   "loss_allreduce": bool(reducer is not None and world > 1),
-                   # (ADVICE r4) the C2 main line carries no loss path and no collective at any N -- its 1 -> N curve is N
-                   # independent launches by design; the configs that name a collective (C4, C5) are the legs
-                   "main_has_collective": bool(reducer is not None and world > 1)},
+    res.update({
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "peak_note": PEAK_NOTE[cfg["precision"]],
                      "unit": "TFLOP/s", "frac": achieved / peak,
                      "frac_step": flops_step / (elapsed / steps) / 1e12 / peak,
@@ -877,7 +886,7 @@ def run_config(name, a, ctx, steps, warmup, main):
                      "kernel_ms": kernel_ms, "kernel_ms_how": probe_how, "flops_per_launch": flops_launch, "samples_per_launch": launch_samples,
                      "step_span_ms": step_span_ms, "launches_per_step": launches,
                      "flops_per_step": flops_step},
-    }
+    })
     if cfg["nof"] and reducer is None and world == 1:
         # the same pass for a mean-only caller (the trainer's loss terms): consensus sums from mf_loss_partials instead of
         # the compacted data-dependent-length vectors -- no host sync, so consecutive steps pipeline
@@ -957,10 +966,19 @@ def compact_leg(r):
 def assemble(a, world, main_cfg, res, leg_results, extras):
     """-> (detail, compact).  `detail` is everything measured (tens of KB: written to gpurun_out/bench_detail_n<N>.json and to
     stderr); `compact` is the ONE stdout line the driver parses: the contract keys + roofline + cpu_baseline + one array per
-    leg, numbers to 4 significant digits, no prose -- at most COMPACT_LIMIT bytes (tests/test_host_cpu.py holds it to that)."""
+    leg, numbers to 4 significant digits, no prose -- at most COMPACT_LIMIT bytes (tests/test_host_cpu.py holds it to that).
+    That is the --full shape.  A plain run has measured none of it: -> (None, compact), where `compact` is the contract keys, the
+    workload's "config" and "rccl_ranks_seen", and emit() then writes no detail."""
     head = {"metric": "ray-samples/sec (4096 rays x 64 samples)", "value": res["value"], "unit": "ray-samples/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": res["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": res["dtype"], "data": "synthetic"}
+    if not a.full:
+        # a plain run: the headline and what describes its workload, nothing that was measured beside it (and no detail)
+        compact = dict(head, value=sig(res["value"], 6), ms_per_step=sig(res["ms_per_step"], 5))
+        compact["config"] = dict(res["config"], workload=CONFIGS[main_cfg].get("short", main_cfg))
+        if "rccl_ranks_seen" in res:
+            compact["rccl_ranks_seen"] = res["rccl_ranks_seen"]
+        return None, compact
     detail = dict(head, config=res["config"], roofline=res["roofline"])
     for k in ("fwd_bwd", "train_steps", "cpu_baseline", "c1_cpu", "error_vs_cpu", "speedup_vs_cpu", "loss_path", "rccl_ranks_seen"):
         if k in res:
@@ -1023,7 +1041,13 @@ def assemble(a, world, main_cfg, res, leg_results, extras):
 
 
 def emit(detail, compact, world):
-    """Detail first (side file + ONE stderr line that does not start with '{'), then the compact line LAST on stdout."""
+    """Detail first (--full: side file + ONE stderr line that does not start with '{'), then the compact line LAST on stdout."""
+    if detail is not None:
+        emit_detail(detail, compact, world)
+    shed_and_print(compact)
+
+
+def emit_detail(detail, compact, world):
     blob = json.dumps(detail)
     try:
         if not compact.get("dryrun"):            # (a dry run leaves the real runs' side files alone)
@@ -1034,6 +1058,9 @@ def emit(detail, compact, world):
     except OSError as exc:
         print(f"bench_detail: could not write the side file ({exc})", file=sys.stderr)
     print("bench_detail " + blob, file=sys.stderr, flush=True)
+
+
+def shed_and_print(compact):
     # never out-grow the reporting channel again: shed the optional tails (never the contract keys) until the line fits
     for k in ("aux_frac", "train_hbm_gb", "train_dp_ms", "fwd_bwd_ms", "train_ms", "error_vs_cpu"):
         if len(json.dumps(compact)) <= COMPACT_LIMIT:
@@ -1048,7 +1075,7 @@ def emit(detail, compact, world):
 
 
 def leg_names(world):
-    """The short extra legs of a default run: every other BASELINE config at N = 1; at N > 1 the headline WITHOUT its
+    """The short extra legs of a --full run: every other BASELINE config at N = 1; at N > 1 the headline WITHOUT its
     collective (C2: what the C2dp main line adds the loss all-reduce to) + the configs that name a collective (C4, C5)."""
     return ["C2x", "C3", "C3x", "C3g", "C5", "C5x", "C5full", "C5xfull"] if world == 1 else ["C2", "C4", "C5"]
 
@@ -1231,16 +1258,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2",
                     help="BASELINE.json configuration of the main line (default C2 = the headline, at every N)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the short legs of the other BASELINE configs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the main line's roofline (kernel probe, per-call spans), the CPU baseline and the error against "
+                         "the CPU oracle, the legs of the other BASELINE configs, the training and auxiliary legs, the detail record")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the short legs of the other BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the error against the CPU oracle")
     ap.add_argument("--no-train-leg", action="store_true",
-                    help="skip the extra fwd+bwd measurement (SURVEY.md §8d: reported separately from the graded forward)")
+                    help="--full without the extra fwd+bwd measurement (SURVEY.md §8d: reported separately from the graded forward)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the main line's last timed step returned as DIR/<key>.npy "
                          "(float32, float64 kept; at most 64 MB in all, a fixed row sample beyond that; rank 0 at N > 1)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:              # a plain run measures the headline alone: the three --no-* options only narrow --full
+        a.no_extra_legs = a.no_cpu_baseline = a.no_train_leg = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and world == 1 and not os.environ.get("MF_BENCH_CHILD"):
         sys.exit(spawn_workers(a.gpus, sys.argv[1:]))      # nothing above touched the GPU (torch is not even imported)

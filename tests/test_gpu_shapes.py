@@ -233,7 +233,7 @@ def test_rccl_one_rank_child(preflight):
 
 
 def test_bench_two_ranks_real_worker_path(preflight):
-    """`python bench.py --gpus 2 --steps 3 --warmup 1` -- bench.py's REAL world > 1 worker path (self-spawned ranks, 127.0.0.1
+    """`python bench.py --gpus 2 --steps 3 --warmup 1 --full` -- bench.py's REAL world > 1 worker path (self-spawned ranks, 127.0.0.1
     rendezvous, the sharded main line WITH its loss all-reduce, C2 / C4 / C5 legs, MAX-over-ranks timing, one compact JSON
     line from rank 0 + the detail on stderr) -- with both ranks on GPU 0 and gloo as the backend (MF_BENCH_SHARE_GPU /
     MF_BENCH_BACKEND: what one GPU can execute; RCCL itself is the other child's subject)."""

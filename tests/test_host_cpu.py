@@ -835,7 +835,7 @@ def test_descriptor_and_slot_caches_follow_edits():
 
 
 def test_bench_self_spawns_its_ranks():
-    """`python bench.py --gpus 2` run BARE (no torch.distributed.run) starts its own two workers before touching
+    """`python bench.py --gpus 2 --full` run BARE (no torch.distributed.run) starts its own two workers before touching
     the GPU; control flow on CPU with MF_BENCH_DRYRUN (gloo rendezvous on 127.0.0.1, overlapped reducer,
     MAX-over-ranks timing, exactly one JSON line from rank 0, exit code = worst worker)."""
     import json
@@ -843,7 +843,7 @@ def test_bench_self_spawns_its_ranks():
     env = dict(os.environ, MF_BENCH_DRYRUN="1")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -851,7 +851,7 @@ def test_bench_self_spawns_its_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["dryrun"][0] == 3.0      # ranks contribute 1 + 2
     # the driver's largest world: 8 ranks (1 + 2 + ... + 8 = 36)
-    r8 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1"],
+    r8 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full"],
                         env=env, capture_output=True, text=True, timeout=400)
     assert r8.returncode == 0, r8.stderr[-2000:]
     d8 = json.loads([l for l in r8.stdout.splitlines() if l.startswith("{")][-1])
@@ -876,7 +876,7 @@ REQUIRED_LINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "m
 def test_bench_last_stdout_line_is_compact(gpus):
     """round 5's 27.9 KB line left the driver's record with parsed = null.  The LAST stdout line of bench.py
     must be ONE strict-JSON object of at most 1800 bytes (it then fits whole in the driver's 2000-character tail) that
-    carries the contract keys + roofline + cpu_baseline + legs; the tens of KB of detail go to stderr / a side file.  Run
+    carries the contract keys + (--full, its longest form) roofline + cpu_baseline + legs; the tens of KB of detail go to stderr / a side file.  Run
     through MF_BENCH_DRYRUN: the same assemble() / emit() as a real run, fed results shaped like run_config()'s with
     full-length floats for the complete leg set of that world size."""
     import json
@@ -884,7 +884,7 @@ def test_bench_last_stdout_line_is_compact(gpus):
     env = dict(os.environ, MF_BENCH_DRYRUN="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.rstrip("\n").splitlines()[-1]
@@ -918,6 +918,35 @@ def test_bench_last_stdout_line_is_compact(gpus):
     # the detail went to stderr as one line that no '{'-line parser picks up
     det = [l for l in r.stderr.splitlines() if l.startswith("bench_detail {")]
     assert len(det) == 1 and json.loads(det[0][len("bench_detail "):])["roofline"]["from_profiles"] is not None
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_reports_the_headline_alone(gpus):
+    """Without --full the benchmark measures its headline and nothing beside it: the line carries the contract keys, the
+    workload's "config" and the ranks seen -- no roofline, no CPU baseline, no legs, no training or auxiliary figures --
+    and no detail record goes to stderr; the three --no-* options change nothing about it.  (MF_BENCH_DRYRUN: the same
+    assemble() / emit() as a real run.)"""
+    import json
+    import subprocess
+    env = dict(os.environ, MF_BENCH_DRYRUN="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    lines = []
+    for extra in ([], ["--no-extra-legs", "--no-cpu-baseline", "--no-train-leg"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5"] + extra,
+                           env=env, capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert not [l for l in r.stderr.splitlines() if l.startswith("bench_detail")]
+        assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
+        lines.append(json.loads(r.stdout.rstrip("\n").splitlines()[-1]))
+    d = lines[0]
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                      "dtype", "data", "config", "rccl_ranks_seen", "dryrun"}, sorted(d)
+    assert set(lines[1]) == set(d) and all(lines[1][k] == d[k] for k in d if k != "dryrun")
+    assert d["metric"] == "ray-samples/sec (4096 rays x 64 samples)" and d["unit"] == "ray-samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["n_gpus"] == gpus and d["steps"] == 20 and d["warmup"] == 5 and d["rccl_ranks_seen"] == gpus
+    assert d["config"]["global_rays"] == 4096 * gpus and d["config"]["main_has_collective"] is (gpus > 1)
 
 
 def test_bench_under_torch_distributed_run():

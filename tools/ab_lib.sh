@@ -27,7 +27,7 @@ else
   for rep in 1 2 3; do
     for name in "$@"; do
       L=$AB/lib_$name.so; [ $name = default ] && L=""       # "default": the in-tree library
-      MOCOFLOW_HIP_LIB=$L python3 $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-train-leg --no-extra-legs $BARGS 2>/dev/null | python3 -c "
+      MOCOFLOW_HIP_LIB=$L python3 $REPO/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-train-leg --no-extra-legs $BARGS 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$name rep$rep kernel_ms %.4f frac %.3f step %.3f' % (r['kernel_ms'], r['frac'], d['ms_per_step']))"

@@ -5,5 +5,5 @@
 for rep in 1 2; do
 for f in ${FLAGS:-0 1 2 3 4 8 15}; do
   echo -n "MF_DEBUG_FLAGS=$f: "
-  MF_DEBUG_FLAGS=$f python bench.py --no-cpu-baseline --no-train-leg --no-extra-legs --steps 30 --warmup 3 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('kernel ms', round(d['roofline']['kernel_ms'],4), 'frac', round(d['roofline']['frac'],4))"
+  MF_DEBUG_FLAGS=$f python bench.py --full --no-cpu-baseline --no-train-leg --no-extra-legs --steps 30 --warmup 3 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('kernel ms', round(d['roofline']['kernel_ms'],4), 'frac', round(d['roofline']['frac'],4))"
 done; done

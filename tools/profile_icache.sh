@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/ic_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 3 --no-cpu-baseline --no-train-leg --no-extra-legs $*"
+ARGS="--steps 10 --warmup 3 --full --no-cpu-baseline --no-train-leg --no-extra-legs $*"
 timeout 300 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $OUT/p1 -- python3 $REPO/bench.py $ARGS > $OUT/p1.log 2>&1
 python3 - $OUT <<'PY'
 import csv, glob, os, sys
