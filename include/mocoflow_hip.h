@@ -49,7 +49,8 @@ extern "C" {
  *     + MF_F_FOLDED_FINAL (the fp32 inference stream with xyz_encoding_final folded into extra_encoding); mf_occ_build
  *     (+ mf_occ_build_scratch_bytes), mf_ray_clip; mf_mesh_label, mf_mesh_table_count / mf_mesh_table_emit, mf_mesh_filter_plan /
  *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows; mf_project_vertices, mf_rasterize (+ mf_raster_scratch_bytes),
- *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade */
+ *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade; mf_resize_u8 (+ mf_resize_u8_scratch_bytes), mf_composite_rows,
+ *     mf_background_plate */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -954,6 +955,58 @@ typedef struct mf_raster_shade_args {
   uint8_t* rgba; uint8_t* mask; float* depth; float* ray_t; int32_t* face;
 } mf_raster_shade_args;
 int32_t mf_raster_shade(const mf_raster_shade_args* a, void* stream);
+
+/* ---- frame ingest (moco_flow_amd/csrc/mf_frames.hip): from decoded 8-bit frames to the tensors mf_ray_batch, mf_ssim and
+ * mf_frame_sheet take -- the resize of datasets/moco_flow_dataset.py:51-55, 169 (also :45, the background image), the composite
+ * of :174-176 over the whole frame, and the background plate of scripts/data_utils.py:150-163.  Integer arithmetic on bytes, or
+ * fp32 rounded once per operation: every result is pinned bit for bit.  No entry allocates or synchronises. */
+
+/* Bytes of the scratch mf_resize_u8 needs (datasets/moco_flow_dataset.py:51-55, 169): the byte image between the two passes,
+ * F H0 W C, or 0 where at most one axis changes size.  -1 on a negative size or C outside {1, 3, 4}. */
+int64_t mf_resize_u8_scratch_bytes(int64_t F, int64_t H0, int64_t W0, int32_t C, int64_t H, int64_t W);
+/* mf_resize_u8 (datasets/moco_flow_dataset.py:51-55, 169: T.Resize on a PIL image): in (F, H0, W0, C) bytes -> out (F, H, W, C)
+ * bytes, C in {1, 3, 4}, equal to Image.fromarray(a).resize((W, H), Image.BILINEAR) of PIL 12 bit for bit: the antialiased
+ * triangle filter in two passes, horizontal first, with 22-bit fixed-point coefficients.
+ *   Per axis (x: W0 -> W, y: H0 -> H) the caller uploads bounds (out, 2) int32 = (first tap, tap count n <= ksize) and kk (out,
+ *   ksize) int32, zeros past n (moco_flow_amd/frames.py builds them in float64 as PIL's precompute_coeffs does).  A pass computes
+ *   clamp((2^21 + sum_t pixel[first + t] kk_t) >> 22, 0, 255) in int32 and writes bytes; the vertical pass reads the horizontal
+ *   pass's bytes (scratch).  A pass whose axis keeps its size is skipped (its tables may be NULL); neither changes: a plain copy.
+ *   C = 4 is resampled premultiplied (PIL's RGBA -> RGBa -> resize -> RGBA): the first pass that runs loads c' = (t + (t >> 8))
+ *   >> 8, t = c a + 128; the last one stores c = c' where a' is 0 or 255, else min(255, 255 c' / a'); the plain copy does
+ *   neither.  in, out and scratch must be 4-byte aligned for C = 4.
+ * A table entry is never trusted with an address: first and n are clamped to the axis; a coefficient is read as a 24-bit unsigned
+ * number (PIL's are at most 2^22 + 1).  32-bit indexing: F H0 W0 C, F H0 W C and
+ * F H W C below 2^31, else MF_E_INVALID (the Python side chunks the frames).  An output of 0 bytes launches nothing; an empty input
+ * axis with a non-empty output is MF_E_INVALID. */
+int32_t mf_resize_u8(const uint8_t* in, int64_t F, int64_t H0, int64_t W0, int32_t C, int64_t H, int64_t W,
+                     const int32_t* xbounds, const int32_t* xkk, int32_t xksize,
+                     const int32_t* ybounds, const int32_t* ykk, int32_t yksize, uint8_t* out, void* scratch, void* stream);
+
+/* mf_composite_rows (datasets/moco_flow_dataset.py:169-176, over every pixel: what mf_ray_batch does for the selected ones):
+ * rows_out (H W, 3) fp32 from
+ *   MF_IMAGE_U8_RGBA  image (H, W, 4) bytes, 4-byte aligned: v_c a + bg_c (1 - a), the expression of mf_ray_batch (the same device
+ *                     function: a row equals the batch's row bit for bit); needs a background
+ *   MF_IMAGE_U8_RGB   image (H, W, 3) bytes: u * (1.0f / 255.0f); takes no background
+ * background_kind: MF_BACKGROUND_ROWS (fp32 (H W, 3)), MF_BACKGROUND_COLOUR (3 device floats) or MF_BACKGROUND_U8 ((H, W, 3)
+ * bytes, read as u * (1.0f / 255.0f) -- the plate of mf_background_plate as it stands).  Any other kind, H W >= 2^31 / 4 or a
+ * NULL that is needed: MF_E_INVALID.  H W = 0 launches nothing. */
+enum { MF_BACKGROUND_U8 = 3 };
+int32_t mf_composite_rows(const void* image, int32_t image_kind, int64_t H, int64_t W, const void* background,
+                          int32_t background_kind, float* rows_out, void* stream);
+
+/* mf_background_plate (scripts/data_utils.py:150-163, generate_background_image): frames (F, H, W, C) bytes, C in {3, 4}
+ * (channel 3 is ignored), masks (F, H, W) bytes -> out (H, W, 3) bytes.  Per pixel and channel the key of frame f is u (255 - m),
+ * 0 .. 65025; out = (key_k + 127) / 255 in integer division of the k-th smallest key, k 0-based from the caller (the reference's
+ * int(num_images * 0.8)).  That is floor(255 x + 0.5) of the reference's float64 np.sort(img / 255. * (1 - msk / 255.), axis=0)[k]:
+ * 255 is odd, so no value lies within 1 / 510 of a rounding boundary.
+ * The k-th key is found by 16 bisection steps on its bits, counting keys below the trial value; no atomics, bit-identical from run
+ * to run.  path: MF_PLATE_AUTO stages a workgroup's tile of keys in LDS -- every frame byte is read from memory once -- while F is
+ * within the LDS bound (a named constant of the unit) and streams the frames from memory per step beyond it; MF_PLATE_STAGED /
+ * MF_PLATE_STREAMED force one (STAGED beyond the bound is MF_E_INVALID).  1 <= F < 65536, 0 <= k < F, H W < 2^31 / 4, else
+ * MF_E_INVALID.  H W = 0 launches nothing. */
+enum { MF_PLATE_AUTO = 0, MF_PLATE_STAGED = 1, MF_PLATE_STREAMED = 2 };
+int32_t mf_background_plate(const uint8_t* frames, const uint8_t* masks, int64_t F, int64_t H, int64_t W, int32_t C, int64_t k,
+                            int32_t path, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

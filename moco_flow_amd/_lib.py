@@ -68,6 +68,8 @@ MF_PANEL_RGB, MF_PANEL_DEPTH = 0, 1
 
 MF_IMAGE_NONE, MF_IMAGE_ROWS, MF_IMAGE_U8_RGB, MF_IMAGE_U8_RGBA = 0, 1, 2, 3
 MF_BACKGROUND_NONE, MF_BACKGROUND_ROWS, MF_BACKGROUND_COLOUR = 0, 1, 2
+MF_BACKGROUND_U8 = 3                      # mf_composite_rows only: an (H, W, 3) byte image
+MF_PLATE_AUTO, MF_PLATE_STAGED, MF_PLATE_STREAMED = 0, 1, 2
 
 
 class mf_ray_batch_args(C.Structure):
@@ -247,6 +249,11 @@ SYMBOLS = {
                                       _fp, _fp]),
     "mf_raster_interpolate": (C.c_int32, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp]),
     "mf_raster_shade": (C.c_int32, [C.POINTER(mf_raster_shade_args), _fp]),
+    "mf_resize_u8_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64]),
+    "mf_resize_u8": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _fp, _fp, C.c_int32,
+                                 _fp, _fp, C.c_int32, _fp, _fp, _fp]),
+    "mf_composite_rows": (C.c_int32, [_fp, C.c_int32, C.c_int64, C.c_int64, _fp, C.c_int32, _fp, _fp]),
+    "mf_background_plate": (C.c_int32, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _fp, _fp]),
 }
 
 _lock = threading.Lock()

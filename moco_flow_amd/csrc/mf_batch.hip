@@ -6,15 +6,8 @@
 //                     (_shared_step, trainer_moco_flow.py:308-312) -- none of those tables exists here.
 // No atomics anywhere: the compaction keeps the pixel order and is bit-identical from run to run.
 #include "mf_host.hpp"
+#include "mf_pixels.hpp"   // the 8-bit pixel arithmetic (and the no-FMA pragma), shared with mf_frames.hip
 #include "mf_rays.hpp"
-
-// 8-bit compositing is the torch expression operation for operation: no fused multiply-add (the Makefile builds every unit
-// with -ffp-contract=off; the pragma keeps it true for a build that forgets the flag)
-#pragma clang fp contract(off)
-
-// u8.float() / 255 as torch evaluates it ON THE DEVICE: a tensor divided by a host scalar is multiplied by the scalar's fp32
-// reciprocal, one rounding for the reciprocal and one for the product.  For 126 of the 256 byte values that is one ulp from the
-// fp32 quotient ToTensor computes on the host; the batch equals the eager device expression it replaces, bit for bit.
 
 namespace mf {
 
@@ -23,7 +16,6 @@ constexpr int kCompactPerLane = 16;                                      // byte
 constexpr int kCompactTile = kCompactThreads * kCompactPerLane;          // 4096 bytes of the mask per workgroup trip
 constexpr int kCompactMaxBlocks = 1024;                                  // the grid stops growing: longer masks take more trips
 constexpr int kBatchThreads = 256;
-constexpr float kInv255 = 1.0f / 255.0f;                                  // rounded once, to fp32
 
 struct MaskCompactPlan { long long per; int nblocks; };
 
@@ -221,17 +213,9 @@ __global__ __launch_bounds__(kBatchThreads) void ray_batch_kernel(const RayBatch
   } else if (ok && p.image_kind == kImageU8Rgb) {
     const unsigned char* im = static_cast<const unsigned char*>(p.image);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) rgb[c] = (float)im[(size_t)pix * 3 + c] * kInv255;     // .float().div(255) on the device
+    for (int c = 0; c < 3; ++c) rgb[c] = u8_unit(im[(size_t)pix * 3 + c]);
   } else if (ok) {
-    const unsigned px = static_cast<const unsigned*>(p.image)[pix];                   // r | g << 8 | b << 16 | a << 24
-    const float a = (float)(px >> 24) * kInv255;
-    const float na = 1.f - a;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = (float)((px >> (8 * c)) & 0xffu) * kInv255;
-      const float fg = v * a, back = bg[c] * na;                           // moco_flow_dataset.py:174, one rounding each
-      rgb[c] = fg + back;
-    }
+    composite_u8_rgba(static_cast<const unsigned*>(p.image)[pix], bg, rgb);           // r | g << 8 | b << 16 | a << 24
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) p.rgbs[k * 3 + c] = rgb[c];

@@ -1,0 +1,217 @@
+"""Frame ingest on the device: from decoded 8-bit frames to the tensors ``batch.FrameRays.sample``, ``metrics.image_metrics`` and
+``vis.frame_sheet`` take (reference: datasets/moco_flow_dataset.py:45, 51-55, 169-176; scripts/data_utils.py:150-163).
+
+    resize            ``T.Resize(size)`` on the PIL image -- PIL's antialiased bilinear resample, bit for bit (mf_resize_u8)
+    composite         ``img[:3] * a + bkgd * (1 - a)`` over the whole frame -> (H W, 3) fp32 rows (mf_composite_rows); row p is the
+                      row FrameRays.sample returns for pixel p, bit for bit
+    to_rows           an (H, W, 3) byte image as (H W, 3) fp32 rows, ``u8.float() / 255`` as the device evaluates it
+    background_plate  ``generate_background_image``: per pixel and channel the k-th smallest of img (1 - msk) over the frames, as
+                      bytes (mf_background_plate) -- without the reference's float64 copy of every frame and its np.sort
+
+Everything is integer arithmetic on bytes or fp32 rounded once per operation, so every result is pinned exactly.  The resize
+coefficients are built here on the host in float64, as PIL's precompute_coeffs builds them, and uploaded once per size pair and
+device.  No gradients; everything runs on the current stream of the inputs' device.  CPU tensors raise: there is no host path."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+__all__ = ["resize", "composite", "to_rows", "background_plate", "resize_tables", "plate_index"]
+
+_PRECISION_BITS = 22           # PIL's PRECISION_BITS = 32 - 8 - 2
+_INDEX_LIMIT = 2 ** 31         # the kernels index with 32 bits: a call stays below this many bytes per image stack
+_tables_host = {}
+_tables_device = {}
+
+
+def resize_tables(n_in, n_out):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc for the bilinear (triangle, support 1) filter along one axis of n_in ->
+    n_out pixels, in float64: (bounds (n_out, 2) int32 = [first tap, tap count], kk (n_out, ksize) int32, ksize).  The taps of
+    one output index are summed in order, as the C loop sums them (a pairwise sum differs in the last bit)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise RuntimeError(f"moco_flow_amd.frames.resize_tables: n_in={n_in} n_out={n_out}; both must be >= 1")
+    key = (n_in, n_out)
+    if key not in _tables_host:
+        scale = n_in / n_out
+        fs = max(scale, 1.0)
+        support = 1.0 * fs
+        ksize = int(math.ceil(support)) * 2 + 1
+        ss = 1.0 / fs
+        center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+        first = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # (int): truncation towards zero
+        count = np.minimum((center + support + 0.5).astype(np.int64), n_in) - first
+        w = np.zeros((n_out, ksize), dtype=np.float64)
+        ww = np.zeros(n_out, dtype=np.float64)
+        for x in range(ksize):
+            arg = np.abs(((x + first) - center + 0.5) * ss)
+            w[:, x] = np.where((x < count) & (arg < 1.0), 1.0 - arg, 0.0)
+            ww = ww + w[:, x]
+        nz = ww != 0.0
+        w[nz] = w[nz] / ww[nz, None]
+        kk = (0.5 + w * float(1 << _PRECISION_BITS)).astype(np.int64).astype(np.int32)    # the weights are >= 0: truncation
+        bounds = np.stack([first, count], axis=1).astype(np.int32)
+        _tables_host[key] = (bounds, kk, ksize)
+    return _tables_host[key]
+
+
+def _device_tables(n_in, n_out, device):
+    key = (n_in, n_out, device)
+    if key not in _tables_device:
+        bounds, kk, ksize = resize_tables(n_in, n_out)
+        _tables_device[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize)
+    return _tables_device[key]
+
+
+def _check_u8(t, what, name):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: {name} must be a uint8 tensor, got {got}")
+    L.require_gpu(t, f"frames.{what}")
+
+
+def resize(images, size):
+    """images: (H0, W0, C) or (F, H0, W0, C) uint8 on the device, C in {1, 3, 4}; size: (H, W), as the YAML's img_size gives it
+    (an int -- torchvision's "shorter side" -- raises).  Returns uint8 of the same rank, equal to
+    ``Image.fromarray(a).resize((W, H), Image.BILINEAR)`` of PIL 12 per frame, bit for bit; RGBA is resampled premultiplied as
+    PIL does (the identity returns the input's bytes).  A stack is resized in chunks of frames that keep every call inside
+    32-bit indexing."""
+    if isinstance(size, (int, np.integer)) or not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise RuntimeError(f"moco_flow_amd.frames.resize: size must be (H, W), got {size!r}")
+    _check_u8(images, "resize", "images")
+    H, W = int(size[0]), int(size[1])
+    if images.dim() not in (3, 4) or images.shape[-1] not in (1, 3, 4):
+        raise RuntimeError(f"moco_flow_amd.frames.resize: images is {tuple(images.shape)}; (H0, W0, C) or (F, H0, W0, C) with C in "
+                           "{1, 3, 4}")
+    stack = images if images.dim() == 4 else images.unsqueeze(0)
+    F, H0, W0, C = (int(v) for v in stack.shape)
+    if H < 0 or W < 0 or (F * H * W > 0 and H0 * W0 == 0):
+        raise RuntimeError(f"moco_flow_amd.frames.resize: ({H0}, {W0}) -> ({H}, {W})")
+    dev = stack.device
+    out = torch.empty((F, H, W, C), dtype=torch.uint8, device=dev)
+    if out.numel() == 0:                                    # nothing to launch
+        return out if images.dim() == 4 else out[0]
+    per_frame = max(H0 * W0, H0 * W, H * W) * C
+    if per_frame >= _INDEX_LIMIT:
+        raise RuntimeError(f"moco_flow_amd.frames.resize: one ({H0}, {W0}, {C}) -> ({H}, {W}) frame needs more than 32-bit indexing")
+    stack = stack.contiguous()
+    xb, xk, xks = _device_tables(W0, W, dev) if W != W0 else (None, None, 0)
+    yb, yk, yks = _device_tables(H0, H, dev) if H != H0 else (None, None, 0)
+    lib = L.lib()
+    chunk = max(1, min(F, (_INDEX_LIMIT - 1) // per_frame))
+    scratch = None
+    if W != W0 and H != H0:
+        scratch = torch.empty(int(lib.mf_resize_u8_scratch_bytes(chunk, H0, W0, C, H, W)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for f0 in range(0, F, chunk):
+            n = min(chunk, F - f0)
+            L.check(lib.mf_resize_u8(stack[f0].data_ptr(), n, H0, W0, C, H, W, L.ptr(xb), L.ptr(xk), xks, L.ptr(yb), L.ptr(yk), yks,
+                                     out[f0].data_ptr(), L.ptr(scratch), L.current_stream(dev)), "mf_resize_u8")
+    return out if images.dim() == 4 else out[0]
+
+
+def _composite_background(background, H, W):
+    """MF_BACKGROUND_* of `background`: None, (H W, 3) fp32 rows, one (3,) fp32 colour, or an (H, W, 3) uint8 image."""
+    if background is None:
+        return L.MF_BACKGROUND_NONE
+    if not isinstance(background, torch.Tensor):
+        raise RuntimeError(f"moco_flow_amd.frames.composite: background must be a tensor, got {type(background).__name__}")
+    shape = tuple(background.shape)
+    if background.dtype == torch.float32 and shape == (H * W, 3):
+        kind = L.MF_BACKGROUND_ROWS
+    elif background.dtype == torch.float32 and shape == (3,):
+        kind = L.MF_BACKGROUND_COLOUR
+    elif background.dtype == torch.uint8 and shape == (H, W, 3):
+        kind = L.MF_BACKGROUND_U8
+    else:
+        raise RuntimeError(f"moco_flow_amd.frames.composite: background is {shape} {background.dtype}; fp32 rows ({H * W}, 3), one "
+                           f"fp32 colour (3,) or a uint8 image ({H}, {W}, 3)")
+    L.require_gpu(background, "frames.composite")
+    return kind
+
+
+def composite(image, background=None):
+    """image: (H, W, 4) uint8 RGBA on the device, composited over `background` -- (H W, 3) fp32 rows, one (3,) fp32 colour or an
+    (H, W, 3) uint8 image such as background_plate's (read as u8 / 255) -- as moco_flow_dataset.py:174 does; or (H, W, 3) uint8
+    without a background: u8 / 255.  Returns the (H W, 3) fp32 rows that metrics.image_metrics and vis.frame_sheet take; row p is
+    what FrameRays.sample(image=image, background=...) returns for pixel p, bit for bit."""
+    _check_u8(image, "composite", "image")
+    if image.dim() != 3 or image.shape[2] not in (3, 4):
+        raise RuntimeError(f"moco_flow_amd.frames.composite: image is {tuple(image.shape)}; (H, W, 4) RGBA or (H, W, 3) RGB")
+    H, W, C = (int(v) for v in image.shape)
+    if H * W * 4 >= _INDEX_LIMIT:
+        raise RuntimeError(f"moco_flow_amd.frames.composite: H={H} W={W}; needs 4 H W < 2^31")
+    kind = _composite_background(background, H, W)
+    if C == 4 and kind == L.MF_BACKGROUND_NONE:
+        raise RuntimeError("moco_flow_amd.frames.composite: an RGBA image needs a background to composite over")
+    if C == 3 and kind != L.MF_BACKGROUND_NONE:
+        raise RuntimeError("moco_flow_amd.frames.composite: an RGB image has no alpha: it takes no background")
+    dev = image.device
+    if background is not None and background.device != dev:
+        raise RuntimeError(f"moco_flow_amd.frames.composite: background is on {background.device}, the image on {dev}")
+    rows = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+    if H * W == 0:
+        return rows
+    image = image.contiguous()
+    background = None if background is None else background.contiguous()
+    with torch.cuda.device(dev):
+        L.check(L.lib().mf_composite_rows(image.data_ptr(), L.MF_IMAGE_U8_RGBA if C == 4 else L.MF_IMAGE_U8_RGB, H, W,
+                                          L.ptr(background), kind, rows.data_ptr(), L.current_stream(dev)), "mf_composite_rows")
+    return rows
+
+
+def to_rows(image_u8):
+    """An (H, W, 3) uint8 image on the device -> (H W, 3) fp32 rows, u8 * (1.0f / 255.0f): a plate or a resized background as
+    FrameRays.sample's `background`."""
+    _check_u8(image_u8, "to_rows", "image_u8")
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise RuntimeError(f"moco_flow_amd.frames.to_rows: image_u8 is {tuple(image_u8.shape)}; (H, W, 3)")
+    return composite(image_u8)
+
+
+_PLATE_PATHS = {"auto": L.MF_PLATE_AUTO, "staged": L.MF_PLATE_STAGED, "streamed": L.MF_PLATE_STREAMED}
+
+
+def plate_index(F, q=0.8):
+    """k = int(F * q), the reference's int(num_images * 0.8) (data_utils.py:162); RuntimeError unless 1 <= F < 65536 and
+    0 <= k < F."""
+    F = int(F)
+    if F < 1 or F >= 65536:
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: F={F}; needs 1 <= F < 65536")
+    k = int(F * q)
+    if not 0 <= k < F:
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: q={q} gives k={k}; needs 0 <= k < F={F}")
+    return k
+
+
+def background_plate(frames, masks, q=0.8, path="auto"):
+    """scripts/data_utils.py:150-163.  frames: (F, H, W, 3 | 4) uint8 on the device (an alpha channel is ignored); masks: (F, H,
+    W) uint8, 255 = foreground.  Returns the (H, W, 3) uint8 plate: per pixel and channel the k-th smallest, k = int(F * q) (the
+    reference's int(num_images * 0.8)), of u (255 - m) over the frames, as (key + 127) // 255 -- floor(255 x + 0.5) of the
+    reference's float64 value.  RuntimeError unless 0 <= k < F.  path: "auto" stages the keys in LDS while F fits and streams
+    the frames beyond that; "staged" / "streamed" force one (the results are identical)."""
+    _check_u8(frames, "background_plate", "frames")
+    _check_u8(masks, "background_plate", "masks")
+    if frames.dim() != 4 or frames.shape[3] not in (3, 4):
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: frames is {tuple(frames.shape)}; (F, H, W, 3) or (F, H, W, 4)")
+    F, H, W, C = (int(v) for v in frames.shape)
+    if tuple(masks.shape) != (F, H, W):
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: masks is {tuple(masks.shape)}; ({F}, {H}, {W})")
+    if masks.device != frames.device:
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: masks is on {masks.device}, the frames on {frames.device}")
+    if path not in _PLATE_PATHS:
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: path={path!r}; one of {sorted(_PLATE_PATHS)}")
+    k = plate_index(F, q)
+    if H * W * 4 >= _INDEX_LIMIT:
+        raise RuntimeError(f"moco_flow_amd.frames.background_plate: H={H} W={W}; needs 4 H W < 2^31")
+    dev = frames.device
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    if H * W == 0:
+        return out
+    frames, masks = frames.contiguous(), masks.contiguous()
+    with torch.cuda.device(dev):
+        L.check(L.lib().mf_background_plate(frames.data_ptr(), masks.data_ptr(), F, H, W, C, k, _PLATE_PATHS[path], out.data_ptr(),
+                                            L.current_stream(dev)), "mf_background_plate")
+    return out
