@@ -8,6 +8,7 @@
 #include "mf_host.hpp"
 #include "mf_pixels.hpp"   // the 8-bit pixel arithmetic (and the no-FMA pragma), shared with mf_frames.hip
 #include "mf_rays.hpp"
+#include "mf_scan.hpp"
 
 namespace mf {
 
@@ -37,78 +38,55 @@ struct MaskCompactParams {
   long long* count;
 };
 
-// sum over the workgroup, every thread receives it
-__device__ __forceinline__ long long mask_block_sum(long long v, long long* lds) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();                                                       // lds may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-#pragma unroll
-  for (int w = 0; w < kCompactThreads / 64; ++w) s += lds[w];
-  return s;
-}
-
 // launch 1: the per-workgroup counts
 __global__ __launch_bounds__(kCompactThreads) void mask_count_kernel(const MaskCompactParams p) {
-  __shared__ long long lds[kCompactThreads / 64];
   const long long lo = blockIdx.x * p.per, hi = lo + p.per < p.n ? lo + p.per : p.n;
   long long c = 0;
   for (long long i = lo + threadIdx.x; i < hi; i += kCompactThreads) c += p.mask[i] != 0;
-  c = mask_block_sum(c, lds);
+  c = block_sum_i64<kCompactThreads>(c);
   if (threadIdx.x == 0) p.blk[blockIdx.x] = c;
 }
 
-// launch 2: every workgroup scans the counts in front of it (at most kCompactMaxBlocks integers: the order of the sum does not
-// matter), then scatters its share tile by tile: a wave owns 1024 consecutive bytes of a tile as 16 rows of 64, the position
-// of a set byte is the ballot prefix within its row plus the rows, waves and tiles in front of it
+// launch 2: every workgroup sums the counts in front of it (at most kCompactMaxBlocks integers), then scatters its share tile by
+// tile: a wave owns 1024 consecutive bytes of a tile as 16 rows of 64, the position of a set byte is its rank within its row
+// plus the rows, waves and tiles in front of it (mf_scan.hpp)
 __global__ __launch_bounds__(kCompactThreads) void mask_scatter_kernel(const MaskCompactParams p) {
-  __shared__ long long lds[kCompactThreads / 64];
-  __shared__ int wave_tot[kCompactThreads / 64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
   long long front = 0, all = 0;
   for (int b = threadIdx.x; b < p.nblocks; b += kCompactThreads) {
     const long long v = p.blk[b];
     all += v;
     if (b < (int)blockIdx.x) front += v;
   }
-  long long base = mask_block_sum(front, lds);
+  long long base = block_sum_i64<kCompactThreads>(front);
   if (blockIdx.x == 0) {
-    all = mask_block_sum(all, lds);
+    all = block_sum_i64<kCompactThreads>(all);
     if (threadIdx.x == 0) *p.count = all;
   }
   const long long lo = blockIdx.x * p.per, hi = lo + p.per < p.n ? lo + p.per : p.n;
   for (long long tile = lo; tile < hi; tile += kCompactTile) {           // lo, hi: the same for every thread of the workgroup
     const long long wbase = tile + (long long)w * (64 * kCompactPerLane);
     unsigned flags = 0;
-    int c = 0;
+    int c[1] = {0}, waves_front[1], tile_tot[1];
 #pragma unroll
     for (int j = 0; j < kCompactPerLane; ++j) {
       const long long i = wbase + j * 64 + lane;
       const bool m = i < hi && p.mask[i] != 0;
       flags |= (unsigned)m << j;
-      c += __popcll(__ballot(m));
+      c[0] += wave_popcount(m);
     }
-    if (lane == 0) wave_tot[w] = c;
-    __syncthreads();
-    long long off = base;
-    int tile_tot = 0;
-#pragma unroll
-    for (int v = 0; v < kCompactThreads / 64; ++v) {
-      if (v < w) off += wave_tot[v];
-      tile_tot += wave_tot[v];
-    }
+    block_offsets<kCompactThreads, 1>(c, waves_front, tile_tot);
+    long long off = base + waves_front[0];
 #pragma unroll
     for (int j = 0; j < kCompactPerLane; ++j) {
       const bool m = (flags >> j) & 1u;
-      const unsigned long long b = __ballot(m);
-      if (m) p.inds[off + __popcll(b & below)] = wbase + j * 64 + lane;   // off + prefix < the total count <= n
-      off += __popcll(b);
+      int row;
+      const int before = wave_rank(m, row);
+      if (m) p.inds[off + before] = wbase + j * 64 + lane;               // off + before < the total count <= n
+      off += row;
     }
-    base += tile_tot;
-    __syncthreads();                                                     // wave_tot is rewritten by the next tile
+    base += tile_tot[0];
+    __syncthreads();                                                     // block_offsets' LDS is rewritten by the next tile
   }
 }
 
@@ -271,7 +249,7 @@ extern "C" int32_t mf_ray_batch(const mf_ray_batch_args* a, void* stream) {
   if (a->image_kind != kImageNone && (!a->image || !a->rgbs_out)) return fail(MF_E_INVALID, "mf_ray_batch: null image or rgbs_out");
   if (a->background_kind != kBackgroundNone && !a->background) return fail(MF_E_INVALID, "mf_ray_batch: null background");
   if (a->background_kind == kBackgroundNone && a->background_out) return fail(MF_E_INVALID, "mf_ray_batch: background_out without a background");
-  if (a->image_kind == kImageU8Rgba && (reinterpret_cast<uintptr_t>(a->image) & 3u))
+  if (a->image_kind == kImageU8Rgba && !is_aligned(a->image, 4))
     return fail(MF_E_INVALID, "mf_ray_batch: an RGBA image must be 4-byte aligned");
   RayBatchParams p{};
   p.cam.H = a->H; p.cam.W = a->W; p.cam.fx = a->focal; p.cam.cx = a->cx; p.cam.cy = a->cy;
@@ -284,7 +262,7 @@ extern "C" int32_t mf_ray_batch(const mf_ray_batch_args* a, void* stream) {
   p.background = a->background; p.background_kind = a->background_kind;
   p.rays = a->rays_out; p.rgbs = a->rgbs_out; p.background_out = a->background_out;
   p.sel = reinterpret_cast<long long*>(a->sel_out);
-  p.rays_vec = (reinterpret_cast<uintptr_t>(a->rays_out) & 15u) == 0;
+  p.rays_vec = is_aligned(a->rays_out, 16);
   const dim3 grid((unsigned)((a->n_rows + kBatchThreads - 1) / kBatchThreads)), block(kBatchThreads);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a->has_chain) hipLaunchKernelGGL(ray_batch_kernel<10>, grid, block, 0, s, p);

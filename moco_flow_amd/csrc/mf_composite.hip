@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64 * kCompWaves) void composite_backward_kernel(Com
       a = fmaxf(sg, 0.f);
       da = sg > 0.f ? 1.f : 0.f;
     } else {
-      a = sg > 20.f ? sg : log1pf(expf(sg));
+      a = softplus_torch(sg);
       const float ez = expf(sg);
       da = sg > 20.f ? 1.f : ez / (ez + 1.f);
     }

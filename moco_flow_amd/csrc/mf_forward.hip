@@ -448,7 +448,7 @@ extern "C" int32_t mf_points_radiance(const mf_nerf_desc* nerf, const void* nerf
   if (!nerf || !nerf_packed || !emb_xyz || (B > 0 && (!xyz || !out)))
     return fail(MF_E_INVALID, "mf_points_radiance: null argument");
   if (B < 0) return fail(MF_E_INVALID, "mf_points_radiance: B=%lld", (long long)B);
-  if (reinterpret_cast<uintptr_t>(out) % 16) return fail(MF_E_INVALID, "mf_points_radiance: out must be 16-byte aligned");
+  if (!is_aligned(out, 16)) return fail(MF_E_INVALID, "mf_points_radiance: out must be 16-byte aligned");
   RadianceParams p{};
   if (!nerf_layout(*nerf, p.nerf.L) || p.nerf.L.NK != 16)
     return fail(MF_E_UNSUPPORTED, "mf_points_radiance: unsupported NeRF configuration");

@@ -10,8 +10,6 @@
 
 namespace mf {
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // ---- resize: PIL's ImagingResampleHorizontal_8bpc / Vertical_8bpc, one lane per output unit ----
 constexpr int kResizeThreads = 256;                                       // one workgroup's share: 256 output units
 constexpr int kResizePrecisionBits = 22;                                  // PIL's PRECISION_BITS = 32 - 8 - 2
@@ -376,7 +374,7 @@ extern "C" int32_t mf_resize_u8(const uint8_t* in, int64_t F, int64_t H0, int64_
   if (horizontal && (!xbounds || !xkk || xksize < 1)) return fail(MF_E_INVALID, "mf_resize_u8: the width changes: xbounds, xkk and xksize >= 1 are needed");
   if (vertical && (!ybounds || !ykk || yksize < 1)) return fail(MF_E_INVALID, "mf_resize_u8: the height changes: ybounds, ykk and yksize >= 1 are needed");
   if (horizontal && vertical && !scratch) return fail(MF_E_INVALID, "mf_resize_u8: both axes change: scratch is needed");
-  if (C == 4 && (!aligned_to(in, 4) || !aligned_to(out, 4) || (horizontal && vertical && !aligned_to(scratch, 4))))
+  if (C == 4 && (!is_aligned(in, 4) || !is_aligned(out, 4) || (horizontal && vertical && !is_aligned(scratch, 4))))
     return fail(MF_E_INVALID, "mf_resize_u8: RGBA in, out and scratch must be 4-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!horizontal && !vertical) {
@@ -401,7 +399,7 @@ extern "C" int32_t mf_resize_u8(const uint8_t* in, int64_t F, int64_t H0, int64_
       p.total = (int32_t)(F * H * W);
       if (horizontal) launch_resize(resize_vertical_kernel<4, false, true>, p, s);
       else launch_resize(resize_vertical_kernel<4, true, true>, p, s);
-    } else if (row_bytes % 4 == 0 && aligned_to(src, 4) && aligned_to(out, 4)) {   // channels are independent: four bytes a lane
+    } else if (row_bytes % 4 == 0 && is_aligned(src, 4) && is_aligned(out, 4)) {   // channels are independent: four bytes a lane
       p.units = (int32_t)(row_bytes / 4);
       p.total = (int32_t)(F * H * (row_bytes / 4));
       launch_resize(resize_vertical_kernel<4, false, false>, p, s);
@@ -429,9 +427,9 @@ extern "C" int32_t mf_composite_rows(const void* image, int32_t image_kind, int6
   if (n == 0) return MF_OK;
   if (!image || !rows_out) return fail(MF_E_INVALID, "mf_composite_rows: null image or rows_out");
   if (rgba && !background) return fail(MF_E_INVALID, "mf_composite_rows: null background");
-  if (rgba && !aligned_to(image, 4)) return fail(MF_E_INVALID, "mf_composite_rows: an RGBA image must be 4-byte aligned");
+  if (rgba && !is_aligned(image, 4)) return fail(MF_E_INVALID, "mf_composite_rows: an RGBA image must be 4-byte aligned");
   CompositeParams p{image, background, rows_out, (int32_t)n, background_kind, 0};
-  p.vec = aligned_to(image, 16) && aligned_to(rows_out, 16) && (!rgba || background_kind == MF_BACKGROUND_COLOUR || aligned_to(background, 16));
+  p.vec = is_aligned(image, 16) && is_aligned(rows_out, 16) && (!rgba || background_kind == MF_BACKGROUND_COLOUR || is_aligned(background, 16));
   const int per = kCompositeThreads * kCompositePerThread;
   const dim3 grid((unsigned)((n + per - 1) / per)), block(kCompositeThreads);
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -1,4 +1,4 @@
-// mf_host.hpp -- host-side helpers shared by the C-ABI translation units.
+// mf_host.hpp -- host-side helpers shared by the C-ABI translation units (and softplus_torch, the one device helper all share).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -42,6 +42,16 @@ inline int persistent_grid(long long work) {
   const long long cus = device_cus();
   return (int)(work < cus ? work : cus);
 }
+
+// grid of a grid-stride launch: ceil(n / per_block) workgroups, at most `cap`, at least `floor`
+inline long long capped_blocks(long long n, long long per_block, long long cap, long long floor = 0) {
+  const long long b = (n + per_block - 1) / per_block; return b < floor ? floor : b < cap ? b : cap;
+}
+
+inline bool is_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of 2
+inline long long align_up(long long x, long long a) { return (x + a - 1) & ~(a - 1); }
+// torch.nn.Softplus(): beta 1, threshold 20 (the render pass, the composite, mf_point_loss_partials, the occupancy grid)
+__device__ __forceinline__ float softplus_torch(float s) { return s > 20.f ? s : log1pf(expf(s)); }
 
 // an embedding's frequencies and weights as 16-entry tables, 0 beyond n_freqs; returns: the frequencies are exactly 2^k
 inline bool emb_table(const mf_embedding& e, float* freq, float* weight) {

@@ -190,8 +190,7 @@ extern "C" int32_t mf_loss_partials(const mf_loss_pass* coarse, const mf_loss_pa
   p.scratch = static_cast<double*>(scratch);
   p.out = out12;
   p.means = means6;
-  int blocks = (int)((work + kLossThreads * 8 - 1) / (kLossThreads * 8));
-  blocks = blocks < 1 ? 1 : (blocks > kLossBlocks ? kLossBlocks : blocks);
+  const int blocks = (int)capped_blocks(work, kLossThreads * 8, kLossBlocks, 1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(loss_partials_kernel, dim3(blocks), dim3(kLossThreads), 0, st, p);
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossBlocks), 0, st, p, blocks);

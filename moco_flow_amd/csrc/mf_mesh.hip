@@ -18,6 +18,7 @@
 // q's crossing edges below `axis`.  map is read only where the count pass wrote it (the table uses crossing edges only).
 #include "mf_host.hpp"
 #include "mf_mc_tables.hpp"
+#include "mf_scan.hpp"
 
 #include <climits>
 
@@ -111,35 +112,33 @@ __device__ __forceinline__ void classify(const McParams& p, long long p0, Points
   }
 }
 
-// exclusive prefix over the block of (a, b), a < 16, b < 32 per thread: bit-sliced wave ballots, then the wave totals via LDS
-__device__ __forceinline__ void block_scan(int a, int b, int& a_ex, int& b_ex, int& a_tot, int& b_tot) {
+// exclusive prefix and total over the block of (a, b), a < 16, b < 32 per thread: bit-sliced wave ballots, then the wave totals
+// via LDS.  The exchange is written out here: through block_offsets (mf_scan.hpp) mc_emit_kernel is allocated 58 VGPRs for 68
+// and another schedule, which is faster on a sparse mesh and slower on a dense one.
+__device__ __forceinline__ void block_scan(int a, int b, int (&ex)[2], int (&tot)[2]) {
   __shared__ int wave_tot[2][kThreads / 64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  const unsigned long long below = lanes_below(lane);
   int ea = 0, eb = 0, ta = 0, tb = 0;
 #pragma unroll
   for (int bit = 0; bit < 4; ++bit) {
     const unsigned long long m = __ballot((a >> bit) & 1);
-    ea += __popcll(m & below) << bit;
-    ta += __popcll(m) << bit;
+    ea += __popcll(m & below) << bit; ta += __popcll(m) << bit;
   }
 #pragma unroll
   for (int bit = 0; bit < 5; ++bit) {
     const unsigned long long m = __ballot((b >> bit) & 1);
-    eb += __popcll(m & below) << bit;
-    tb += __popcll(m) << bit;
+    eb += __popcll(m & below) << bit; tb += __popcll(m) << bit;
   }
   if (lane == 0) { wave_tot[0][w] = ta; wave_tot[1][w] = tb; }
   __syncthreads();
-  a_tot = b_tot = 0;
+  tot[0] = tot[1] = 0;
 #pragma unroll
   for (int v = 0; v < kThreads / 64; ++v) {
     if (v < w) { ea += wave_tot[0][v]; eb += wave_tot[1][v]; }
-    a_tot += wave_tot[0][v];
-    b_tot += wave_tot[1][v];
+    tot[0] += wave_tot[0][v]; tot[1] += wave_tot[1][v];
   }
-  a_ex = ea;
-  b_ex = eb;
+  ex[0] = ea; ex[1] = eb;
 }
 
 template <bool kVec>
@@ -147,51 +146,23 @@ __global__ __launch_bounds__(kThreads) void mc_count_kernel(const McParams p) {
   const long long p0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPerThread;
   Points s;
   classify<kVec>(p, p0, s);
-  int v_ex, t_ex, v_tot, t_tot;
-  block_scan(s.nv, s.nt, v_ex, t_ex, v_tot, t_tot);
+  int ex[2], tot[2];                                            // vertices, triangles
+  block_scan(s.nv, s.nt, ex, tot);
 #pragma unroll
   for (int q = 0; q < kPerThread; ++q) {
     if (s.mask[q]) {
-      p.map[p0 + q] = (v_ex << 3) | s.mask[q];
-      v_ex += __popc(s.mask[q]);
+      p.map[p0 + q] = (ex[0] << 3) | s.mask[q];
+      ex[0] += __popc(s.mask[q]);
     }
   }
-  if (threadIdx.x == 0) {
-    p.blk[blockIdx.x] = v_tot;
-    p.blk[p.nblocks + blockIdx.x] = t_tot;
-  }
+  if (threadIdx.x == 0) { p.blk[blockIdx.x] = tot[0]; p.blk[p.nblocks + blockIdx.x] = tot[1]; }
 }
 
 // one block: exclusive int64 prefix of the per-block totals (vertices, triangles), and the two grand totals
 __global__ __launch_bounds__(kScanThreads) void mc_scan_kernel(const McParams p) {
-  __shared__ long long wave_tot[2][kScanThreads / 64];
-  const int nb = p.nblocks, per = (nb + kScanThreads - 1) / kScanThreads;
-  const int lo = min(nb, (int)threadIdx.x * per), hi = min(nb, lo + per);
-  long long sv = 0, st = 0;
-  for (int b = lo; b < hi; ++b) { sv += p.blk[b]; st += p.blk[nb + b]; }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long long iv = sv, it = st;                                   // inclusive wave scan
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long uv = __shfl_up(iv, d), ut = __shfl_up(it, d);
-    if (lane >= d) { iv += uv; it += ut; }
-  }
-  if (lane == 63) { wave_tot[0][w] = iv; wave_tot[1][w] = it; }
-  __syncthreads();
-  long long bv = 0, bt = 0, tv = 0, tt = 0;
-  for (int v = 0; v < kScanThreads / 64; ++v) {
-    if (v < w) { bv += wave_tot[0][v]; bt += wave_tot[1][v]; }
-    tv += wave_tot[0][v];
-    tt += wave_tot[1][v];
-  }
-  long long ov = bv + iv - sv, ot = bt + it - st;
-  for (int b = lo; b < hi; ++b) {
-    p.off[b] = ov;
-    p.off[nb + b] = ot;
-    ov += p.blk[b];
-    ot += p.blk[nb + b];
-  }
-  if (threadIdx.x == 0) { p.counts[0] = tv; p.counts[1] = tt; }
+  long long total[2];
+  scan_totals<kScanThreads, 2>(p.blk, p.nblocks, p.off, total);
+  if (threadIdx.x == 0) { p.counts[0] = total[0]; p.counts[1] = total[1]; }
 }
 
 template <bool kVec>
@@ -199,10 +170,10 @@ __global__ __launch_bounds__(kThreads) void mc_emit_kernel(const McParams p) {
   const long long p0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPerThread;
   Points s;
   classify<kVec>(p, p0, s);
-  int v_ex, t_ex, v_tot, t_tot;
-  block_scan(s.nv, s.nt, v_ex, t_ex, v_tot, t_tot);
-  long long vid = p.off[blockIdx.x] + v_ex;
-  long long tid = p.off[p.nblocks + blockIdx.x] + t_ex;
+  int ex[2], tot[2];
+  block_scan(s.nv, s.nt, ex, tot);
+  long long vid = p.off[blockIdx.x] + ex[0];
+  long long tid = p.off[p.nblocks + blockIdx.x] + ex[1];
 #pragma unroll
   for (int q = 0; q < kPerThread; ++q) {
     const float f0 = s.f[0][q];
@@ -326,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void mc_normals_kernel(const NormalsParam
   o[0] = n[0]; o[1] = n[1]; o[2] = n[2];
 }
 
-bool vec_rows(const McParams& p) { return p.n2 % 4 == 0 && reinterpret_cast<uintptr_t>(p.vol) % 16 == 0; }
+bool vec_rows(const McParams& p) { return p.n2 % 4 == 0 && is_aligned(p.vol, 16); }
 
 }  // namespace mc
 }  // namespace mf

@@ -28,6 +28,7 @@
 // big component would otherwise send every add to one address.  Compaction is
 // mf_mask_compact (mf_batch.hip): ballots and fixed-order sums, original order kept.
 #include "mf_host.hpp"
+#include "mf_scan.hpp"
 
 using namespace mf;
 
@@ -43,12 +44,7 @@ constexpr int kMaxBlocks = 2048;                 // grid-stride loops: the grid 
 constexpr int kUnionBlocks = 512;
 constexpr long long kIndexLimit = 1LL << 31;     // 32-bit internal indexing
 
-inline unsigned grid_for(long long n, int cap = kMaxBlocks) {
-  const long long b = (n + kThreads - 1) / kThreads;
-  return (unsigned)(b < 1 ? 1 : b < cap ? b : cap);
-}
-
-inline long long align16(long long b) { return (b + 15) & ~15LL; }
+inline unsigned grid_for(long long n, int cap = kMaxBlocks) { return (unsigned)capped_blocks(n, kThreads, cap, 1); }
 
 // parents are read and written by many workgroups at once: relaxed agent-scope accesses (served by L2, never a stale L1 line
 // for good), the hook itself is a compare-and-swap
@@ -83,8 +79,7 @@ __device__ __forceinline__ bool in_range(long long i, long long n) { return (uns
 
 // sum over the wave, added once to a device counter; every lane of the wave calls it
 __device__ __forceinline__ void wave_add(long long* counter, long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  v = wave_sum_i64(v);
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
 }
 
@@ -213,11 +208,11 @@ inline TableScratch table_scratch(void* scratch, long long V) {
   char* base = static_cast<char*>(scratch);
   TableScratch s;
   long long o = 0;
-  s.tcount = reinterpret_cast<int*>(base + o); o += align16(4 * V);
-  s.vcount = reinterpret_cast<int*>(base + o); o += align16(4 * V);
-  s.is_root = reinterpret_cast<unsigned char*>(base + o); o += align16(V);
+  s.tcount = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
+  s.vcount = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
+  s.is_root = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
   s.slot = reinterpret_cast<long long*>(base + o); o += 16;
-  s.compact = base + o; o += align16(mf_mask_compact_scratch_bytes(V));
+  s.compact = base + o; o += align_up(mf_mask_compact_scratch_bytes(V), 16);
   s.bytes = o;
   return s;
 }
@@ -299,13 +294,13 @@ inline FilterScratch filter_scratch(void* scratch, long long V, long long T) {
   char* base = static_cast<char*>(scratch);
   FilterScratch s;
   long long o = 0;
-  s.keep_root = reinterpret_cast<unsigned char*>(base + o); o += align16(V);
-  s.vflag = reinterpret_cast<unsigned char*>(base + o); o += align16(V);
-  s.tflag = reinterpret_cast<unsigned char*>(base + o); o += align16(T);
-  s.remap = reinterpret_cast<int*>(base + o); o += align16(4 * V);
+  s.keep_root = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
+  s.vflag = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
+  s.tflag = reinterpret_cast<unsigned char*>(base + o); o += align_up(T, 16);
+  s.remap = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
   s.slot = reinterpret_cast<long long*>(base + o); o += 16;
   const long long cv = mf_mask_compact_scratch_bytes(V), ct = mf_mask_compact_scratch_bytes(T);   // not monotonic in n
-  s.compact = base + o; o += align16(cv > ct ? cv : ct);
+  s.compact = base + o; o += align_up(cv > ct ? cv : ct, 16);
   s.bytes = o;
   return s;
 }
@@ -335,7 +330,7 @@ using namespace mf::cc;
 
 extern "C" int64_t mf_mesh_label_scratch_bytes(int64_t V, int64_t T) {
   const int rc = mesh_shape("mf_mesh_label_scratch_bytes", V, T);
-  return rc != MF_OK ? rc : align16(4 * V);
+  return rc != MF_OK ? rc : align_up(4 * V, 16);
 }
 
 extern "C" int32_t mf_mesh_label(const int64_t* tris, int64_t T, int64_t V, int64_t* labels, int64_t* bad, void* scratch,

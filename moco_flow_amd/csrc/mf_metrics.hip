@@ -149,11 +149,7 @@ inline long long ssim_workgroups(long long B, long long C, long long H, long lon
   return n * B;
 }
 
-inline long long sqerr_blocks(long long n) {
-  const long long per = (long long)kSqerrThreads * kSqerrPerThread;
-  const long long g = (n + per - 1) / per;
-  return g > kSqerrMaxBlocks ? kSqerrMaxBlocks : g;
-}
+inline long long sqerr_blocks(long long n) { return capped_blocks(n, (long long)kSqerrThreads * kSqerrPerThread, kSqerrMaxBlocks); }
 
 }  // namespace mf
 

@@ -16,10 +16,9 @@ namespace mf {
 
 constexpr int kOccThreads = 256;
 
-// the activated density of the render pass (mf_raypass.hpp) and of mf_point_loss_partials
 __device__ __forceinline__ float occ_activate(float s, int act) {
   if (act == MF_ACT_RELU) return s < 0.f ? 0.f : s;                        // NaN stays NaN, as torch.relu leaves it
-  return s > 20.f ? s : log1pf(expf(s));
+  return softplus_torch(s);
 }
 
 struct OccBuildParams {

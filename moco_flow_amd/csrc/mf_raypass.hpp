@@ -63,7 +63,7 @@ MF_D void composite_group(const P& p, int lane, int wave, long long ray0, int nr
       if (p.noise) sg = sg + p.noise[ray * S + ii];                          // :166 (pre-scaled)
       float a;
       if (p.activation == MF_ACT_RELU) a = fmaxf(sg, 0.f);
-      else a = sg > 20.f ? sg : log1pf(expf(sg));                            // nn.Softplus(beta=1, threshold=20)
+      else a = softplus_torch(sg);                                             // nn.Softplus(beta=1, threshold=20)
       float alpha = 1.f - expf(-delta * a);                                  // :170/172
       if (!v) alpha = 0.f;
       const float pt = v ? (1.f - alpha) + 1e-10f : 1.f;                     // :176-177

@@ -7,6 +7,7 @@
 // exact integer count of cdf[k] <= u.
 #include "mf_host.hpp"
 #include "mf_core.hpp"
+#include "mf_scan.hpp"
 
 namespace mf {
 
@@ -172,41 +173,19 @@ __global__ __launch_bounds__(256) void compact_count_kernel(CompactParams p) {
   int c = 0;
   for (int base = 0; base < p.S; base += 64) {
     const int i = base + lane;
-    const bool m = i < p.S && p.alphas[ray * p.S + i] >= 0.01f;                              // :306
-    c += __popcll(__ballot(m));
+    c += wave_popcount(i < p.S && p.alphas[ray * p.S + i] >= 0.01f);                         // :306
   }
   if (lane == 0) p.offs[ray] = c;
 }
 
-// exclusive scan of the per-ray counts by one workgroup; offs[n_rays] = total
+// exclusive scan of the per-ray counts, in place, by one workgroup (mf_scan.hpp); offs[n_rays] = total
 __global__ __launch_bounds__(1024) void compact_scan_kernel(CompactParams p) {
-  __shared__ long long part[1024];
-  __shared__ long long carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (long long base = 0; base < p.n_rays; base += 1024) {
-    const long long i = base + threadIdx.x;
-    const long long v = i < p.n_rays ? p.offs[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-      const long long o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-      __syncthreads();
-      part[threadIdx.x] += o;
-      __syncthreads();
-    }
-    const long long incl = part[threadIdx.x];
-    const long long carry = carry_s;
-    if (i < p.n_rays) p.offs[i] = carry + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + incl;
-    __syncthreads();
-  }
+  long long total[1];
+  scan_totals<1024, 1>(p.offs, p.n_rays, p.offs, total);
   if (threadIdx.x == 0) {
-    const long long total = carry_s;
-    p.offs[p.n_rays] = total;
+    p.offs[p.n_rays] = total[0];
     // no sample passes the threshold: the reference falls back to an all-true mask (:307-308)
-    *p.count = total == 0 ? p.n_rays * (long long)p.S : total;
+    *p.count = total[0] == 0 ? p.n_rays * (long long)p.S : total[0];
   }
 }
 
@@ -219,13 +198,13 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(CompactParams p) {
   for (int base = 0; base < p.S; base += 64) {
     const int i = base + lane;
     const bool m = i < p.S && (all || p.alphas[ray * p.S + i] >= 0.01f);
-    const unsigned long long b = __ballot(m);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    int row;
+    const int before = wave_rank(m, row);
     if (m) {
       if (p.oa) p.oa[o + before] = p.va[ray * p.S + i];
       if (p.ob) p.ob[o + before] = p.vb[ray * p.S + i];
     }
-    o += __popcll(b);
+    o += row;
   }
 }
 

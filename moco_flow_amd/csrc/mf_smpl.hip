@@ -214,11 +214,9 @@ __global__ void smpl_apply_kernel(const float* trans, const long long* ind, long
 
 using namespace mf;
 
-static int64_t smpl_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 extern "C" int64_t mf_smpl_scratch_bytes(int64_t n_verts, int64_t B) {
   if (n_verts < 1 || B < 0) return 0;
-  return smpl_align(B * n_verts * 3 * 4) + smpl_align(B * 72 * 4) + smpl_align(B * 384 * 4) + smpl_align(B * 208 * 4);
+  return align_up(B * n_verts * 3 * 4, 256) + align_up(B * 72 * 4, 256) + align_up(B * 384 * 4, 256) + align_up(B * 208 * 4, 256);
 }
 
 extern "C" int32_t mf_smpl_lbs(const mf_smpl_model* m, const float* pose, int32_t pose_is_rotmat, const float* betas, int64_t B,
@@ -236,9 +234,9 @@ extern "C" int32_t mf_smpl_lbs(const mf_smpl_model* m, const float* pose, int32_
   for (int i = 0; i < 24; ++i) p.parent[i] = m->parent[i];
   p.pose = pose; p.beta = betas; p.verts = verts; p.T = T;
   char* s = static_cast<char*>(scratch);
-  p.v_shaped = reinterpret_cast<float*>(s); s += smpl_align(B * p.V * 3 * 4);
-  p.J = reinterpret_cast<float*>(s); s += smpl_align(B * 72 * 4);
-  p.G = reinterpret_cast<float*>(s); s += smpl_align(B * 384 * 4);
+  p.v_shaped = reinterpret_cast<float*>(s); s += align_up(B * p.V * 3 * 4, 256);
+  p.J = reinterpret_cast<float*>(s); s += align_up(B * 72 * 4, 256);
+  p.G = reinterpret_cast<float*>(s); s += align_up(B * 384 * 4, 256);
   p.lrot = reinterpret_cast<float*>(s);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(smpl_shape_kernel, dim3((p.V * 3 + 255) / 256, (unsigned)B), dim3(256), 0, st, p);

@@ -98,10 +98,7 @@ constexpr int kPtLossThreads = 256;
 constexpr int kPtLossMaxBlocks = 256;
 constexpr int kPtLossSlots = 5;                     // sum |bw - cano|, sum |fw - query|, sum bce, rows taken by L1, outside rows
 
-inline int point_loss_blocks(long long Q) {
-  const long long b = (Q + kPtLossThreads - 1) / kPtLossThreads;
-  return (int)(b < kPtLossMaxBlocks ? b : kPtLossMaxBlocks);
-}
+inline int point_loss_blocks(long long Q) { return (int)capped_blocks(Q, kPtLossThreads, kPtLossMaxBlocks); }
 
 struct PointLossParams {
   long long Q;
@@ -112,9 +109,6 @@ struct PointLossParams {
   // backward
   const float* seeds3; float* g_bw; float* g_fw; float* g_sigma[2];
 };
-
-// torch.nn.Softplus(): beta 1, threshold 20
-__device__ __forceinline__ float softplus_torch(float s) { return s > 20.f ? s : log1pf(expf(s)); }
 
 __global__ __launch_bounds__(kPtLossThreads) void point_loss_partials_kernel(const PointLossParams p) {
   double acc[kPtLossSlots];

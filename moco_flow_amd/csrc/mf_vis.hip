@@ -95,11 +95,7 @@ __global__ __launch_bounds__(kRangeFinishThreads) void depth_range_finish_kernel
   block_minmax_store<kRangeFinishThreads>(lo, hi, out2);
 }
 
-inline long long range_blocks(long long n) {
-  const long long per = (long long)kRangeThreads * kRangePerThread;
-  const long long g = (n + per - 1) / per;
-  return g > kRangeMaxBlocks ? kRangeMaxBlocks : g;
-}
+inline long long range_blocks(long long n) { return capped_blocks(n, (long long)kRangeThreads * kRangePerThread, kRangeMaxBlocks); }
 
 // ---- the colour table in LDS: the bytes and their ToTensor values b / 255 (one fp32 division each) ----
 struct LutLds {
@@ -235,8 +231,6 @@ __global__ __launch_bounds__(kVisThreads) void frame_sheet_kernel(SheetParams p)
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace mf
 
 using namespace mf;
@@ -257,7 +251,7 @@ extern "C" int32_t mf_depth_range(const float* depth, int64_t n, float nan_value
   if (!depth || !scratch) return fail(MF_E_INVALID, "mf_depth_range: null argument (depth or scratch)");
   const long long blocks = range_blocks(n);
   float* parts = static_cast<float*>(scratch);
-  if (aligned(depth, 16))
+  if (is_aligned(depth, 16))
     hipLaunchKernelGGL(depth_range_kernel<true>, dim3((unsigned)blocks), dim3(kRangeThreads), 0, st, depth, (long long)n, nan_value, parts);
   else
     hipLaunchKernelGGL(depth_range_kernel<false>, dim3((unsigned)blocks), dim3(kRangeThreads), 0, st, depth, (long long)n, nan_value, parts);
@@ -274,7 +268,7 @@ extern "C" int32_t mf_depth_colormap(const float* depth, int64_t n, const float*
   const long long blocks = (n + per - 1) / per;
   if (blocks > 0x7fffffffLL) return fail(MF_E_INVALID, "mf_depth_colormap: n=%lld needs more than 2^31 - 1 workgroups", (long long)n);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n % 4 == 0 && aligned(depth, 16) && aligned(out_planar, 16))
+  if (n % 4 == 0 && is_aligned(depth, 16) && is_aligned(out_planar, 16))
     hipLaunchKernelGGL(depth_colormap_kernel<true>, dim3((unsigned)blocks), dim3(kVisThreads), 0, st, depth, (long long)n, range2, nan_value, lut, out_planar);
   else
     hipLaunchKernelGGL(depth_colormap_kernel<false>, dim3((unsigned)blocks), dim3(kVisThreads), 0, st, depth, (long long)n, range2, nan_value, lut, out_planar);
@@ -313,8 +307,8 @@ extern "C" int32_t mf_frame_sheet(const mf_sheet_panel* panels, int32_t n_panels
   p.W = (int32_t)W;
   p.n_panels = n_panels;
   p.n_out = (int32_t)(H * W * n_panels);
-  p.vec_u8 = out_u8 && aligned(out_u8, 4);
-  p.vec_planar = out_planar && p.n_out % 4 == 0 && aligned(out_planar, 16);
+  p.vec_u8 = out_u8 && is_aligned(out_u8, 4);
+  p.vec_planar = out_planar && p.n_out % 4 == 0 && is_aligned(out_planar, 16);
   const int per = kVisThreads * kVisPerThread;
   const unsigned blocks = (unsigned)((p.n_out + (long long)per - 1) / per);
   hipLaunchKernelGGL(frame_sheet_kernel, dim3(blocks), dim3(kVisThreads), 0, static_cast<hipStream_t>(stream), p);

@@ -57,9 +57,11 @@ def test_fixtures_equal_oracle_and_skimage(M, name):
 
 
 @pytest.mark.parametrize("shape,iso,clamp", [((9, 11, 13), 0.0, False), ((7, 5, 64), 0.3, False), ((40, 37, 64), -0.1, False),
-                                             ((33, 29, 31), 0.25, True), ((3, 2, 1027), 0.0, False), ((64, 2, 3), 0.5, True)])
+                                             ((33, 29, 31), 0.25, True), ((3, 2, 1027), 0.0, False), ((64, 2, 3), 0.5, True),
+                                             ((5, 7, 30000), 0.8, False), ((3, 5, 70001), 0.8, False)])
 def test_random_volumes_equal_oracle(M, shape, iso, clamp):
-    """White noise: every case, many blocks (> 1024 points), rows of n2 % 4 == 0 (float4 loads) and not."""
+    """White noise: every case, many blocks (> 1024 points), rows of n2 % 4 == 0 (float4 loads) and not.  The last two hold
+    1026 blocks: the scan workgroup's 1024 threads take a ragged share of the block totals (2 each, threads 0-512 only)."""
     vol = np.random.default_rng(sum(shape)).standard_normal(shape).astype(np.float32)
     v, t, exact = assert_equals_oracle(M, vol, iso, clamp, str(shape))
     assert len(t) > 0
