@@ -50,7 +50,7 @@ extern "C" {
  *     (+ mf_occ_build_scratch_bytes), mf_ray_clip; mf_mesh_label, mf_mesh_table_count / mf_mesh_table_emit, mf_mesh_filter_plan /
  *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows; mf_project_vertices, mf_rasterize (+ mf_raster_scratch_bytes),
  *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade; mf_resize_u8 (+ mf_resize_u8_scratch_bytes), mf_composite_rows,
- *     mf_background_plate */
+ *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -891,6 +891,40 @@ int32_t mf_occ_build(const float* sigma, int64_t nx, int64_t ny, int64_t nz, int
 int32_t mf_ray_clip(const float* rays, int64_t ray_stride, int64_t n_rays, const uint32_t* bits, int32_t gx, int32_t gy,
                     int32_t gz, const float* lo /* host */, const float* hi /* host */, const float* inv_cell /* host */, float dt,
                     float* t_first, float* t_last, uint8_t* hit, void* stream);
+
+/* ---- sparse lattice queries: sigma only where a bit grid is occupied.  visualize_mesh (trainer_moco_flow.py:490-538,
+ * trainer_nerf.py:200-259) evaluates every point of its lattice, and so does the lattice behind mf_occ_build; a body fills about a
+ * tenth of its box.  The lattice is (n0, n1, n2) points, axis 2 fastest, given by three ascending fp32 coordinate tables;
+ * world_of_axis (host int32[3], a permutation of (0, 1, 2)) names the world coordinate -- and so the grid axis -- that volume
+ * axis a carries ((1, 0, 2) for visualize_mesh's 'xy' meshgrid).  A BRICK is 8 x 8 x 8 lattice points: brick (b0, b1, b2) owns
+ * the indices [8 b_a, min(8 b_a + 7, n_a - 1)] of every axis, nb_a = ceil(n_a / 8), linear brick index (b0 nb1 + b1) nb2 + b2.
+ * Each side in [1, 2^31) and fewer than 2^31 bricks, else MF_E_INVALID.  Integer work and copies only; no atomics, every output
+ * word has one writer, bit-identical from run to run.  No entry allocates or synchronises. ----
+ *
+ * mf_lattice_select (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259): bits / (gx, gy, gz) as mf_occ_build writes
+ * them (padding bits zero); range_a (device int32 (nb_a, 2)): per brick coordinate of volume axis a the inclusive first and last
+ * grid cell, along grid axis world_of_axis[a], that the brick's grown index range touches, or an empty range (first > last) --
+ * built by the caller (moco_flow_amd/points.py restates mf_ray_clip's cell rule on the host); a range is clipped to the grid
+ * before it is used.  A brick is active iff its three ranges are non-empty and some bit of the cell box they span is set: one
+ * lane per brick ORs the box's words.  slot (nb0 nb1 nb2) int32 = the brick's rank among the active ones in ascending linear
+ * index, or -1; brick_ids int32, room for nb0 nb1 nb2 entries, the first K written, ascending; count (device int64[1]) = K.
+ * Ranks through the ordered scan (mf_scan.hpp); scratch: mf_lattice_select_scratch_bytes bytes. */
+int64_t mf_lattice_select_scratch_bytes(int64_t n0, int64_t n1, int64_t n2);
+int32_t mf_lattice_select(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, const int32_t* range0, const int32_t* range1,
+                          const int32_t* range2, int64_t n0, int64_t n1, int64_t n2, const int32_t* world_of_axis /* host */,
+                          int32_t* slot, int32_t* brick_ids, int64_t* count, void* scratch, void* stream);
+/* mf_lattice_points (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259): brick_ids (K) int32 -> points (K 512, 3)
+ * fp32, the input of mf_points_sigma: brick r has rows [512 r, 512 r + 512), local order (l0, l1, l2) with l2 fastest, and
+ * column world_of_axis[a] of a row is axis_a[min(8 b_a + l_a, n_a - 1)] -- a partial brick repeats its last point (those rows are
+ * evaluated and never stored).  An id outside [0, nb0 nb1 nb2) is clamped, never dereferenced.  K = 0 launches nothing. */
+int32_t mf_lattice_points(const int32_t* brick_ids, int64_t K, const float* axis0, const float* axis1, const float* axis2, int64_t n0,
+                          int64_t n1, int64_t n2, const int32_t* world_of_axis /* host */, float* points, void* stream);
+/* mf_lattice_scatter (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259): sigma (K 512) fp32 in the row order of
+ * mf_lattice_points, slot as mf_lattice_select wrote it -> volume (n0, n1, n2) fp32: point (i0, i1, i2) = sigma[512 s + (i0 % 8)
+ * 64 + (i1 % 8) 8 + i2 % 8] with s the slot of its brick, or `fill` where s is -1 (or not below K).  ONE pass writes every point
+ * exactly once: no memset, no second writer.  K = 0 (sigma may be NULL) fills the volume. */
+int32_t mf_lattice_scatter(const float* sigma, const int32_t* slot, int64_t K, int64_t n0, int64_t n1, int64_t n2, float fill,
+                           float* volume, void* stream);
 
 /* ---- triangle rasterizer (moco_flow_amd/csrc/mf_raster.hip, which writes out the fill rule and every operation order): the
  * pictures the reference draws with pyrender -- the stage-1 views of the posed SMPL mesh and the SMPL overlay,

@@ -19,7 +19,7 @@ from .factory import get_loss, get_model
 from .losses import MSELoss
 from .nerf import NeRF
 from .nof import NoF
-from .points import query_radiance, query_sigma
+from .points import query_radiance, query_sigma, query_sigma_lattice
 from .mesh import (export_obj, export_ply, extract_colored_mesh, extract_mesh, filter_components, marching_cubes, mesh_components,
                    vertex_normals)
 from . import metrics
@@ -44,6 +44,6 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "marching_cubes", "mesh_components", "filter_components", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
            "vis", "visualize_depth", "decode_results", "frame_sheet", "write_png", "batch", "FrameRays",
            "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
-           "occupancy", "OccupancyGrid",
+           "occupancy", "OccupancyGrid", "query_sigma_lattice",
            "raster", "project_vertices", "rasterize", "interpolate", "render_mesh", "smpl_views",
            "frames", "resize", "composite", "to_rows", "background_plate"]

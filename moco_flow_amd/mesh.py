@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .points import query_radiance, query_sigma
+from .points import query_radiance, query_sigma, query_sigma_lattice
 
 
 def marching_cubes(volume, isovalue, clamp_zero=False):
@@ -234,21 +234,39 @@ def lattice(N_grid, device):
                         ax.view(1, 1, N).expand(N, N, N)], -1).reshape(-1, 3)
 
 
+def _sparse_volume(N_grid, nerf, nerf_embedding_xyz, occupancy, margin, bw_nof, nof_embeddings, ind, precision):
+    """``lattice``'s sigma volume through ``query_sigma_lattice``: the same coordinates, volume axis 0 carrying y and axis 1
+    carrying x ('xy' indexing), 0 in the inactive bricks."""
+    ax = np.linspace(-1.5, 1.5, N_grid).astype(np.float32)
+    return query_sigma_lattice((ax, ax, ax), nerf, nerf_embedding_xyz, occupancy, world_of_axis=(1, 0, 2), margin=margin,
+                               fill=0.0, bw_nof=bw_nof, nof_embeddings=nof_embeddings, ind=ind, precision=precision)
+
+
 def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                 precision=None, keep_largest=None, min_triangles=None):
+                 precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=1):
     """visualize_mesh (trainer_moco_flow.py:490-538) up to the file: raw sigma of the NeRF on the N_grid^3 lattice over
     [-1.5, 1.5]^3 (query_sigma; with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow, ``ind`` =
     frame_idx * 2 / num_frames - 1), the isosurface of max(sigma, 0) at ``sigma_threshold``, then the reference's
     post-processing: vertex columns 0 and 1 swapped, triangle columns 1 and 2 swapped, vertices / N_grid * 3 - 1.5 (the
     reference divides by N_grid, not N_grid - 1).  Returns (verts (V, 3) float32, tris (T, 3) int64) on the NeRF's device;
     ``export_obj`` writes them.  ``keep_largest`` / ``min_triangles`` (not in the reference): filter_components with these
-    on the raw isosurface, before the post-processing; both None leaves the path as it was."""
+    on the raw isosurface, before the post-processing; both None leaves the path as it was.
+
+    ``occupancy`` (an ``OccupancyGrid``, not in the reference; None leaves the path as it was): sigma is evaluated only in
+    the lattice bricks the grid marks, ``margin`` lattice points around each (``_sparse_volume``, ``query_sigma_lattice``),
+    and is 0 -- the empty side under the clamp -- everywhere else; no lattice tensor is built, and the call reads one more
+    count from the device.  The mesh equals the dense one, bit for bit, exactly when every cell that crosses the threshold
+    has its eight corners in active bricks.  A grid from a coarse pass can miss a thin part: that belongs to the grid's
+    ``dilate`` and to a coarse threshold below ``sigma_threshold``, which nobody has validated on a trained checkpoint."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_mesh")
-    xyz = lattice(N_grid, dev)
     with torch.no_grad():
-        sigma = query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof, nof_embeddings, ind, precision=precision)
-        del xyz
+        if occupancy is None:
+            xyz = lattice(N_grid, dev)
+            sigma = query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof, nof_embeddings, ind, precision=precision)
+            del xyz
+        else:
+            sigma = _sparse_volume(N_grid, nerf, nerf_embedding_xyz, occupancy, margin, bw_nof, nof_embeddings, ind, precision)
         verts, tris = marching_cubes(sigma.view(N_grid, N_grid, N_grid), sigma_threshold, clamp_zero=True)
         if keep_largest is not None or min_triangles is not None:
             verts, tris = filter_components(verts, tris, keep_largest, min_triangles)
@@ -258,7 +276,7 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
 
 
 def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                         precision=None, keep_largest=None, min_triangles=None):
+                         precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=2):
     """extract_mesh with what a coloured mesh needs: (verts (V, 3), tris (T, 3), normals (V, 3), colors (V, 3)).
 
     verts / tris are extract_mesh's for the same arguments (``nerf_embeddings`` = [xyz, ind | None, dir | None] as
@@ -268,13 +286,18 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
     through the same NoF / ``ind``; a "dir" NeRF is looked at straight on, view_dirs = -normal ((0, 0, -1) where the
     normal is zero).  An empty mesh gives four empty tensors.  ``keep_largest`` / ``min_triangles``: as in extract_mesh;
     the filter runs before the radiance query, with the normals as a vertex attribute, so a dropped vertex is never
-    queried."""
+    queried.  ``occupancy`` / ``margin``: as in extract_mesh; the default margin is 2 because the normals' central
+    differences read one lattice point beyond a crossing cell's corners -- normals equal the dense ones exactly when those
+    neighbours lie in active bricks as well."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_colored_mesh")
-    xyz = lattice(N_grid, dev)
     with torch.no_grad():
-        sigma = query_sigma(xyz, nerf, nerf_embeddings[0], bw_nof, nof_embeddings, ind, precision=precision)
-        del xyz
+        if occupancy is None:
+            xyz = lattice(N_grid, dev)
+            sigma = query_sigma(xyz, nerf, nerf_embeddings[0], bw_nof, nof_embeddings, ind, precision=precision)
+            del xyz
+        else:
+            sigma = _sparse_volume(N_grid, nerf, nerf_embeddings[0], occupancy, margin, bw_nof, nof_embeddings, ind, precision)
         volume = sigma.view(N_grid, N_grid, N_grid)
         raw, tris = marching_cubes(volume, sigma_threshold, clamp_zero=True)
         normals = vertex_normals(volume, raw, clamp_zero=True)[:, [1, 0, 2]].contiguous()

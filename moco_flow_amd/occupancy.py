@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .points import query_sigma
+from .points import query_sigma, query_sigma_lattice
 
 __all__ = ["OccupancyGrid"]
 
@@ -74,20 +74,26 @@ class OccupancyGrid:
         return cls(bits, (nx - 1, ny - 1, nz - 1), lo, hi, count)
 
     @staticmethod
-    def lattice(N_grid, aabb, device):
-        """``from_field``'s query points (N, 3) and their (Nx, Ny, Nz): np.linspace(lo_a, hi_a, N_a) in float64 cast to fp32,
-        x slowest, z fastest -- NOT ``mesh.lattice``'s 'xy' order."""
+    def lattice_axes(N_grid, aabb):
+        """The lattice's coordinates per axis, three fp32 numpy arrays, and its (Nx, Ny, Nz)."""
         n = (int(N_grid),) * 3 if np.isscalar(N_grid) else tuple(int(v) for v in N_grid)
         box = np.asarray(aabb, dtype=np.float64)
         if box.shape != (2, 3) or len(n) != 3:
             raise RuntimeError(f"OccupancyGrid: aabb must be (2, 3) and N_grid an int or a 3-tuple, got {box.shape} and {N_grid!r}")
-        ax = [torch.from_numpy(np.linspace(box[0, a], box[1, a], n[a]).astype(np.float32)).to(device) for a in range(3)]
+        return [np.linspace(box[0, a], box[1, a], n[a]).astype(np.float32) for a in range(3)], n
+
+    @staticmethod
+    def lattice(N_grid, aabb, device):
+        """``from_field``'s query points (N, 3) and their (Nx, Ny, Nz): np.linspace(lo_a, hi_a, N_a) in float64 cast to fp32,
+        x slowest, z fastest -- NOT ``mesh.lattice``'s 'xy' order."""
+        axes, n = OccupancyGrid.lattice_axes(N_grid, aabb)
+        ax = [torch.from_numpy(x).to(device) for x in axes]
         pts = torch.stack([ax[0].view(-1, 1, 1).expand(*n), ax[1].view(1, -1, 1).expand(*n), ax[2].view(1, 1, -1).expand(*n)], -1)
         return pts.reshape(-1, 3), n
 
     @classmethod
     def from_field(cls, nerf, nerf_embedding_xyz, aabb, N_grid=128, sigma_threshold=1.0, activate_type="softplus", dilate=1,
-                   bw_nof=None, nof_embeddings=None, ind=None, precision=None):
+                   bw_nof=None, nof_embeddings=None, ind=None, precision=None, within=None):
         """The grid of the networks over ``aabb`` ((2, 3): min and max corner, as ``rescale_AABB`` returns it): one
         ``query_sigma`` call on the lattice -- with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow at
         image index ``ind``, in ``precision`` -- then ``from_sigma``; bit-identical to those two steps by hand.
@@ -98,9 +104,22 @@ class OccupancyGrid:
 
         ``sigma_threshold`` = 1.0 on the ACTIVATED density is a starting value: nobody has validated it on a trained
         checkpoint.  Too high a threshold hides thin or faint parts of the body; check a few frames against a render
-        without the grid before relying on it."""
+        without the grid before relying on it.
+
+        ``within`` (None leaves the path as it was): a coarser ``OccupancyGrid`` over the same box.  The lattice is then
+        queried only in the bricks of 8 x 8 x 8 points that ``within`` marks, one lattice point of margin around each
+        (``query_sigma_lattice`` with fill = -inf, which no activation lifts over a threshold >= 0), and ``from_sigma`` runs
+        on that volume -- bit-identical to those two steps by hand.  This ADDS ONE HOST SYNCHRONISATION, the read of the
+        active-brick count, which the dense path does not have.  What ``within`` does not mark stays empty here: a part it
+        missed is missed again, whatever ``sigma_threshold`` is."""
         dev = next(nerf.parameters()).device
         L.require_gpu(next(nerf.parameters()), "OccupancyGrid.from_field")
+        if within is not None:
+            axes, _ = cls.lattice_axes(N_grid, aabb)
+            box = np.asarray(aabb, dtype=np.float64)
+            sigma = query_sigma_lattice(axes, nerf, nerf_embedding_xyz, within, fill=float("-inf"), bw_nof=bw_nof,
+                                        nof_embeddings=nof_embeddings, ind=ind, precision=precision)
+            return cls.from_sigma(sigma, box[0], box[1], sigma_threshold, activate_type, dilate)
         xyz, n = cls.lattice(N_grid, aabb, dev)
         box = np.asarray(aabb, dtype=np.float64)
         with torch.no_grad():

@@ -18,8 +18,9 @@ bytes: 24 B per triangle read + 4 B per vertex of labels (the labelling), the co
 per kept triangle (the filter), each over its time as a fraction of the 4.69 TB/s device-to-device copy rate -- information
 only: the accesses to the parents are random and no share of a peak is claimed.  The host path these replace, in the same
 process where scipy is importable: the device -> host copy of the mesh, scipy.sparse.csgraph.connected_components, a numpy
-re-index to the largest component (once each; --no-host skips it).  Usage: time_mesh.py [--no-host] [--components-only]
-[N ...]  (default 256 512)"""
+re-index to the largest component (once each; --no-host skips it).  --sparse: only extract_mesh end to end, without and behind
+an occupancy grid (query_sigma_lattice; the timings beside tools/time_lattice.py --sparse).  Usage: time_mesh.py [--no-host]
+[--components-only] [--sparse] [N ...]  (default 256 512)"""
 import os
 import statistics
 import sys
@@ -117,6 +118,30 @@ def components_leg(what, N, verts, tris, mc_ms, sigma_ms=None):
         host_path(verts, tris)
 
 
+if "--sparse" in sys.argv:
+    # extract_mesh end to end without and behind a grid: tools/time_occupancy.py's capsule scaled to the mesh lattice's box
+    # [-1.5, 1.5]^3 (about 10 % of it), as a 128^3 grid dilated by 1.  The random NeRF crosses the threshold wherever it is
+    # evaluated, so the sparse mesh is the part of the dense one inside the active bricks: V and T are printed per row.
+    ax = [torch.linspace(-1, 1, 128, device=dev, dtype=torch.float64) for _ in range(3)]
+    X, Y, Z = torch.meshgrid(*ax, indexing="ij")
+    dist = torch.sqrt(X ** 2 + (Y.abs() - 0.6).clamp_min(0) ** 2 + Z ** 2)
+    grid = M.OccupancyGrid.from_sigma(torch.where(dist <= 0.38, 5.0, -5.0).float(), (-1.5,) * 3, (1.5,) * 3, 1.0, "softplus", 1)
+    del X, Y, Z, dist
+    print(f"extract_mesh end to end, dense and behind the capsule grid ({grid.occupied_fraction():.3f} of its 127^3 cells occupied)")
+    for N in Ns:
+        for prec in ("f32", "bf16"):
+            kw = dict(N_grid=N, sigma_threshold=10, precision=prec)
+            ms, out = timeit(lambda: M.extract_mesh(nerf, emb, **kw), warm=1, n=3)
+            row(f"extract_mesh {prec}", N, ms, out)
+            ms_s, out = timeit(lambda: M.extract_mesh(nerf, emb, occupancy=grid, **kw), warm=1, n=3)
+            row(f"extract_mesh {prec}, occupancy=grid", N, ms_s, out)
+            a = np.linspace(-1.5, 1.5, N).astype(np.float32)
+            _, (K, bricks) = M.query_sigma_lattice((a, a, a), nerf, emb, grid, world_of_axis=(1, 0, 2), fill=0.0, precision=prec,
+                                                   return_stats=True)
+            print(f"    {ms_s / ms:.3f} x; active bricks {K} of {bricks} = {K / bricks:.3f}", flush=True)
+            del out
+            torch.cuda.empty_cache()
+    sys.exit(0)
 print("marching_cubes (clamp_zero, threshold 10) on the f32 sigma lattice; the components leg on each mesh")
 for N in Ns:
     with torch.no_grad():
