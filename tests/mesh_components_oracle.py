@@ -45,6 +45,63 @@ def components(tris, V):
     return (lab,) + table(tris, lab)
 
 
+def pattern_mesh(pattern):
+    """(tris, V) of the mesh a pattern spells: component c owns the vertices v with pattern[v] == c (at least three) and is a
+    strip over them in ascending order; the rows are in the order of their column-0 vertex.  In element order the vertices'
+    labels are the pattern itself and the triangles' are the pattern without the last two vertices of every component."""
+    pattern = np.asarray(pattern, np.int64)
+    rows = []
+    for c in np.unique(pattern):
+        v = np.flatnonzero(pattern == c)
+        assert len(v) >= 3, c
+        rows.append(np.stack([v[:-2], v[1:-1], v[2:]], 1))
+    tris = np.concatenate(rows)
+    return tris[np.argsort(tris[:, 0], kind="stable")], len(pattern)
+
+
+BRANCHES = ("carry_add", "take_flush", "take_empty", "leader_add_holding")
+
+
+def wave_count_replay(keys, threads, max_blocks):
+    """The decisions of wave_count (csrc/mf_mesh_components.hip) for ``keys`` in element order -- the labels of the
+    triangles' column-0 vertices, or of the vertices -- under a grid of min(ceil(N / threads), max_blocks) workgroups of
+    ``threads`` threads in waves of 64: a wave holds one (key, count) pair across the trips of its grid-stride loop, and per
+    trip visits its distinct keys in the order of their first lane.  Returns (adds, later): ``adds[k]`` the sum of everything
+    added to counter k, the final flush included; ``later[b]`` how often branch b of BRANCHES was taken on a trip after the
+    first: the held key seen again (its count goes to the pair), a new majority taking a non-empty pair (which is flushed),
+    a key taking an empty pair, and a minority key added by its leader while another key is held."""
+    keys = np.asarray(keys, np.int64).reshape(-1).tolist()
+    N = len(keys)
+    blocks = min(-(-N // threads), max_blocks)
+    adds, later = {}, dict.fromkeys(BRANCHES, 0)
+
+    def add(k, c):
+        adds[k] = adds.get(k, 0) + c
+
+    for first in range(0, blocks * threads, 64):                    # the wave's first element on its first trip
+        held, n = 0, 0
+        for trip, start in enumerate(range(first, N, blocks * threads)):
+            seen = {}                                               # insertion order: the order of the leaders
+            for k in keys[start:start + 64]:
+                seen[k] = seen.get(k, 0) + 1
+            for k, c in seen.items():
+                if n and k == held:
+                    n += c
+                    branch = "carry_add"
+                elif c > 32 or not n:
+                    branch = "take_flush" if n else "take_empty"
+                    if n:
+                        add(held, n)
+                    held, n = k, c
+                else:
+                    add(k, c)
+                    branch = "leader_add_holding"
+                later[branch] += trip > 0
+        if n:
+            add(held, n)
+    return adds, later
+
+
 def ranking(ids, tri_counts):
     """Positions into the table in rank order: triangle count descending, then label ascending."""
     return np.lexsort((ids, -tri_counts))

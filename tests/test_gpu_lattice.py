@@ -2,8 +2,13 @@
 -- integer decisions on host-built tables and copies, so there is no tolerance --, query_sigma_lattice against the dense
 query_sigma on the same lattice (bit-identical in the active bricks: every point-query kernel computes a sample's column
 independently of its place in the batch; `fill` everywhere else), and the callers: extract_mesh / extract_colored_mesh behind a
-grid and OccupancyGrid.from_field(within=...) against their dense runs."""
+grid and OccupancyGrid.from_field(within=...) against their dense runs.  The shapes of the "past" tests are derived from the
+launch constants of csrc/mf_lattice.hip: select where the scan over the workgroups' counts crosses a wave and gives a thread
+several entries (up to the 512^3 lattice), scatter past one trip of either loop, one query with all of them at once."""
 import ctypes
+import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -18,6 +23,18 @@ pytestmark = pytest.mark.gpu
 
 IND_SCALAR = -0.25
 UNTOUCHED = -7
+
+_SRC = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "moco_flow_amd", "csrc", "mf_lattice.hip")).read()
+
+
+def _const(name):
+    """An integer launch constant of csrc/mf_lattice.hip, `N` or `1 << N`."""
+    m = re.search(r"\bconstexpr int %s = (?:(\d+) << )?(\d+);" % name, _SRC)
+    return int(m.group(2)) if m.group(1) is None else int(m.group(1)) << int(m.group(2))
+
+
+LAT_THREADS = _const("kLatThreads")                                     # bricks per workgroup of select, lanes per row of scatter
+SCATTER_MAX_BLOCKS = _const("kLatScatterMaxBlocks")                     # rows of the volume per trip of scatter
 
 
 @pytest.fixture(scope="module")
@@ -66,11 +83,14 @@ def _select(M, grid, axes, woa, margin):
     return slot.cpu().numpy(), ids.cpu().numpy(), int(count.item())
 
 
-def _check_select(M, dense, lo, hi, axes, woa, margin, what):
-    grid = _grid(M, dense, lo, hi)
+def _oracle_select(dense, lo, hi, axes, woa, margin, select=LO.select):
     lo32, hi32, inv, _ = O.grid_constants(dense.shape, lo, hi, 0.5)
-    n = [len(a) for a in axes]
-    want_slot, want_ids, want_K = LO.select(dense, LO.range_tables(axes, margin, dense.shape, lo32, hi32, inv, woa), n, woa)
+    return select(dense, LO.range_tables(axes, margin, dense.shape, lo32, hi32, inv, woa), [len(a) for a in axes], woa)
+
+
+def _check_select(M, dense, lo, hi, axes, woa, margin, what, want=None):
+    grid = _grid(M, dense, lo, hi)
+    want_slot, want_ids, want_K = _oracle_select(dense, lo, hi, axes, woa, margin) if want is None else want
     slot, ids, K = _select(M, grid, axes, woa, margin)
     assert K == want_K, (what, K, want_K)
     assert np.array_equal(slot, want_slot), what
@@ -137,6 +157,69 @@ def test_select_under_a_grid_finer_than_the_lattice(M):
     assert K == 1
 
 
+# ------------------------------------------------------------------------------------------------ select: the scan's tiers
+# lat_scan_kernel scans one count per workgroup of LAT_THREADS bricks with LAT_THREADS threads (scan_totals<kLatThreads, 1>,
+# csrc/mf_scan.hpp): thread t owns `per` = ceil(counts / LAT_THREADS) entries from t * per on.  The shapes follow from the
+# constant; each case asserts the tier it was built for, so another constant fails the case and does not empty it.
+T_ = LAT_THREADS
+SELECT_TIERS = {
+    # name: (lattice, thin, counts, per); thin: the short axis covers one or two cells and not the whole grid
+    "wave": ((4 * T_ + 1, 4 * T_ + 1, 1), False, None, 1),             # more counts than a wave has lanes: the waves-in-front term
+    "full": ((8 * T_, 8 * T_, 8), True, T_, 1),                         # every scan thread holds exactly one count
+    "odd": ((8 * T_ - 7, 8 * T_ + 1, 3), True, T_ + 1, 2),              # two per thread, the last owner holds a single one
+    "idle": ((8 * T_ + 1, 8 * T_ + 1, 1), False, None, 2),              # two per thread, the upper threads own nothing
+    "512": ((2 * T_, 2 * T_, 2 * T_), False, 4 * T_, 4),                # the 512^3 lattice of a fine extraction
+}
+SELECT_WOA = ((0, 1, 2), (2, 0, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def select_tier_case(name, woa, margin):
+    """(dense, lo, hi, axes, the oracle's (slot, brick_ids, K)) of one tier, with the properties the case is for asserted on
+    the ORACLE's result: nothing here has seen the device."""
+    n, thin, counts, per = SELECT_TIERS[name]
+    dense = np.random.default_rng(40).random((40, 40, 40)) < 0.2
+    lo, hi = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
+    axes = _axes(n, (-1.0, -1.0, -0.02 if thin else -1.0), (1.0, 1.0, 0.02 if thin else 1.0))
+    bricks = int(np.prod(LO.n_bricks(n)))
+    nblocks = -(-bricks // LAT_THREADS)
+    assert nblocks > 64 and -(-nblocks // LAT_THREADS) == per and (counts is None or nblocks == counts), (name, bricks, nblocks)
+    owners = -(-nblocks // per)                                         # scan threads with at least one entry
+    if name == "wave":
+        assert nblocks <= LAT_THREADS
+    if name == "full":
+        assert bricks == LAT_THREADS * LAT_THREADS and owners == LAT_THREADS
+    if name == "odd":
+        assert nblocks % 2 == 1 and bricks % LAT_THREADS == 0
+    if name == "idle":
+        assert owners < LAT_THREADS - 64 and bricks % LAT_THREADS != 0  # a whole wave of idle threads, a ragged last workgroup
+    if name == "512":
+        assert n == (512, 512, 512) and owners == LAT_THREADS
+    slot, ids, K = want = _oracle_select(dense, lo, hi, axes, woa, margin, LO.select_fast)
+    on = np.zeros(nblocks * LAT_THREADS, dtype=np.int64)
+    on[:bricks] = slot >= 0
+    per_group = on.reshape(nblocks, LAT_THREADS).sum(1)
+    assert per_group.sum() == K and len(slot) == bricks
+    assert 0.1 < K / bricks < 0.9, (name, woa, margin, K / bricks)
+    assert (per_group > 0).sum() >= 0.75 * nblocks, (name, woa, margin)
+    assert len(np.unique(per_group)) >= 16, (name, woa, margin)
+    return dense, lo, hi, axes, want
+
+
+@pytest.mark.parametrize("name", list(SELECT_TIERS))
+def test_select_past_one_count_per_lane_wave_and_thread(M, name):
+    """slot, brick_ids and K where the scan over the workgroups' counts crosses a wave (more than 64 counts), fills every
+    thread (LAT_THREADS counts), gives a thread several entries (more than LAT_THREADS: an odd number of counts, idle upper
+    threads) and at the 512^3 lattice's 1024 counts, under two world_of_axis and margins 0 and 1.  The flat lattices cost
+    nothing: select reads the per-axis tables only.  The oracle is LO.select_fast, which tests/test_lattice_cpu.py holds to
+    LO.select."""
+    for woa in SELECT_WOA:
+        for margin in (0, 1):
+            dense, lo, hi, axes, want = select_tier_case(name, woa, margin)
+            K, nbk = _check_select(M, dense, lo, hi, axes, woa, margin, (name, woa, margin), want=want)
+            print(f"\nselect tier {name} {woa} margin {margin}: {K} of {nbk} bricks")
+
+
 # ------------------------------------------------------------------------------------------------ points and scatter
 def _points(M, ids, axes, woa):
     L = M._lib
@@ -158,8 +241,7 @@ def _scatter(M, sigma, slot, K, n, fill):
     return vol.cpu().numpy()
 
 
-@pytest.mark.parametrize("n", [(19, 13, 21), (9, 2, 65), (8, 16, 8)])
-def test_points_and_scatter_equal_the_oracle_bit_for_bit(M, n):
+def _points_and_scatter(M, n, woas):
     rng = np.random.default_rng(sum(n) + 1)
     nb = LO.n_bricks(n)
     on = rng.random(nb[0] * nb[1] * nb[2]) < 0.5
@@ -169,17 +251,46 @@ def test_points_and_scatter_equal_the_oracle_bit_for_bit(M, n):
     slot = np.where(on, np.cumsum(on) - 1, -1).astype(np.int32)
     K = len(ids)
     axes = [np.sort(rng.normal(size=v)).astype(np.float32) for v in n]   # uneven spacing
-    for woa in ((0, 1, 2), (1, 0, 2), (2, 1, 0)):
+    for woa in woas:
         got, want = _points(M, ids, axes, woa), LO.points(ids, axes, woa)
         assert got.shape == want.shape and np.array_equal(got.view(np.int32), want.view(np.int32)), woa
     sigma = rng.normal(size=K * 512).astype(np.float32)
     sigma[::97] = np.nan
     sigma[5::101] = -0.0
+    mask = LO.active_mask(slot, n)
     for fill in (float("-inf"), 0.0):
         got, want = _scatter(M, sigma, slot, K, n, fill), LO.scatter(sigma, slot, n, np.float32(fill))
         assert np.array_equal(got.view(np.int32), want.view(np.int32)), fill
-        mask = LO.active_mask(slot, n)
         assert 0 < mask.sum() < mask.size and (got[~mask].view(np.int32) == np.float32(fill).view(np.int32)).all()
+    return K
+
+
+@pytest.mark.parametrize("n", [(19, 13, 21), (9, 2, 65), (8, 16, 8)])
+def test_points_and_scatter_equal_the_oracle_bit_for_bit(M, n):
+    _points_and_scatter(M, n, ((0, 1, 2), (1, 0, 2), (2, 1, 0)))
+
+
+# lat_scatter_kernel: one workgroup per (i0, i1) row and trip, at most SCATTER_MAX_BLOCKS workgroups, LAT_THREADS lanes along i2
+SCATTER_LONG = (9, 10, 2 * LAT_THREADS + 91)                            # three trips along i2, the last ragged, on a few rows
+SCATTER_ROWS = (SCATTER_MAX_BLOCKS // 258 + 3, 258, 9)                  # a second trip over the rows for some workgroups only
+SCATTER_BOTH = (SCATTER_MAX_BLOCKS // 250 + 3, 250, LAT_THREADS + 3)
+
+
+@pytest.mark.parametrize("n", [SCATTER_LONG, SCATTER_ROWS, SCATTER_BOTH], ids=["long_rows", "many_rows", "both"])
+def test_points_and_scatter_past_their_first_trips(M, n):
+    """The same check where a row of the volume is longer than the workgroup (a second and third trip of the i2 loop), where
+    the volume has more rows than the grid has workgroups (a second trip of the row loop, taken by the first workgroups
+    only), and both at once; every side ends in a partial brick."""
+    rows, trips2 = n[0] * n[1], -(-n[2] // LAT_THREADS)
+    assert all(v % 8 for v in n), n
+    if n == SCATTER_LONG:
+        assert trips2 == 3 and n[2] % LAT_THREADS and rows < SCATTER_MAX_BLOCKS
+    if n == SCATTER_ROWS:
+        assert SCATTER_MAX_BLOCKS < rows < 2 * SCATTER_MAX_BLOCKS and trips2 == 1
+    if n == SCATTER_BOTH:
+        assert SCATTER_MAX_BLOCKS < rows < 2 * SCATTER_MAX_BLOCKS and trips2 == 2
+    K = _points_and_scatter(M, n, ((2, 0, 1),))
+    assert K > 0.4 * np.prod(LO.n_bricks(n))
 
 
 def test_a_launch_with_no_active_brick(M):
@@ -246,6 +357,39 @@ def test_query_sigma_lattice_equals_the_dense_query_in_active_bricks(M, prec, no
     cuda_axes = [_dev(a) for a in axes]                                 # device tensors as axes: the same volume
     assert torch.equal(_bits(M.query_sigma_lattice(cuda_axes, nerfs[0], embs[0], grid, world_of_axis=woa, fill=0.0, precision=prec, **flow)),
                        _bits(vol))
+
+
+FLAT = (8 * LAT_THREADS + 1, 8 * LAT_THREADS + 1, 1)                    # SELECT_TIERS["idle"]: two counts per scan thread
+
+
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
+def test_query_sigma_lattice_past_65536_bricks(M, prec):
+    """The documented guarantee on a flat lattice where select scans more counts than it has threads and scatter takes a second
+    trip over the rows: K and the brick total are the oracle's; the volume is, bit for bit, query_sigma on the oracle's
+    points of the active bricks laid out by the oracle's scatter -- a point's sigma does not depend on its place in the batch
+    --, which also says that every other point is `fill`."""
+    woa, fill = (0, 1, 2), float("-inf")
+    case = dict(n=8, S=8, M=0, extra="dir", regime="dense", nof="none")
+    embs, nerfs, _ = build_case(M, case, 0, device="cuda")
+    grid, dense = _ball_grid(M)
+    axes = _axes(FLAT, (-1.0, -1.0, -0.4), (1.0, 1.0, -0.4))             # the one z is the ball centre's
+    bricks = int(np.prod(LO.n_bricks(FLAT)))
+    assert bricks > LAT_THREADS * LAT_THREADS and FLAT[0] * FLAT[1] > SCATTER_MAX_BLOCKS
+    slot, ids, K = _oracle_select(dense, grid.lo, grid.hi, axes, woa, 1, LO.select_fast)
+    assert 0.02 * bricks < K < 0.5 * bricks
+    with torch.no_grad():
+        vol, stats = M.query_sigma_lattice(axes, nerfs[0], embs[0], grid, world_of_axis=woa, margin=1, fill=fill, precision=prec,
+                                           return_stats=True)
+        rows = M.query_sigma(_dev(LO.points(ids, axes, woa)), nerfs[0], embs[0], precision=prec)
+    assert stats == (K, bricks)
+    assert tuple(vol.shape) == FLAT and vol.dtype == torch.float32 and vol.is_contiguous()
+    want = LO.scatter(rows.cpu().numpy(), slot, FLAT, np.float32(fill))
+    mask = LO.active_mask(slot, FLAT)
+    got = vol.cpu().numpy()
+    diff = int((got.view(np.int32) != want.view(np.int32)).sum())
+    print(f"\nquery_sigma_lattice {prec} on {FLAT}: {K} of {bricks} bricks, {int(mask.sum())} active points, {diff} words differ")
+    assert diff == 0
+    assert np.isfinite(got[mask]).all() and np.isneginf(got[~mask]).all() and 0 < mask.sum() < mask.size
 
 
 # ------------------------------------------------------------------------------------------------ the callers

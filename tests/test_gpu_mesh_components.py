@@ -3,9 +3,12 @@ mf_gather_rows) against the numpy oracle of their contract (tests/mesh_component
 marching-cubes meshes of the fixtures, white-noise volumes (up to a thousand small components, many ties in triangle count),
 index meshes built to be hard on a concurrent union-find (long paths in every index order, one hub, interleaved index
 ranges, degenerate and repeated triangles, unused vertices, empty inputs), an index out of range, determinism, idempotence,
-and the two keywords of extract_mesh / extract_colored_mesh."""
+the two keywords of extract_mesh / extract_colored_mesh, and index meshes past one trip of the table's and the filter's
+grid-stride loops (sizes from the launch constants of csrc/mf_mesh_components.hip), with patterns that drive the wave-level
+count through every branch it has for a pair carried from an earlier trip."""
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -167,6 +170,119 @@ def test_index_meshes_equal_the_oracle(M, name):
     assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=1)
     assert_filter(M, verts, tris, attr, comps, what=name, min_triangles=1)
     assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=3, min_triangles=2)
+
+
+# ---------------------------------------------------------------- past one trip of the grid-stride loops
+# Every kernel of the table and of the filter is a grid-stride loop of at most MAX_BLOCKS workgroups of THREADS threads: it
+# takes a second trip only past TRIP elements.  A 512^3 extraction has millions of triangles; no mesh above reaches TRIP.
+_SRC = open(os.path.join(HERE, "..", "moco_flow_amd", "csrc", "mf_mesh_components.hip")).read()
+_const = lambda name: int(re.search(r"\bconstexpr int %s = (\d+);" % name, _SRC).group(1))
+THREADS, MAX_BLOCKS = _const("kThreads"), _const("kMaxBlocks")
+TRIP = THREADS * MAX_BLOCKS
+RAGGED = 70_001                                         # the elements of the last trip: some workgroups take it, the last wave partly
+assert STRIP + 2 < TRIP and 40 * 37 * 64 * 5 < TRIP and 0 < RAGGED < TRIP and RAGGED % 64 and THREADS % 64 == 0
+SHORT = TRIP // 4 + 19_000                              # strips of 4 triangles on 6 vertices
+
+
+@functools.lru_cache(maxsize=None)
+def big_mesh(name):
+    """(tris, V) of one mesh with more than TRIP triangles, vertices or components."""
+    rng = np.random.default_rng(11)
+    if name == "strip":                                 # one component: T, V > TRIP; vertices permuted, rows shuffled
+        T = TRIP + RAGGED
+        return rng.permutation(T + 2)[strip(T)[rng.permutation(T)]], T + 2
+    if name == "disjoint":                              # C = T > TRIP components of one triangle each, on scattered vertices
+        T = TRIP + 6_001
+        return rng.permutation(3 * T).reshape(T, 3), 3 * T
+    if name == "isolated":                              # C = V > TRIP components without a triangle
+        return np.zeros((0, 3), np.int64), TRIP + RAGGED
+    assert name == "short_strips"                       # C = SHORT; kept whole: Vk, Tk > TRIP
+    tris = (strip(4)[None] + 6 * np.arange(SHORT, dtype=np.int64)[:, None, None]).reshape(-1, 3)
+    return tris[rng.permutation(len(tris))], 6 * SHORT
+
+
+@functools.lru_cache(maxsize=None)
+def big_components(name):
+    return CC.components(*big_mesh(name))
+
+
+def _index_verts(V):
+    """Vertices that are their own old indices, and an int32 attribute: the kept rows say which were kept."""
+    return np.arange(V, dtype=np.int64)[:, None].repeat(3, 1).astype(np.float32), np.arange(V, dtype=np.int32)
+
+
+@pytest.mark.parametrize("name", ["strip", "disjoint", "isolated", "short_strips"])
+def test_table_and_filter_past_one_trip(M, name):
+    """table_tris / table_verts / table_gather and the root compaction, keep_roots / keep_verts / keep_tris, remap / reindex
+    and the row gathers with more than TRIP triangles, vertices, components, kept vertices and kept triangles."""
+    tris, V = big_mesh(name)
+    comps = big_components(name)
+    T, C = len(tris), len(comps[1])
+    assert_components(M, tris, V, want=comps, what=name)
+    verts, attr = _index_verts(V)
+    if name == "strip":
+        assert T > TRIP and V > TRIP and C == 1
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=1)
+        assert len(v) == V and len(t) == T
+    if name == "disjoint":
+        assert C == T > TRIP and V > 3 * TRIP
+        assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=3)                   # every rank is a tie: by label
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, min_triangles=1)
+        assert len(v) == V and len(t) == T
+    if name == "isolated":
+        assert C == V > TRIP and T == 0
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=2)
+        assert len(v) == 2 and len(t) == 0
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, min_triangles=1)
+        assert len(v) == 0 and len(t) == 0
+    if name == "short_strips":
+        assert C == SHORT and T == 4 * SHORT > TRIP and (comps[2] == 4).all() and (comps[3] == 6).all()
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, min_triangles=1)        # all of it: Vk, Tk > TRIP
+        assert len(v) == V > TRIP and len(t) == T
+        v, t, _ = assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=5, min_triangles=5)
+        assert len(v) == 0 and len(t) == 0
+
+
+# WaveCount (csrc/mf_mesh_components.hip) carries a wave's (key, count) pair across the trips; on the first trip the pair
+# starts empty, so what it does with a pair held over is reached only past TRIP elements.  A pattern spells the mesh
+# (CC.pattern_mesh): rows and vertices are in pattern order, nothing is shuffled -- the order is the input.  Lane l of a wave
+# reads the elements = l (mod 64): TRIP and every workgroup's base are multiples of 64.
+def _pattern(name):
+    n = RAGGED + (TRIP if name == "one_three_trips" else 0)
+    lane = np.arange(n) % 64
+    later = {"one": np.zeros(n), "one_three_trips": np.zeros(n),             # the held key again: carried, flushed once
+             "switch": np.ones(n),                                          # a new majority flushes a non-empty pair
+             "minority_low": lane >= 20,                                    # 20 A then 44 B: A is carried, then B takes the pair
+             "minority_high": lane < 44,                                    # 44 B take the pair, then A, no longer held: its leader adds
+             "half": lane >= 32,                                            # 32 A carried, 32 B: no majority, their leader adds
+             "distinct": 1 + lane}[name]                                    # 64 keys of one lane each
+    return np.concatenate([np.zeros(TRIP, np.int64), later.astype(np.int64)])
+
+
+PATTERNS = {"one": (1, ("carry_add",)), "one_three_trips": (1, ("carry_add",)), "switch": (2, ("take_flush",)),
+            "minority_low": (2, ("carry_add", "take_flush")), "minority_high": (2, ("take_flush", "leader_add_holding")),
+            "half": (2, ("carry_add", "leader_add_holding")), "distinct": (65, ("leader_add_holding",))}
+
+
+@pytest.mark.parametrize("name", list(PATTERNS))
+def test_counts_carried_across_trips(M, name):
+    """tri_counts and vert_counts where a wave meets, on a later trip, the key it holds, a new majority, the held key as a
+    minority before or after the new majority, an even split and 64 distinct keys.  CC.wave_count_replay proves on the
+    oracle's labels that the mesh drives both counting kernels through the branches it was built for."""
+    n_comps, branches = PATTERNS[name]
+    tris, V = CC.pattern_mesh(_pattern(name))
+    comps = lab, ids, tc, vc = CC.components(tris, V)
+    assert len(ids) == n_comps and min(len(tris), V) > TRIP * (2 if name == "one_three_trips" else 1)
+    for what, keys, counts in (("triangles", lab[tris[:, 0]], tc), ("vertices", lab, vc)):
+        adds, later = CC.wave_count_replay(keys, THREADS, MAX_BLOCKS)
+        assert [adds.get(int(r), 0) for r in ids] == counts.tolist(), (name, what)
+        for b in branches:
+            assert later[b] > 0, (name, what, later)
+        print(f"{name} {what}: {len(keys)} elements, on later trips {later}")
+    assert_components(M, tris, V, want=comps, what=name)
+    verts, attr = _index_verts(V)
+    assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=1)
+    assert_filter(M, verts, tris, attr, comps, what=name, keep_largest=2, min_triangles=3)
 
 
 def test_index_out_of_range_raises_and_leaves_nothing_behind(M):

@@ -182,6 +182,34 @@ def test_select_of_a_lattice_outside_the_box_is_empty():
     assert K == 27 and np.array_equal(ids, np.arange(27)) and np.array_equal(slot, np.arange(27))
 
 
+def test_select_fast_equals_select():
+    """LO.select_fast (all bricks at once, for the large lattices of tests/test_gpu_lattice.py) against the brick-by-brick
+    definition: every lattice and grid the select tests use, partly covering and overhanging boxes, empty and full grids,
+    a lattice outside the box, and a flat lattice of 129 x 129 bricks."""
+    box = ((-0.4, -1.2, -0.1), (0.7, 0.3, 2.0))
+    unit = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
+    lin = lambda n, lo=unit[0], hi=unit[1]: [np.linspace(lo[a], hi[a], n[a]).astype(np.float32) for a in range(3)]
+    rng = np.random.default_rng(3)
+    cases = [(rng.random((5, 4, 7)) < d, box, lin(n)) for d in (0.0, 0.1, 0.15, 1.0)
+             for n in ((19, 13, 21), (8, 16, 8), (2, 2, 2), (9, 2, 65), (70, 60, 50))]
+    cases += [(rng.random((40, 40, 40)) < 0.0004, unit, lin((12, 12, 12))), (rng.random((40, 40, 40)) < 0.2, unit, lin((1025, 1025, 1))),
+              (rng.random((19, 16, 22)) < 0.05, ((-1.0, -0.8, -1.1), (1.0, 0.9, 1.2)), lin((20, 17, 23), (-1.0, -0.8, -1.1), (1.0, 0.9, 1.2))),
+              (np.ones((4, 5, 6), dtype=bool), unit, lin((19, 13, 19), (1.5, -1.0, -1.0), (2.5, 1.0, 1.0)))]
+    partial = 0
+    for dense, (lo, hi), axes in cases:
+        n = [len(a) for a in axes]
+        lo32, hi32, inv = _grid_consts(dense.shape, lo, hi)
+        for woa in ((0, 1, 2), (1, 0, 2), (2, 0, 1)):
+            for margin in (0, 1, 2):
+                tables = LO.range_tables(axes, margin, dense.shape, lo32, hi32, inv, woa)
+                want, got = LO.select(dense, tables, n, woa), LO.select_fast(dense, tables, n, woa)
+                for w, g in zip(want[:2], got[:2]):
+                    assert g.dtype == w.dtype and np.array_equal(g, w), (dense.shape, n, woa, margin)
+                assert got[2] == want[2]
+                partial += 0 < want[2] < len(want[0])
+    assert partial > len(cases) * 9 // 3                               # bricks on both sides in more than a third of the runs
+
+
 def test_points_and_scatter_invert_each_other():
     n = (19, 13, 21)
     rng = np.random.default_rng(5)

@@ -80,6 +80,55 @@ def test_oracle_on_hand_made_meshes():
     assert lab.shape == ids.shape == tc.shape == vc.shape == (0,)
 
 
+def _replay(tris, V, comps, threads, max_blocks):
+    """CC.wave_count_replay over the triangles and the vertices: its sums equal the oracle's table; the branch counts of both."""
+    lab, ids, tc, vc = comps
+    out = []
+    for keys, counts in ((lab[tris[:, 0]], tc), (lab, vc)):
+        adds, later = CC.wave_count_replay(keys, threads, max_blocks)
+        assert [adds.get(int(r), 0) for r in ids] == counts.tolist() and sum(adds.values()) == len(keys)
+        out.append(later)
+    return out
+
+
+def test_small_meshes_never_carry_a_count_across_trips():
+    """The gap that tests/test_gpu_mesh_components.py closes past TRIP elements, written down: under the kernels' launch
+    constants every mesh of the older tests is counted in one trip, so WaveCount never meets a pair held over."""
+    import test_gpu_mesh_components as G
+    assert (G.THREADS, G.MAX_BLOCKS, G.TRIP) == (256, 2048, 524288)                    # read from the source; a change shows here
+    meshes = [(name, fixture_mesh(name)[1], len(fixture_mesh(name)[0])) for name in sorted(PINNED)]
+    meshes += [(name,) + G.index_mesh(name) for name in G.INDEX_MESHES]
+    for name, tris, V in meshes:
+        assert max(len(tris), V) < G.TRIP, name
+        for later in _replay(tris, V, CC.components(tris, V), G.THREADS, G.MAX_BLOCKS):
+            assert not any(later.values()), (name, later)
+
+
+def test_replay_on_patterns_under_a_small_grid():
+    """CC.pattern_mesh and CC.wave_count_replay under a grid of 3 workgroups of 128 threads: every branch of a later trip is
+    taken by the pattern built for it, and the replayed sums are the oracle's counts."""
+    threads, blocks = 128, 3
+    trip, n = threads * blocks, 5 * 64 + 37
+    lane = np.arange(n) % 64
+    cases = {"one": (np.zeros(n), ("carry_add",)), "switch": (np.ones(n), ("take_flush",)),
+             "minority_low": (lane >= 20, ("carry_add", "take_flush")), "minority_high": (lane < 44, ("take_flush", "leader_add_holding")),
+             "half": (lane >= 32, ("carry_add", "leader_add_holding")), "distinct": (1 + lane, ("leader_add_holding",))}
+    seen = set()
+    for name, (later_part, branches) in cases.items():
+        pattern = np.concatenate([np.zeros(trip, np.int64), np.asarray(later_part, np.int64)])
+        tris, V = CC.pattern_mesh(pattern)
+        comps = CC.components(tris, V)
+        assert np.array_equal(comps[0], comps[1][pattern]) and len(tris) == V - 2 * len(comps[1])   # the labels spell the pattern
+        assert np.array_equal(tris[:, 0], np.sort(tris[:, 0])) and len(np.unique(tris[:, 0])) == len(tris)
+        for later in _replay(tris, V, comps, threads, blocks):
+            for b in branches:
+                assert later[b] > 0, (name, later)
+            seen |= {b for b in later if later[b]}
+    assert seen == set(CC.BRANCHES) - {"take_empty"}                    # a wave that takes a later trip filled its pair on the first
+    adds, later = CC.wave_count_replay([7] * 40 + [5] * 24 + [5] * 10, 64, 1)         # one wave, two trips, by hand
+    assert adds == {7: 40, 5: 34} and later == dict(carry_add=0, take_flush=0, take_empty=0, leader_add_holding=1)
+
+
 def test_library_exports_header_symbols_and_prototypes():
     import moco_flow_amd._lib as L
     header = open(os.path.join(ROOT, "include", "mocoflow_hip.h")).read()
