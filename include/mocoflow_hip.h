@@ -50,7 +50,8 @@ extern "C" {
  *     (+ mf_occ_build_scratch_bytes), mf_ray_clip; mf_mesh_label, mf_mesh_table_count / mf_mesh_table_emit, mf_mesh_filter_plan /
  *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows; mf_project_vertices, mf_rasterize (+ mf_raster_scratch_bytes),
  *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade; mf_resize_u8 (+ mf_resize_u8_scratch_bytes), mf_composite_rows,
- *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter */
+ *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter;
+ *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -1041,6 +1042,49 @@ int32_t mf_composite_rows(const void* image, int32_t image_kind, int64_t H, int6
 enum { MF_PLATE_AUTO = 0, MF_PLATE_STAGED = 1, MF_PLATE_STREAMED = 2 };
 int32_t mf_background_plate(const uint8_t* frames, const uint8_t* masks, int64_t F, int64_t H, int64_t W, int32_t C, int64_t k,
                             int32_t path, uint8_t* out, void* stream);
+
+/* ---- matte clean-up (csrc/mf_regions.hip): the connected regions of a thresholded byte image, per frame of an (F, H, W) stack.
+ * Contract: members are alpha >= thres (below != 0: alpha < thres), thres in [0, 256]; regions are the 8- or 4-connected
+ * components of the members of one frame (frames never interact, rows do not wrap); the label of a member is the smallest
+ * row-major index y W + x of its region within its frame, -1 for a non-member; area = pixel count.  Integers only, every output a
+ * pure function of the input.  Every entry: F, H, W >= 0 and F H W < 2^31 (32-bit indexing), else MF_E_INVALID; all refusals come
+ * before any launch; F H W = 0 launches nothing.  Not cv2: contourArea is a polygon area, not a pixel count, and RETR_TREE's hole
+ * contours erase a one-pixel ring around every hole of the kept region. */
+
+/* mf_mask_label_scratch_bytes (scripts/data_utils.py:102-114, :135-147): bytes of the scratch that the five entries below share:
+ * parent int32 [F H W] | area int32 [F H W] | uint64 [F] | int64 [launch constant].  -1 on a refused shape. */
+int64_t mf_mask_label_scratch_bytes(int64_t F, int64_t H, int64_t W);
+
+/* mf_mask_label (scripts/data_utils.py:102-114, :135-147: the threshold `raw[..., 3] >= thres` and the regions findContours
+ * traces): pixel g of the stack is read at alpha[g stride], stride 1 (an alpha plane) or 4 (channel 3 of RGBA in place: pass
+ * rgba + 3); connectivity 8 or 4.  labels (F, H, W) int32.  Leaves area[f H W + label] of every region in scratch for
+ * mf_mask_select.  Lock-free union-find: per tile in LDS, across the tile seams in global memory, then one flattening pass; the
+ * scratch may hold anything on entry.  thres outside [0, 256], another connectivity or stride, a NULL: MF_E_INVALID. */
+int32_t mf_mask_label(const uint8_t* alpha, int32_t stride, int64_t F, int64_t H, int64_t W, int32_t thres, int32_t below,
+                      int32_t connectivity, int32_t* labels, void* scratch, void* stream);
+
+/* mf_mask_select (scripts/data_utils.py:102-114 find_max_region, :135-147): out (F, H, W) bytes = 255 where the pixel's region
+ * has area >= min_area and (largest == 0 or it is its frame's largest region: most pixels, ties to the smaller label), else 0; a
+ * frame without members is all 0.  scratch as mf_mask_label of these labels left it.  One 64-bit atomicMax per wave and frame
+ * finds the winner; no host read. */
+int32_t mf_mask_select(const int32_t* labels, int64_t F, int64_t H, int64_t W, int32_t largest, int64_t min_area, uint8_t* out,
+                       void* scratch, void* stream);
+
+/* mf_mask_fill_holes (scripts/data_utils.py:102-114, :135-147 keep the outer contour's inside): in place on mask (F, H, W) bytes,
+ * 0 = outside.  A hole is a 4-connected component of the zeros of a frame without a pixel on the frame's first or last row or
+ * column (the complement of 8-connected foreground: a pocket that leaks only through a diagonal gap is a hole, a bay on the
+ * border is not); its pixels become 255.  H <= 2 or W <= 2: nothing to fill, nothing launched. */
+int32_t mf_mask_fill_holes(uint8_t* mask, int64_t F, int64_t H, int64_t W, void* scratch, void* stream);
+
+/* mf_mask_table_count / mf_mask_table_emit (scripts/data_utils.py:102-114: the areas find_max_region ranks; :135-147).
+ * count: counts[f] (int64) = the regions of frame f of these labels.  emit, after the caller has read the counts: C = their sum;
+ * table (C, 7) int32, rows (frame0 + frame, label, area, x0, y0, x1, y1) with inclusive bounds (frame0 >= 0: the stack's place
+ * in a longer one that the caller passes chunk by chunk), in (frame, label) order (ordered integer
+ * ranks, csrc/mf_scan.hpp); needs only the labels, the scratch may hold anything.  A C below the true count leaves the later
+ * regions out, one above it leaves the extra rows 0; C < 0 or C > F H W: MF_E_INVALID.  C = 0 launches nothing. */
+int32_t mf_mask_table_count(const int32_t* labels, int64_t F, int64_t H, int64_t W, int64_t* counts, void* stream);
+int32_t mf_mask_table_emit(const int32_t* labels, int64_t F, int64_t H, int64_t W, int64_t frame0, int64_t C, int32_t* table,
+                           void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

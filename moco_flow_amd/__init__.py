@@ -8,7 +8,7 @@ and ``moco_flow_amd.metrics`` for the reference's ``models.metrics`` (mse, psnr,
 ``moco_flow_amd.supervision`` for its SMPL point supervision (correspondence, point_losses: no compaction, no host read),
 ``moco_flow_amd.occupancy`` for a frame's occupancy grid (OccupancyGrid: culls and clips test-time rays in front of render_image),
 ``moco_flow_amd.raster`` for the pictures the reference draws with pyrender (render_mesh, smpl_views: the stage-1 SMPL views),
-``moco_flow_amd.frames`` for frame ingest (resize as PIL does it, composite / to_rows, background_plate: bytes in, tensors out).
+``moco_flow_amd.frames`` for frame ingest (resize as PIL does it, composite / to_rows, background_plate, clean_mask / mask_regions: bytes in, tensors out).
 Every forward value comes from hand-written HIP kernels reached through the C ABI in include/mocoflow_hip.h
 (libmocoflow_hip.so); CPU tensors and a missing library raise.  The backward is HIP as well -- of render_rays passes
 (which record gradients in fp32 whatever set_precision says) and of module-level NeRF / NoF / Embedding calls; shapes it
@@ -35,7 +35,7 @@ from .occupancy import OccupancyGrid
 from . import raster
 from .raster import interpolate, project_vertices, rasterize, render_mesh, smpl_views
 from . import frames
-from .frames import background_plate, composite, resize, to_rows
+from .frames import Regions, background_plate, clean_mask, composite, mask_regions, resize, to_rows
 from .autograd import set_dx_precision, set_wgrad_precision
 from .rendering import render_rays, resample_merge, sample_pdf, set_precision, set_train_forward_precision
 
@@ -46,4 +46,4 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
            "occupancy", "OccupancyGrid", "query_sigma_lattice",
            "raster", "project_vertices", "rasterize", "interpolate", "render_mesh", "smpl_views",
-           "frames", "resize", "composite", "to_rows", "background_plate"]
+           "frames", "resize", "composite", "to_rows", "background_plate", "clean_mask", "mask_regions", "Regions"]

@@ -260,6 +260,12 @@ SYMBOLS = {
                                  _fp, _fp, C.c_int32, _fp, _fp, _fp]),
     "mf_composite_rows": (C.c_int32, [_fp, C.c_int32, C.c_int64, C.c_int64, _fp, C.c_int32, _fp, _fp]),
     "mf_background_plate": (C.c_int32, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _fp, _fp]),
+    "mf_mask_label_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_mask_label": (C.c_int32, [_fp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
+    "mf_mask_select": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _fp, _fp, _fp]),
+    "mf_mask_fill_holes": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp]),
+    "mf_mask_table_count": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp]),
+    "mf_mask_table_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp]),
 }
 
 _lock = threading.Lock()

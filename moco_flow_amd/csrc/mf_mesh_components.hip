@@ -8,27 +8,16 @@
 // label of a vertex is the smallest vertex index of its component; a triangle belongs to the component of its column-0
 // vertex; every output is a pure function of the input.
 //
-// Labelling: lock-free union-find on 32-bit parents.  parent[v] = v; one pass over the triangles unites (t0, t1) and
-// (t1, t2); one pass writes labels[v] = root of v.  Three invariants hold at every instant, whatever the interleaving:
-//   (1) parent[x] <= x, with equality exactly at roots: every chain strictly descends, so it ends and no cycle can form;
-//   (2) a non-root never becomes a root again: the only write to a root is the compare-and-swap that hooks it, and path
-//       splitting writes to x only after it has seen parent[x] != x;
-//   (3) every write stores a vertex of the same tree: a union hooks the larger root under a vertex of the other tree of
-//       the edge it was given, path splitting stores a former ancestor.
-// A stale read therefore still yields a vertex of the right tree and only costs steps.  By (1) the root of a tree is its
-// smallest index, and a union returns only when both ends have one root or its own compare-and-swap has hooked one under
-// the other, so after the pass the trees are the components and the labels are their minima -- which thread won which
-// compare-and-swap changes the shape of the trees in between, never the result.
-// Nothing waits: a failed compare-and-swap means another thread has hooked that very root in the meantime (progress), the
-// loser goes on from the value it got back, which is strictly smaller; there is no flag, no barrier across workgroups and no
-// cooperative launch.
+// Labelling: the lock-free union-find of mf_unionfind.hpp (its invariants are proved there) on 32-bit parents.  parent[v] = v;
+// one pass over the triangles unites (t0, t1) and (t1, t2); one pass writes labels[v] = root of v, the smallest index of the
+// component -- which thread won which compare-and-swap never shows in the result.
 //
-// Counts are integer atomic adds (sums do not depend on their order), first reduced across the lanes of a wave that hit
-// the same label and, for the label most of the wave shares, across the wave's whole share of the mesh: a mesh that is one
-// big component would otherwise send every add to one address.  Compaction is
+// Counts are uf::wave_count's integer atomic adds, reduced across a wave first: a mesh that is one big component would
+// otherwise send every add to one address.  Compaction is
 // mf_mask_compact (mf_batch.hip): ballots and fixed-order sums, original order kept.
 #include "mf_host.hpp"
 #include "mf_scan.hpp"
+#include "mf_unionfind.hpp"
 
 using namespace mf;
 
@@ -46,34 +35,7 @@ constexpr long long kIndexLimit = 1LL << 31;     // 32-bit internal indexing
 
 inline unsigned grid_for(long long n, int cap = kMaxBlocks) { return (unsigned)capped_blocks(n, kThreads, cap, 1); }
 
-// parents are read and written by many workgroups at once: relaxed agent-scope accesses (served by L2, never a stale L1 line
-// for good), the hook itself is a compare-and-swap
-__device__ __forceinline__ int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x; path splitting on the way: every visited vertex is re-pointed at its grandparent
-__device__ __forceinline__ int find_root(int* parent, int x) {
-  int p = ld(parent + x);
-  while (p != x) {
-    const int g = ld(parent + p);
-    if (g == p) return p;
-    st(parent + x, g);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-  int ra = find_root(parent, a), rb = find_root(parent, b);
-  while (ra != rb) {
-    if (ra < rb) { const int t = ra; ra = rb; rb = t; }          // hook the larger root under the smaller
-    const int old = atomicCAS(parent + ra, ra, rb);
-    if (old == ra) return;
-    ra = find_root(parent, old);                                 // another thread hooked ra under old < ra: go on from there
-    rb = find_root(parent, rb);
-  }
-}
+using namespace mf::uf;                          // ld / st, find_root, unite, WaveCount / wave_count / wave_count_flush
 
 __device__ __forceinline__ bool in_range(long long i, long long n) { return (unsigned long long)i < (unsigned long long)n; }
 
@@ -81,39 +43,6 @@ __device__ __forceinline__ bool in_range(long long i, long long n) { return (uns
 __device__ __forceinline__ void wave_add(long long* counter, long long v) {
   v = wave_sum_i64(v);
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
-}
-
-// cnt[key] += 1 for every valid lane, summed on chip first: per distinct key of the wave one add of the lanes' number
-// (ballot), and the key most of the wave shares is carried in a wave-uniform (key, count) pair across the trips of the
-// grid-stride loop and added once at the end -- a mesh that is one big component sends one add per wave to the hot
-// address, not one per 64 elements (returning or not, adds to one word are served one at a time).  Integer sums: the
-// result does not depend on what was cached where.  Every lane of the wave calls both functions.
-struct WaveCount { int key; int n; };
-
-__device__ __forceinline__ void wave_count_flush(int* cnt, WaveCount& w) {
-  if ((threadIdx.x & 63) == 0 && w.n) atomicAdd(cnt + w.key, w.n);
-  w.n = 0;
-}
-
-__device__ __forceinline__ void wave_count(int* cnt, int key, bool valid, WaveCount& w) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(valid);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int k = __shfl(key, leader);
-    const unsigned long long m = __ballot(valid && key == k);
-    const int c = __popcll(m);
-    if (w.n && k == w.key) {
-      w.n += c;
-    } else if (c > 32 || !w.n) {                                  // the wave's majority (or the first key seen) takes the pair
-      wave_count_flush(cnt, w);
-      w.key = k;
-      w.n = c;
-    } else if (lane == leader) {
-      atomicAdd(cnt + k, c);
-    }
-    todo &= ~m;
-  }
 }
 
 __global__ __launch_bounds__(kThreads) void init_kernel(int* parent, long long V) {

@@ -1,5 +1,5 @@
 // mf_scan.hpp -- the ordered integer prefix of the library, written once.  Users: mf_sample.hip (compact_*_kernel: mf_compact_mask),
-// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add).
+// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add), mf_regions.hip (reg_table_*_kernel).
 // Integer arithmetic: the order of the additions is free.  THE CONTRACT IS WHO RANKS BEFORE WHOM AND WHO SYNCHRONISES; "bit-
 // identical, no atomics, original order kept" (the ray batch) rests on it.  Workgroups are 1-D, whole waves (lane =
 // threadIdx.x & 63, wave = threadIdx.x >> 6); lower lanes rank before higher ones, lower waves and lower threads' shares likewise.

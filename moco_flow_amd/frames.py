@@ -7,10 +7,15 @@
     to_rows           an (H, W, 3) byte image as (H W, 3) fp32 rows, ``u8.float() / 255`` as the device evaluates it
     background_plate  ``generate_background_image``: per pixel and channel the k-th smallest of img (1 - msk) over the frames, as
                       bytes (mf_background_plate) -- without the reference's float64 copy of every frame and its np.sort
+    clean_mask        the matte background_plate takes, from the raw alpha: threshold at 196, keep the largest connected region
+                      (scripts/data_utils.py:135-147, find_max_region :102-114), optionally fill its holes (mf_mask_label,
+                      mf_mask_select, mf_mask_fill_holes) -- a contract of its own in exact integers, not cv2's contour tracing
+    mask_regions      the regions themselves: labels, and the table of areas and bounding boxes (mf_mask_table_count / _emit)
 
 Everything is integer arithmetic on bytes or fp32 rounded once per operation, so every result is pinned exactly.  The resize
 coefficients are built here on the host in float64, as PIL's precompute_coeffs builds them, and uploaded once per size pair and
 device.  No gradients; everything runs on the current stream of the inputs' device.  CPU tensors raise: there is no host path."""
+import collections
 import math
 
 import numpy as np
@@ -18,7 +23,8 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["resize", "composite", "to_rows", "background_plate", "resize_tables", "plate_index"]
+__all__ = ["resize", "composite", "to_rows", "background_plate", "resize_tables", "plate_index", "clean_mask", "mask_regions",
+           "Regions"]
 
 _PRECISION_BITS = 22           # PIL's PRECISION_BITS = 32 - 8 - 2
 _INDEX_LIMIT = 2 ** 31         # the kernels index with 32 bits: a call stays below this many bytes per image stack
@@ -215,3 +221,116 @@ def background_plate(frames, masks, q=0.8, path="auto"):
         L.check(L.lib().mf_background_plate(frames.data_ptr(), masks.data_ptr(), F, H, W, C, k, _PLATE_PATHS[path], out.data_ptr(),
                                             L.current_stream(dev)), "mf_background_plate")
     return out
+
+
+Regions = collections.namedtuple("Regions", ["labels", "counts", "table"])
+
+# bytes of device memory (the labels and the kernels' scratch: 12 per pixel) that clean_mask / mask_regions hold per chunk of frames
+SCRATCH_BUDGET = 1 << 30
+_REGION_BYTES_PER_PIXEL = 12
+
+
+def _alpha_plane(alpha, what):
+    """(tensor to keep alive, address of pixel 0, pixel stride in bytes, F, H, W, single image) of the alpha argument of
+    clean_mask / mask_regions.  A contiguous RGBA stack, or its channel view ``rgba[..., c]``, is read in place with stride 4."""
+    _check_u8(alpha, what, "alpha")
+    shape = tuple(int(v) for v in alpha.shape)
+    rgba = alpha.dim() == 4 or (alpha.dim() == 3 and shape[-1] == 4)
+    if alpha.dim() not in (2, 3, 4) or (alpha.dim() == 4 and shape[-1] != 4):
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: alpha is {shape}; (H, W) or (F, H, W) bytes, or (H, W, 4) / (F, H, W, 4) RGBA")
+    single = alpha.dim() == (3 if rgba else 2)
+    stack = alpha.unsqueeze(0) if single else alpha
+    F, H, W = (int(v) for v in stack.shape[:3])
+    if H * W >= _INDEX_LIMIT:
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: H={H} W={W}; needs H W < 2^31")
+    if rgba:
+        stack = stack.contiguous()
+        return stack, stack.data_ptr() + 3, 4, F, H, W, single
+    if F * H * W > 0 and not stack.is_contiguous() and tuple(stack.stride()) == (4 * H * W, 4 * W, 4):
+        return stack, stack.data_ptr(), 4, F, H, W, single              # a channel of a contiguous RGBA stack
+    stack = stack.contiguous()
+    return stack, stack.data_ptr(), 1, F, H, W, single
+
+
+def _region_args(what, thres, connectivity=8, min_area=0):
+    if isinstance(thres, bool) or not isinstance(thres, (int, np.integer)) or not 0 <= int(thres) <= 256:
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: thres={thres!r}; an integer in [0, 256]")
+    if connectivity not in (4, 8):
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: connectivity={connectivity!r}; 4 or 8")
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
+        raise RuntimeError(f"moco_flow_amd.frames.{what}: min_area={min_area!r}; an integer >= 0")
+
+
+def _region_chunk(F, H, W):
+    """frames per call: inside the scratch budget and 32-bit indexing, at least one"""
+    hw = max(H * W, 1)
+    return max(1, min(F, (_INDEX_LIMIT - 1) // hw, SCRATCH_BUDGET // (_REGION_BYTES_PER_PIXEL * hw)))
+
+
+def clean_mask(alpha, thres=196, largest=True, min_area=0, fill_holes=False):
+    """scripts/data_utils.py:135-147 on the device.  alpha: (H, W) or (F, H, W) uint8, or (H, W, 4) / (F, H, W, 4) RGBA whose
+    channel 3 is read in place (a 3-D tensor whose last dimension is 4 is RGBA).  Returns uint8 {0, 255} of shape (H, W) /
+    (F, H, W): 255 where alpha >= thres and the pixel's 8-connected region has at least min_area pixels and, with `largest`, is
+    the frame's largest (most pixels; ties go to the region that starts first in row-major order).  fill_holes: the zeros that
+    no 4-connected path of zeros joins to the frame's border become 255.  A frame without a member gives zeros (the reference
+    raises there, on np.argmax of an empty list).  This is what background_plate takes as `masks` and what
+    ``raw[..., 3] = mask`` (:146) writes back.
+    Not cv2's result in two documented ways: area is the pixel count, not contourArea's polygon area, and
+    the one-pixel ring that the reference erases around every hole of the kept region is kept.
+    Runs on the current stream without a host synchronisation; a stack goes through in chunks of frames under SCRATCH_BUDGET."""
+    _region_args("clean_mask", thres, 8, min_area)
+    stack, ptr, stride, F, H, W, single = _alpha_plane(alpha, "clean_mask")
+    dev = stack.device
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
+    if out.numel() > 0:
+        lib = L.lib()
+        chunk = _region_chunk(F, H, W)
+        scratch = torch.empty(int(lib.mf_mask_label_scratch_bytes(chunk, H, W)), dtype=torch.uint8, device=dev)
+        labels = torch.empty((chunk, H, W), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            stream = L.current_stream(dev)
+            for f0 in range(0, F, chunk):
+                n = min(chunk, F - f0)
+                L.check(lib.mf_mask_label(ptr + f0 * H * W * stride, stride, n, H, W, int(thres), 0, 8, labels.data_ptr(),
+                                          scratch.data_ptr(), stream), "mf_mask_label")
+                L.check(lib.mf_mask_select(labels.data_ptr(), n, H, W, int(bool(largest)), int(min_area), out[f0].data_ptr(),
+                                           scratch.data_ptr(), stream), "mf_mask_select")
+                if fill_holes:
+                    L.check(lib.mf_mask_fill_holes(out[f0].data_ptr(), n, H, W, scratch.data_ptr(), stream), "mf_mask_fill_holes")
+    return out[0] if single else out
+
+
+def mask_regions(alpha, thres=196, connectivity=8, below=False):
+    """The connected regions of ``alpha >= thres`` (below: ``alpha < thres``) per frame; alpha as clean_mask takes it.  Returns
+    Regions(labels, counts, table): labels int32 (H, W) / (F, H, W), the smallest row-major index y W + x of the pixel's region
+    within its frame, -1 off the members; counts (F,) int64, the regions of each frame; table (sum counts, 7) int32 with rows
+    (frame, label, area, x0, y0, x1, y1), bounds inclusive, in (frame, label) order.  One host read: the counts, which size the
+    table."""
+    _region_args("mask_regions", thres, connectivity)
+    stack, ptr, stride, F, H, W, single = _alpha_plane(alpha, "mask_regions")
+    dev = stack.device
+    labels = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+    counts = torch.zeros((F,), dtype=torch.int64, device=dev)
+    if labels.numel() == 0:
+        return Regions(labels[0] if single else labels, counts, torch.empty((0, 7), dtype=torch.int32, device=dev))
+    lib = L.lib()
+    chunk = _region_chunk(F, H, W)
+    scratch = torch.empty(int(lib.mf_mask_label_scratch_bytes(chunk, H, W)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = L.current_stream(dev)
+        for f0 in range(0, F, chunk):
+            n = min(chunk, F - f0)
+            L.check(lib.mf_mask_label(ptr + f0 * H * W * stride, stride, n, H, W, int(thres), int(bool(below)), int(connectivity),
+                                      labels[f0].data_ptr(), scratch.data_ptr(), stream), "mf_mask_label")
+            L.check(lib.mf_mask_table_count(labels[f0].data_ptr(), n, H, W, counts[f0:].data_ptr(), stream), "mf_mask_table_count")
+        host = counts.cpu().numpy()                                       # the one host read
+        table = torch.empty((int(host.sum()), 7), dtype=torch.int32, device=dev)
+        row = 0
+        for f0 in range(0, F, chunk):
+            n = min(chunk, F - f0)
+            c = int(host[f0:f0 + n].sum())
+            if c > 0:
+                L.check(lib.mf_mask_table_emit(labels[f0].data_ptr(), n, H, W, f0, c, table[row:].data_ptr(), scratch.data_ptr(), stream),
+                        "mf_mask_table_emit")
+            row += c
+    return Regions(labels[0] if single else labels, counts, table)
