@@ -51,7 +51,8 @@ extern "C" {
  *     mf_mesh_filter_emit (+ their _scratch_bytes), mf_gather_rows; mf_project_vertices, mf_rasterize (+ mf_raster_scratch_bytes),
  *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade; mf_resize_u8 (+ mf_resize_u8_scratch_bytes), mf_composite_rows,
  *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter;
- *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit */
+ *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit;
+ *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -670,6 +671,46 @@ int32_t mf_mesh_filter_emit(const int64_t* tris, int64_t T, int64_t V, int64_t V
  * launched. */
 int32_t mf_gather_rows(const void* src, int64_t n_src, int64_t row_bytes, const int64_t* inds, int64_t n, void* dst,
                        void* stream);
+
+/* ---- mesh simplification by vertex clustering: the triangle count of an isosurface (1.8 M triangles on a smooth field at
+ * 512^3) brought down on the device, in one pass and as a pure function of the input (tests/mesh_simplify_oracle.py restates
+ * the contract in numpy).  The reference has no counterpart: it writes the full mesh (trainer_moco_flow.py:535-548).
+ * verts (V, 3) fp32, tris (T, 3) int64; lo, hi: HOST double[3]; cell > 0: the edge of a cubic cell in the vertices' units;
+ * n_a = floor((hi_a - lo_a) / cell) + 1 cells per axis, computed by the caller in double and checked here; n0 n1 n2, V, T
+ * below 2^31 (32-bit internal indexing), anything else MF_E_INVALID -- from mf_simplify_mesh_scratch_bytes already, before
+ * anything is allocated.
+ * Cell of a vertex, per axis in double: t = (double(v) - lo) / cell, c = floor(t), id = (c0 n1 + c1) n2 + c2.  A vertex that is
+ * not finite or lies outside [lo, hi] on an axis, and a triangle with an index outside [0, V), are counted into `bad`: nothing
+ * is clamped, a bad index is never dereferenced, the caller rejects the mesh.
+ * A triangle is degenerate, and dropped, if two of its three cells are equal.  Two others are duplicates if their cell triples
+ * are equal up to cyclic rotation (the opposite winding is another triangle); of a class the smallest triangle index
+ * survives.  Survivors keep their order and their corner order.  A cell is used if a survivor names it; the new vertices
+ * are the used cells, ascending by id; first[k] = the smallest vertex index in used cell k; cluster[v] = the new index of
+ * v's cell, -1 for a vertex of an unused cell.
+ * Duplicates are found in an open-addressing table of `slots` int32 entries -- a power of two above T, at most 2^31: an empty
+ * slot always remains, every probe ends, and the probe loop is bounded by `slots` besides.  A slot holds a triangle index;
+ * its key is recomputed from that triangle's cells.  Insert: linear probing from the hash of the rotation-canonical triple;
+ * compare-and-swap into an empty slot, atomicMin into a slot of the same key, on to the next otherwise.  A taken slot never
+ * changes its key class, so each class settles in one slot whatever the interleaving, and the slot ends as the class's minimum.
+ * Every rank is mf_scan.hpp's (fixed order); sums, minima and counts over a cell's members are integer atomics: every output
+ * is bit-identical from run to run.  Scratch is the caller's; nothing is allocated, everything runs on `stream`, nothing
+ * synchronises.  V = 0 or T = 0 is legal (the missing array may be NULL).
+ *
+ * mf_simplify_mesh_plan: cell ids, the table, the survivor flags, the used-cell bit mask and its word prefixes go to scratch;
+ * counts (device int64[3]) = [Vk = used cells, Tk = survivors, bad].  Up to six launches.
+ * mf_simplify_mesh_emit, with the same mesh, grid and scratch and the two counts read: tris_k (Tk, 3) = the survivors, corners
+ * rewritten to the new indices; first (Vk); cluster (V).  verts_k (Vk, 3) with sums (28 Vk bytes of the caller's, 8-byte
+ * aligned) = the exact mean of each used cell's members in fixed point: per axis q = llrint((t - c) 2^20), S = the int64 sum of
+ * q over the n members, verts_k = float(lo + cell (c + (double(S) / double(n)) / 2^20)), every operation rounded once in
+ * double; both NULL: positions are the caller's (rows first[k] of verts through mf_gather_rows keep a vertex on its lattice
+ * edge).  Tk == 0: cluster is filled with -1, nothing else is touched.  Up to three launches. */
+int64_t mf_simplify_mesh_scratch_bytes(int64_t V, int64_t T, int64_t n0, int64_t n1, int64_t n2, int64_t slots);
+int32_t mf_simplify_mesh_plan(const float* verts, int64_t V, const int64_t* tris, int64_t T, const double* lo, const double* hi,
+                              double cell, int64_t n0, int64_t n1, int64_t n2, int64_t slots, int64_t* counts, void* scratch,
+                              void* stream);
+int32_t mf_simplify_mesh_emit(const float* verts, int64_t V, const int64_t* tris, int64_t T, const double* lo, const double* hi,
+                              double cell, int64_t n0, int64_t n1, int64_t n2, int64_t Vk, int64_t Tk, void* scratch, void* sums,
+                              float* verts_k, int64_t* tris_k, int64_t* first, int64_t* cluster, void* stream);
 
 /* ---- validation metrics: models/metrics.py:4-22 (mse, psnr, ssim), called per validation image by val_step
  * (trainer_moco_flow.py:453-473).  The reference's ssim is kornia 0.6.5's kornia.metrics.ssim.ssim(img1, img2, window_size,

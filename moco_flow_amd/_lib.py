@@ -220,6 +220,11 @@ SYMBOLS = {
     "mf_mesh_filter_plan": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp]),
     "mf_mesh_filter_emit": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
     "mf_gather_rows": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, _fp]),
+    "mf_simplify_mesh_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mf_simplify_mesh_plan": (C.c_int32, [_fp, C.c_int64, _fp, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                          C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp]),
+    "mf_simplify_mesh_emit": (C.c_int32, [_fp, C.c_int64, _fp, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                          C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "mf_ssim_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mf_ssim": (C.c_int32, [_fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),

@@ -1,9 +1,10 @@
 // mf_scan.hpp -- the ordered integer prefix of the library, written once.  Users: mf_sample.hip (compact_*_kernel: mf_compact_mask),
-// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add), mf_regions.hip (reg_table_*_kernel).
+// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add), mf_regions.hip (reg_table_*_kernel),
+// mf_mesh_simplify.hip (the survivors' and the used cells' ranks).
 // Integer arithmetic: the order of the additions is free.  THE CONTRACT IS WHO RANKS BEFORE WHOM AND WHO SYNCHRONISES; "bit-
 // identical, no atomics, original order kept" (the ray batch) rests on it.  Workgroups are 1-D, whole waves (lane =
 // threadIdx.x & 63, wave = threadIdx.x >> 6); lower lanes rank before higher ones, lower waves and lower threads' shares likewise.
-//   wave_popcount, wave_rank, wave_sum_i64   every lane of the wave calls them (converged); no LDS, no barrier
+//   wave_popcount, wave_rank, wave_prefix_small, wave_sum_i64   every lane of the wave calls them (converged); no LDS, no barrier
 //   block_sum_i64<THREADS>        every thread of the workgroup calls it and receives the sum.  Owns THREADS / 64 words of LDS and
 //                                 opens with the barrier that lets it be called again: the caller places none
 //   block_offsets<THREADS, COLS>  every thread calls it and receives, per column, the sum of the totals of the waves in front of
@@ -23,6 +24,21 @@ __device__ __forceinline__ int wave_rank(bool m, int& total) {          // one b
   const unsigned long long b = __ballot(m);
   total = __popcll(b);
   return __popcll(b & lanes_below(threadIdx.x & 63));
+}
+
+// the exclusive prefix over the lanes of a small count v in [0, 2^BITS), and the wave's sum: one ballot per bit of v
+template <int BITS>
+__device__ __forceinline__ int wave_prefix_small(int v, int& total) {
+  const unsigned long long below = lanes_below(threadIdx.x & 63);
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int bit = 0; bit < BITS; ++bit) {
+    const unsigned long long m = __ballot((v >> bit) & 1);
+    before += __popcll(m & below) << bit;
+    total += __popcll(m) << bit;
+  }
+  return before;
 }
 
 __device__ __forceinline__ long long wave_sum_i64(long long v) {         // every lane receives the sum

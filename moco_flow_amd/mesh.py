@@ -3,7 +3,10 @@
 without the volume leaving the device -- and what a coloured mesh adds: vertex normals from the same volume
 (mf_mc_normals), vertex colours from the radiance field (query_radiance), a PLY writer that carries both; and the mesh
 clean-up that follows an isosurface at a fixed threshold: connected components (mf_mesh_label, mf_mesh_table_*) and the
-filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device."""
+filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device; and the
+reduction of the triangle count by vertex clustering (simplify_mesh: mf_simplify_mesh_*)."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -225,6 +228,121 @@ def _filter(verts, tris, labels, ids, keep, attrs=()):
             *(gather_rows(a.detach().contiguous(), vert_inds) for a in attrs))
 
 
+def _simplify_grid(lo, hi, cell):
+    """Cells per axis of the clustering grid, in float64 on the host: n_a = floor((hi_a - lo_a) / cell) + 1."""
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise RuntimeError(f"simplify_mesh: lo={lo.tolist()} hi={hi.tolist()} (a vertex that is not finite, or a bound that is not)")
+    if (hi < lo).any():
+        raise ValueError(f"simplify_mesh: hi={hi.tolist()} below lo={lo.tolist()}")
+    return [int(min(x, 2.0 ** 31)) for x in np.floor((hi - lo) / cell) + 1.0]     # 2^31 on an axis: the library refuses it
+
+
+def simplify_mesh(verts, tris, cell, lo=None, hi=None, placement="mean", attrs=(), return_map=False, _slots=None):
+    """Vertex clustering on the device: verts (V, 3) float32 and tris (T, 3) int64 on a 'cuda' device ->
+    (verts_k (Vk, 3) float32, tris_k (Tk, 3) int64, *attrs_k[, first (Vk,) int64, cluster (V,) int64]), the last two with
+    ``return_map``.
+
+    ``cell`` > 0 is the edge of a cubic cell in the vertices' own units; ``lo`` / ``hi`` are 3-vectors of host floats and
+    default to verts.amin(0) / verts.amax(0), which costs one more device -> host read.  Cells per axis n_a =
+    floor((hi_a - lo_a) / cell) + 1 in float64; n0 n1 n2, V and T below 2^31, refused before anything is allocated.  The
+    cell of a vertex, per axis in float64: t = (double(v) - lo) / cell, c = floor(t), id = (c0 n1 + c1) n2 + c2.  A vertex
+    that is not finite or lies outside [lo, hi] on an axis, and a triangle with an index outside [0, V), raise RuntimeError:
+    nothing is clamped, a bad index is never dereferenced.
+
+    A triangle is dropped as degenerate if two of its three cells are equal.  Two others are duplicates if their cell
+    triples are equal up to cyclic rotation (the same cells in the opposite winding are not); of each class the triangle
+    with the smallest original index survives; survivors keep their order and their corner order.  The new vertices are the
+    cells a survivor names, ascending by cell id; every other vertex is dropped, cluster[v] = -1 (a vertex in no triangle,
+    a vertex of a cell only degenerate triangles name); first[k] = the smallest original index in cell k, cluster[v] = the
+    new index of v's cell.  Rows first[k] of every tensor in ``attrs`` (each (V, ...), any dtype) are copied byte for byte
+    (mf_gather_rows).  ``placement="first"``: verts_k[k] = verts[first[k]] byte for byte -- the vertex stays on its lattice
+    edge, so vertex_normals stays valid for it.  ``placement="mean"``: the exact mean of the cell's members in fixed point,
+    q = llrint((t - c) 2^20) per axis, S = the int64 sum over the n members, verts_k = float32(lo + cell (c + (S / n) / 2^20)),
+    each operation rounded once in float64: integer atomics make it independent of their order.  Every output is a pure
+    function of the input, bit-identical from run to run (include/mocoflow_hip.h mf_simplify_mesh_*).  Nothing kept:
+    (0, ...) tensors; V = 0 or T = 0 is legal.  One device -> host read ([Vk, Tk, bad]) besides the one of the defaults.
+
+    ``_slots`` (private, for tests): the size of the duplicate table, a power of two above T; default the next power of
+    two >= 2 T + 1."""
+    if placement not in ("mean", "first"):
+        raise ValueError(f"simplify_mesh: placement={placement!r} ('mean' or 'first')")
+    _check_tris(tris, "simplify_mesh")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError(f"simplify_mesh: verts must be (V, 3), got shape {tuple(verts.shape)}")
+    if verts.dtype != torch.float32:
+        raise RuntimeError(f"simplify_mesh: verts must be float32, got {verts.dtype}")
+    V, T = verts.shape[0], tris.shape[0]
+    attrs = tuple(attrs)
+    for i, a in enumerate(attrs):
+        if a.dim() < 1 or a.shape[0] != V:
+            raise RuntimeError(f"simplify_mesh: attrs[{i}] has shape {tuple(a.shape)} for {V} vertices")
+    cell = float(cell)
+    if not (cell > 0.0 and np.isfinite(cell)):
+        raise ValueError(f"simplify_mesh: cell={cell} (a finite edge above 0)")
+    if (lo is None) != (hi is None):
+        raise ValueError("simplify_mesh: give both lo and hi, or neither")
+    if lo is not None:
+        lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("simplify_mesh: lo and hi are 3-vectors")
+        n = _simplify_grid(lo, hi, cell)
+    for t in (tris, verts) + attrs:
+        L.require_gpu(t, "simplify_mesh")
+    verts, tris = verts.detach().contiguous(), tris.detach().contiguous()
+    if lo is None:
+        if V:
+            ends = torch.stack([verts.amin(0), verts.amax(0)]).double().cpu().numpy()      # the extra read
+        else:
+            ends = np.zeros((2, 3))
+        lo, hi = ends[0], ends[1]
+        n = _simplify_grid(lo, hi, cell)
+    slots = int(_slots) if _slots is not None else min(1 << (2 * T).bit_length(), 1 << 31)
+    dbl3 = C.c_double * 3
+    grid = (dbl3(*lo.tolist()), dbl3(*hi.tolist()), cell, *n)
+    scratch, counts = _simplify_plan(verts, tris, grid, slots)
+    Vk, Tk, bad = (int(x) for x in counts.tolist())
+    if bad:
+        raise RuntimeError(f"simplify_mesh: {bad} vertices that are not finite or lie outside [lo, hi], or triangles that name "
+                           f"a vertex outside [0, {V})")
+    verts_k, tris_k, first, cluster = _simplify_emit(verts, tris, grid, scratch, Vk, Tk, placement == "mean")
+    if verts_k is None:
+        verts_k = gather_rows(verts, first)
+    out = (verts_k, tris_k, *(gather_rows(a.detach().contiguous(), first) for a in attrs))
+    return out + (first, cluster) if return_map else out
+
+
+def _simplify_plan(verts, tris, grid, slots):
+    """Launch the planning step on checked, contiguous device tensors: (scratch, counts), counts = device int64 [Vk, Tk, bad].
+    ``grid`` = (lo, hi, cell, n0, n1, n2), lo and hi as ctypes double[3].  No host read."""
+    lib, dev, V, T = L.lib(), tris.device, verts.shape[0], tris.shape[0]
+    need = int(lib.mf_simplify_mesh_scratch_bytes(V, T, *grid[3:], slots))
+    if need < 0:                                     # too many cells, V, T or a bad table size: before anything is allocated
+        L.check(need, "mf_simplify_mesh_scratch_bytes")
+    scratch = _bytes(need, dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mf_simplify_mesh_plan(L.ptr(verts) if V else None, V, L.ptr(tris) if T else None, T, *grid, slots,
+                                          counts.data_ptr(), scratch.data_ptr(), L.current_stream(dev)), "mf_simplify_mesh_plan")
+    return scratch, counts
+
+
+def _simplify_emit(verts, tris, grid, scratch, Vk, Tk, mean):
+    """The emit step after the plan on the same stream, with the counts read: (verts_k or None, tris_k, first, cluster);
+    verts_k only for the mean placement."""
+    lib, dev, V, T = L.lib(), tris.device, verts.shape[0], tris.shape[0]
+    verts_k = torch.empty((Vk, 3), dtype=torch.float32, device=dev) if mean else None
+    sums = _bytes(28 * Vk, dev) if mean and Vk else None
+    tris_k = torch.empty((Tk, 3), dtype=torch.int64, device=dev)
+    first = torch.empty(Vk, dtype=torch.int64, device=dev)
+    cluster = torch.empty(V, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mf_simplify_mesh_emit(L.ptr(verts) if V else None, V, L.ptr(tris) if T else None, T, *grid, Vk, Tk,
+                                          scratch.data_ptr(), L.ptr(sums), L.ptr(verts_k) if mean and Vk else None,
+                                          L.ptr(tris_k) if Tk else None, L.ptr(first) if Vk else None,
+                                          L.ptr(cluster) if V else None, L.current_stream(dev)), "mf_simplify_mesh_emit")
+    return verts_k, tris_k, first, cluster
+
+
 def lattice(N_grid, device):
     """visualize_mesh's query points (trainer_moco_flow.py:490-498): np.linspace(-1.5, 1.5, N) in float64 cast to fp32, laid
     out as np.stack(np.meshgrid(x, y, z), -1).reshape(-1, 3) ('xy' indexing: point (a, b, c) is (x[b], y[a], z[c]))."""
@@ -243,7 +361,7 @@ def _sparse_volume(N_grid, nerf, nerf_embedding_xyz, occupancy, margin, bw_nof, 
 
 
 def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                 precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=1):
+                 precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=1, simplify=None):
     """visualize_mesh (trainer_moco_flow.py:490-538) up to the file: raw sigma of the NeRF on the N_grid^3 lattice over
     [-1.5, 1.5]^3 (query_sigma; with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow, ``ind`` =
     frame_idx * 2 / num_frames - 1), the isosurface of max(sigma, 0) at ``sigma_threshold``, then the reference's
@@ -257,7 +375,12 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
     and is 0 -- the empty side under the clamp -- everywhere else; no lattice tensor is built, and the call reads one more
     count from the device.  The mesh equals the dense one, bit for bit, exactly when every cell that crosses the threshold
     has its eight corners in active bricks.  A grid from a coarse pass can miss a thin part: that belongs to the grid's
-    ``dilate`` and to a coarse threshold below ``sigma_threshold``, which nobody has validated on a trained checkpoint."""
+    ``dilate`` and to a coarse threshold below ``sigma_threshold``, which nobody has validated on a trained checkpoint.
+
+    ``simplify`` (not in the reference; None leaves the path as it was, byte for byte): the edge of a clustering cell in
+    lattice steps, e.g. ``simplify=4``.  simplify_mesh runs on the raw isosurface in index coordinates, after the component
+    filter and before the post-processing, with lo = 0 and hi = N_grid - 1 (known on the host: no extra read) and
+    ``placement="mean"``."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_mesh")
     with torch.no_grad():
@@ -270,13 +393,15 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
         verts, tris = marching_cubes(sigma.view(N_grid, N_grid, N_grid), sigma_threshold, clamp_zero=True)
         if keep_largest is not None or min_triangles is not None:
             verts, tris = filter_components(verts, tris, keep_largest, min_triangles)
+        if simplify is not None:
+            verts, tris = simplify_mesh(verts, tris, simplify, lo=(0.0,) * 3, hi=(N_grid - 1.0,) * 3, placement="mean")
         verts = verts[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
     return verts, tris
 
 
 def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                         precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=2):
+                         precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=2, simplify=None):
     """extract_mesh with what a coloured mesh needs: (verts (V, 3), tris (T, 3), normals (V, 3), colors (V, 3)).
 
     verts / tris are extract_mesh's for the same arguments (``nerf_embeddings`` = [xyz, ind | None, dir | None] as
@@ -288,7 +413,12 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
     the filter runs before the radiance query, with the normals as a vertex attribute, so a dropped vertex is never
     queried.  ``occupancy`` / ``margin``: as in extract_mesh; the default margin is 2 because the normals' central
     differences read one lattice point beyond a crossing cell's corners -- normals equal the dense ones exactly when those
-    neighbours lie in active bricks as well."""
+    neighbours lie in active bricks as well.
+
+    ``simplify``: as in extract_mesh, positions by ``placement="mean"`` as well; it runs after the filter and before the
+    radiance query, so colours are queried at the simplified vertices only (the query gets cheaper by the vertex ratio).
+    The normal of a new vertex is the normal of ``first`` -- the row of its cell's smallest original vertex, carried as an
+    attribute byte for byte: a unit vector (or zero) already, not re-normalised and not averaged."""
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_colored_mesh")
     with torch.no_grad():
@@ -304,6 +434,9 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
         del sigma, volume
         if keep_largest is not None or min_triangles is not None:
             raw, tris, normals = filter_components(raw, tris, keep_largest, min_triangles, attrs=(normals,))
+        if simplify is not None:
+            raw, tris, normals = simplify_mesh(raw, tris, simplify, lo=(0.0,) * 3, hi=(N_grid - 1.0,) * 3, placement="mean",
+                                               attrs=(normals,))
         verts = raw[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
         if verts.shape[0] == 0:

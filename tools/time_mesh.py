@@ -19,8 +19,18 @@ per kept triangle (the filter), each over its time as a fraction of the 4.69 TB/
 only: the accesses to the parents are random and no share of a peak is claimed.  The host path these replace, in the same
 process where scipy is importable: the device -> host copy of the mesh, scipy.sparse.csgraph.connected_components, a numpy
 re-index to the largest component (once each; --no-host skips it).  --sparse: only extract_mesh end to end, without and behind
-an occupancy grid (query_sigma_lattice; the timings beside tools/time_lattice.py --sparse).  Usage: time_mesh.py [--no-host]
-[--components-only] [--sparse] [N ...]  (default 256 512)"""
+an occupancy grid (query_sigma_lattice; the timings beside tools/time_lattice.py --sparse).
+
+--simplify CELL: only the simplification leg (simplify_mesh, vertex clustering with a cell of CELL lattice steps) on both
+meshes of each size (default 512): its two steps by HIP events on the stream, median of 20 after 5 warm-ups -- the plan (cell
+ids, the duplicate table, survivors, the ranks of the used cells; scratch allocation included) and the emit (members' sums and
+minima, the mean positions, the re-indexed triangles; output allocation included) -- and simplify_mesh end to end with its
+read of the counts, both placements.  Beside each time the algorithmic bytes (plan: 12 B per vertex + 24 B per triangle read;
+emit: the same read, 20 B per new vertex + 24 B per kept triangle + 8 B per vertex of cluster written) over the 4.69 TB/s
+device-to-device copy rate -- information only: the table probes and the per-cell atomics are random accesses and no share
+of a peak is claimed.  The numpy oracle (tests/mesh_simplify_oracle.py) on the same mesh in the same process, once, where
+the mesh has at most 8 M triangles (--no-host skips it); it also checks the device's result bit for bit.
+Usage: time_mesh.py [--no-host] [--components-only] [--sparse] [--simplify CELL] [N ...]  (default 256 512)"""
 import os
 import statistics
 import sys
@@ -37,7 +47,9 @@ COPY_RATE = 6.29e12
 D2D_COPY_RATE = 4.69e12
 HOST = "--no-host" not in sys.argv
 COMPONENTS_ONLY = "--components-only" in sys.argv
-Ns = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or [256, 512]
+SIMPLIFY = float(sys.argv[sys.argv.index("--simplify") + 1]) if "--simplify" in sys.argv else None
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--simplify"]
+Ns = [int(a) for a in _args] or ([512] if SIMPLIFY is not None else [256, 512])
 dev = torch.device("cuda")
 sd = synth.nerf_state(0, regime="dense")
 sd["sigma.weight"] = sd["sigma.weight"] * np.float32(3.0)
@@ -118,6 +130,79 @@ def components_leg(what, N, verts, tris, mc_ms, sigma_ms=None):
         host_path(verts, tris)
 
 
+def time_events(f, warm=5, n=20):
+    """Median of n device times of f() in ms, by HIP events on the current stream, after `warm` calls."""
+    for _ in range(warm):
+        out = f()
+    ts = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = f()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts), out
+
+
+def simplify_leg(what, N, verts, tris, cell):
+    import ctypes
+    V, T = len(verts), len(tris)
+    d3 = ctypes.c_double * 3
+    grid = (d3(0, 0, 0), d3(N - 1, N - 1, N - 1), float(cell), *M.mesh._simplify_grid(np.zeros(3), np.full(3, N - 1.0), cell))
+    slots = 1 << (2 * T).bit_length()
+    ms_plan, (scratch, counts) = time_events(lambda: M.mesh._simplify_plan(verts, tris, grid, slots))
+    Vk, Tk, bad = counts.tolist()
+    ms_emit, _ = time_events(lambda: M.mesh._simplify_emit(verts, tris, grid, scratch, Vk, Tk, True))
+    kw = dict(lo=(0,) * 3, hi=(N - 1,) * 3)
+    ms_mean, out = time_events(lambda: M.simplify_mesh(verts, tris, cell, placement="mean", return_map=True, **kw))
+    ms_first, _ = time_events(lambda: M.simplify_mesh(verts, tris, cell, placement="first", **kw))
+    b_plan, b_emit = 12 * V + 24 * T, 12 * V + 24 * T + 20 * Vk + 24 * Tk + 8 * V
+    frac = lambda b, ms: b / (ms * 1e-3) / D2D_COPY_RATE
+    print(f"  simplify, {what} {N}^3, cell {cell}: V {V} -> {Vk}, T {T} -> {Tk} ({bad} bad), table of {slots} slots")
+    print(f"    plan  {ms_plan:9.3f} ms  ({b_plan / 1e9:.3f} GB algorithmic = {frac(b_plan, ms_plan):.3f} of the copy rate)")
+    print(f"    emit  {ms_emit:9.3f} ms  ({b_emit / 1e9:.3f} GB algorithmic = {frac(b_emit, ms_emit):.3f} of the copy rate)")
+    print(f"    simplify_mesh end to end, with its read of the counts: mean {ms_mean:9.3f} ms, first {ms_first:9.3f} ms", flush=True)
+    if not HOST:
+        return
+    if T > 8_000_000:
+        print(f"    numpy oracle: not measured ({T} triangles: np.unique on the cell triples needs tens of GB and minutes)", flush=True)
+        return
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import mesh_simplify_oracle as S
+    t0 = time.perf_counter()
+    v, t = verts.cpu().numpy(), tris.cpu().numpy()
+    t1 = time.perf_counter()
+    want = S.simplify(v, t, cell, (0,) * 3, (N - 1,) * 3)
+    t2 = time.perf_counter()
+    same = all(torch.equal(g.cpu(), torch.from_numpy(w)) for g, w in zip(out, want))
+    print(f"    numpy oracle: device -> host copy {1e3 * (t1 - t0):8.1f} ms, simplify {1e3 * (t2 - t1):10.1f} ms; the device's result "
+          f"{'equals it bit for bit' if same else 'DIFFERS'}", flush=True)
+
+
+if SIMPLIFY is not None:
+    print(f"simplify_mesh (vertex clustering, cell {SIMPLIFY} lattice steps) on the marching-cubes meshes of the f32 sigma lattice "
+          "(threshold 10) and of the smooth field (0.3)")
+    for N in Ns:
+        with torch.no_grad():
+            xyz = M.mesh.lattice(N, dev)
+            vol = M.query_sigma(xyz, nerf, emb).view(N, N, N)
+            del xyz
+        verts, tris = M.marching_cubes(vol, 10.0, clamp_zero=True)
+        del vol
+        simplify_leg("test NeRF sigma at 10", N, verts, tris, SIMPLIFY)
+        del verts, tris
+        torch.cuda.empty_cache()
+        ax = torch.linspace(0, 1, N, device=dev)
+        x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+        vol = (torch.sin(6.0 * x + 2.0 * y * y) + torch.sin(5.0 * y + 3.0 * z) + torch.sin(7.0 * z + 4.0 * x * y)).contiguous()
+        del x, y, z
+        verts, tris = M.marching_cubes(vol, 0.3)
+        del vol
+        simplify_leg("smooth field", N, verts, tris, SIMPLIFY)
+        del verts, tris
+        torch.cuda.empty_cache()
+    sys.exit(0)
 if "--sparse" in sys.argv:
     # extract_mesh end to end without and behind a grid: tools/time_occupancy.py's capsule scaled to the mesh lattice's box
     # [-1.5, 1.5]^3 (about 10 % of it), as a 128^3 grid dilated by 1.  The random NeRF crosses the threshold wherever it is
