@@ -154,7 +154,12 @@ int32_t mf_nof_pack_p(const mf_nof_desc* d, int32_t precision, void* packed, voi
  * the default NeRF); the resident block has the same size and offsets, its extra bias is b' and the final layer's bias slot is
  * unused.  A small kernel in front of the pack computes W' and b' -- float64 sums over ascending k, rounded to fp32 once, no
  * atomics: packs are bit-identical -- into a scratch area of round_up((W/2 * W + W/2) * 4, 1024) bytes (129 KiB) that is
- * appended behind the panels and counted by mf_nerf_fold_packed_bytes.  fp32 and W = 256 only (0 / MF_E_UNSUPPORTED otherwise);
+ * appended behind the panels and counted by mf_nerf_fold_packed_bytes.  The extra block W_e[:, W:] ext is the same for every
+ * sample of a ray: the stream's extra_encoding panels hold W' alone (32 groups each; 2048 groups in all for the default NeRF,
+ * where they were 2064) and W_e[:, W:] follows the scratch area as W/2 rows of 32 (dir) | 16 (ind) | 0 (none) floats, natural
+ * column order, zero-padded -- the bytes its k-quads took in the panels, so mf_nerf_fold_packed_bytes returns what it did.  The
+ * pass adds it to b' once per ray.  The layout is private to the library (pack and pass must come from the same build); the
+ * C ABI and MF_ABI_VERSION are unchanged.  fp32 and W = 256 only (0 / MF_E_UNSUPPORTED otherwise);
  * extra_feat_type dir, ind or none.  Read by mf_render_pass with MF_F_FOLDED_FINAL; every other entry point takes the
  * streams of mf_nerf_pack*.  Must be re-run whenever the parameters change. */
 int64_t mf_nerf_fold_packed_bytes(const mf_nerf_desc* d);

@@ -236,6 +236,10 @@ MF_HD int extra_groups(const NetLayout& L) {
   if (L.bf16) return (((L.hsplit_mask >> L.n_trunk) & 1) ? L.terms : 1) * L.NK + (L.emb_split ? L.terms : 1) * L.extra_steps;
   return 2 * (hidden_batches(L) + L.extra_steps / 4);
 }
+// the folded fp32 stream (FoldLayout, mf_layout.hpp): extra_encoding's panels hold the hidden block alone; the extra block's
+// weight columns wait behind the panels, fold_ext_cols floats per output row (32: dir, 16: ind, 0: none)
+MF_HD int fold_extra_groups(const NetLayout& L) { return 2 * hidden_batches(L); }
+MF_HD int fold_ext_cols(const NetLayout& L) { return 4 * L.extra_steps; }
 
 // MF_PREC_BF16X3: a tile's groups stream as ONE panel up to 32 groups, as two halves beyond (the 3-slot LDS ring holds
 // 32 KiB slots; the groups of a tile are contiguous in the packed buffer, so a panel boundary is only a barrier position)

@@ -73,14 +73,19 @@ constexpr uint32_t kRenderLdsCap = 160 * 1024;   // LDS of one render workgroup
 // keeps at most one wave per ray busy and costs two workgroup barriers (~4 k cycles per 128-sample tile at G = 2 in the fp32
 // pass: tools/timeline.py), so it should come once per several tiles -- as long as the CUs' shares stay what they were (same
 // makespan in rays).
-inline int plan_ray_groups(long long n_rays, int S, int tile, uint32_t lds, int& G, long long& n_groups) {
-  const int max_samples = lds < kRenderLdsCap ? (int)((kRenderLdsCap - lds) / 20) : 0;
-  if (S > max_samples) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
+// `ray_bytes`: what the kernel stages per RAY of the group besides (the folded fp32 kernels' bias row and encoding, mf_render.hip).
+inline int plan_ray_groups(long long n_rays, int S, int tile, uint32_t lds, int& G, long long& n_groups, uint32_t ray_bytes = 0) {
+  const long long room = lds < kRenderLdsCap ? (long long)(kRenderLdsCap - lds) : 0;
+  auto fits = [&](long long g) {       // (the per-ray rows sit behind place_sample_buffers' padding to 16 bytes)
+    return (ray_bytes ? ((g * S * 20 + 15) & ~15ll) + g * (long long)ray_bytes : g * S * 20) <= room;
+  };
+  const int max_samples = (int)((room > ray_bytes ? room - ray_bytes : 0) / 20);      // of a single ray
+  if (!fits(1)) return fail(MF_E_UNSUPPORTED, "mf_render_pass: n_samples=%d exceeds the %d samples a workgroup can stage", S, max_samples);
   G = 1;
-  while ((G * S) % tile != 0 && (G + 1) * S <= max_samples && G < 64) ++G;
+  while ((G * S) % tile != 0 && fits(G + 1) && G < 64) ++G;
   if ((G * S) % tile != 0) {
     int best = 1; double best_eff = 0;
-    for (int g = 1; g * S <= max_samples && g <= 64; ++g) {
+    for (int g = 1; fits(g) && g <= 64; ++g) {
       const int tiles = (g * S + tile - 1) / tile;
       const double eff = (double)(g * S) / (tiles * tile);
       if (eff > best_eff + 1e-9) { best_eff = eff; best = g; }
@@ -92,7 +97,7 @@ inline int plan_ray_groups(long long n_rays, int S, int tile, uint32_t lds, int&
   const long long base = makespan(G);
   int sets = 1;
   for (int c = 2; c <= 8; ++c)
-    if ((long long)G * c * S <= max_samples && (long long)G * c <= 64 && makespan((long long)G * c) <= base) sets = c;
+    if (fits((long long)G * c) && (long long)G * c <= 64 && makespan((long long)G * c) <= base) sets = c;
   G *= sets;
   n_groups = (n_rays + G - 1) / G;
   return MF_OK;

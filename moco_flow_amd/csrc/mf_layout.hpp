@@ -135,18 +135,28 @@ inline bool nerf_layout(const mf_nerf_desc& d, NetLayout& L, int bf16 = 0) {
 // resident block keeps its size and offsets (the final layer's bias slot is unused, off_bias_extra holds b').  L stays the
 // unfolded layout: the kernels read the same offsets and panel sizes from it.  W' ((W/2) x W, row-major) and b' (W/2) live in
 // a scratch area behind the panels, padded to a whole group; it belongs to the packed buffer.  fp32 and W = 256 only.
+// The extra block (rendering.py:133-142: the encoding of the ray's direction or image index) is the same for every sample of a
+// ray, so the folded kernels add W_e[:, W:] PE(ext) to b' once per ray (mf_render_body.hpp, the per-ray bias table) and the
+// stream's extra panels carry the hidden block alone: fold_extra_groups = 32 groups per panel, 2 048 in all instead of 2 064
+// for a 27-column block.  W_e[:, W:] sits behind W' and b' for that phase: W/2 rows in natural order, fold_ext_cols floats
+// each (the block's columns, zero-padded) -- exactly the bytes the extra k-quads occupied in the panels, so the packed buffer
+// keeps its size.  (fold_extra_groups, fold_ext_cols: mf_core.hpp)
 struct FoldLayout {
   int64_t panel_bytes;       // the folded stream's panels
-  int64_t scratch_bytes;     // W' then b'
+  int64_t scratch_bytes;     // W' then b' (padded to a group), then W_e[:, W:]
   int64_t off_w, off_b;      // byte offsets of W' and b' in the packed buffer
+  int64_t off_x;             // byte offset of W_e[:, W:] ((W/2) x fold_ext_cols, row-major)
 };
 inline bool nerf_fold_layout(const mf_nerf_desc& d, NetLayout& L, FoldLayout& F) {
   F = FoldLayout{};
   if (!nerf_layout(d, L, 0) || L.W != 256) return false;
-  F.panel_bytes = L.panel_bytes - (int64_t)trunk_groups(L, L.n_trunk - 1) * L.NP * kGroupBytes;
-  F.scratch_bytes = round_up(((int64_t)(L.W / 2) * L.W + L.W / 2) * 4, kGroupBytes);
+  F.panel_bytes = L.panel_bytes - (int64_t)trunk_groups(L, L.n_trunk - 1) * L.NP * kGroupBytes -
+                  (int64_t)(extra_groups(L) - fold_extra_groups(L)) * (L.NP / 2) * kGroupBytes;
+  const int64_t wb_bytes = round_up(((int64_t)(L.W / 2) * L.W + L.W / 2) * 4, kGroupBytes);
+  F.scratch_bytes = wb_bytes + (int64_t)(L.W / 2) * fold_ext_cols(L) * 4;
   F.off_w = L.res_bytes + F.panel_bytes;
   F.off_b = F.off_w + (int64_t)(L.W / 2) * L.W * 4;
+  F.off_x = F.off_w + wb_bytes;
   return true;
 }
 

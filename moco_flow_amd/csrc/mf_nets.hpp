@@ -102,16 +102,89 @@ MF_D void extra_layer(const NetDev& net, const f32x4 (&act)[NK],
   }
 }
 
+// extra_encoding of the folded stream whose extra block is a per-ray bias (render_fold_kernel, mf_render_body.hpp): the panels
+// hold the hidden block alone, so the layer is a plain out_pair per panel; `bias_off` is the LANE's LDS byte offset of its
+// ray's row b' + W_e[:, W:] PE(ext) of the group's bias table (or, uniform, the layer's shared bias vector b').
+MF_D NextLayer next_extra_fold(const NetDev& n, uint32_t bias_off) {
+  NextLayer f;
+  f.groups = fold_extra_groups(n.L);
+  f.jump = nullptr;
+  f.bias_off = bias_off;
+  return f;
+}
+template <int NK>
+MF_D void extra_layer_fold(const NetDev& net, const f32x4 (&act)[NK], f32x4 (&out)[NK / 2], uint32_t bias_off,
+                           Stream& st, CarryT<kPD>& carry, const LaneId& id, const NextLayer& nxt) {
+  constexpr int NPO = NK / 4;
+  const int groups = fold_extra_groups(net.L);
+  const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < NPO; ++t) {
+    const uint32_t p = st.slot_off(0) + id.lane * 16;
+    const uint32_t pn = st.slot_off(1) + id.lane * 16;
+    const uint32_t nb = (t + 1 < NPO) ? bias_off + 32 * (t + 1) * 4 : nxt.bias_off;
+    auto hook = [&](int ph) { st.sync_and_dma(t + 2 < NPO ? groups : nxt.groups, t == NPO - 2 ? nxt.jump : nullptr, id, ph); };
+    out_pair<2, NK, 4>(carry, act, dummy, p, pn, nb, id.g, id.wave < kWaves / 2 && !(st.dbg & 64), hook, 0.f, out[2 * t],
+                       out[2 * t + 1]);
+    st.advance();
+  }
+}
+
+// Layer 0 of the folded kernels in LONG panels.  Its panels are a quarter of the others' length (K = 64: 32 MFMAs per wave against
+// 128-160), yet each pays a panel's barrier and LDS-DMA issue.  The stream's bytes are what they were -- layer 0's eight panels of
+// eight groups are contiguous -- but one LDS-DMA and ONE barrier cover kLongPairs output-tile pairs (32 groups, which
+// fit a ring slot): the early half of the workgroup meets at the first pair's leading MFMAs, the late half at the middle pair's.
+// Every pair is out_pair's own sequence, so the accumulation order and the results are untouched.
+constexpr int kLongPairs = 4;
+MF_D int long_groups(const NetDev& n) { return kLongPairs * trunk_groups(n.L, 0); }
+MF_D NextLayer follow_of_long(const NetDev& n) {           // follow_of for a network whose layer 0 streams in long panels
+  NextLayer f = follow_of(n);
+  f.groups = long_groups(n);
+  return f;
+}
+template <int PD>
+MF_D void start_program_long(const NetDev& n, Stream& st, CarryT<PD>& carry, const LaneId& id) {
+  st.start(first_panel(n), long_groups(n), id);
+  carry.load(st.slot_off(0) + id.lane * 16, n.res_lds + n.L.off_bias_trunk * 4, id.g);
+}
+template <int NK, int EMB>
+MF_D void trunk_layer0_long(const NetDev& net, f32x4 (&act)[NK], const float (&emb)[EMB], Stream& st, CarryT<kPD>& carry,
+                            const LaneId& id, const NextLayer& nxt) {
+  constexpr int NP = NK / 2;
+  static_assert(NP % kLongPairs == 0 && NP / kLongPairs == 2, "both long panels' DMA (two ahead) is the next layer's");
+  constexpr uint32_t pair_bytes = 2 * (EMB / 4) * kGroupBytes;
+  const float lo = (net.L.relu_mask & 1) ? 0.f : -__builtin_inff();
+  const uint32_t bias_off = net.res_lds + net.L.off_bias_trunk * 4;
+  const bool late = id.wave < kWaves / 2 && !(st.dbg & 64);
+#pragma unroll
+  for (int sp = 0; sp < NP / kLongPairs; ++sp) {
+    const uint32_t p = st.slot_off(0) + id.lane * 16;
+    const uint32_t pn = st.slot_off(1) + id.lane * 16;
+#pragma unroll
+    for (int i = 0; i < kLongPairs; ++i) {
+      const int t = sp * kLongPairs + i;
+      const uint32_t nb = (t + 1 < NP) ? bias_off + 32 * (t + 1) * 4 : nxt.bias_off;
+      // out_pair places an early wave's hook behind its first MFMA pair: pair 0 for the early half, the middle pair for the late
+      auto hook = [&](int ph) { if (i == (late ? kLongPairs / 2 : 0)) st.sync_and_dma(nxt.groups, nullptr, id, ph); };
+      out_pair<1, NK, EMB>(carry, act, emb, p + i * pair_bytes, i + 1 < kLongPairs ? p + (i + 1) * pair_bytes : pn, nb, id.g, false,
+                           hook, lo, act[2 * t], act[2 * t + 1]);          // (MODE 1 reads no hidden input: in place)
+    }
+    st.advance();
+  }
+}
+
 // Canonical NeRF on this wave's 16 samples.  `follow`: the first layer of whatever the panel
 // program evaluates after this network (the stream jumps there behind the last panel used).
 // DUMP (training forward): `dump_row` = this lane's sample row [h_0 .. h_{D-1} | final | extra] (nullptr: skip).
 // FOLD (fp32 inference, MF_F_FOLDED_FINAL): the stream of mf_nerf_pack_fold -- extra_encoding's panels (W' = W_e[:, :W] W_f in
 // their hidden block, b' as their bias) follow trunk layer D - 1 and read its output; xyz_encoding_final is not evaluated.
-template <int NK, bool DUMP = false, bool FOLD = false>
+// Its extra block is the lane's bias row `ray_bias` (extra_layer_fold); `ext` is not read.
+// LONG0: layer 0 streams in long panels (trunk_layer0_long): whoever runs in front of the network follows with follow_of_long.
+template <int NK, bool DUMP = false, bool FOLD = false, bool LONG0 = false>
 MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const float (&ext)[kStepsExtraMax],
                     bool sigma_only, Stream& st, CarryT<kPD>& carry, const LaneId& id,
                     const NextLayer& follow, float& sigma, float (&rgb)[3], float* dump_row = nullptr,
-                    unsigned* mask_row = nullptr) {
+                    unsigned* mask_row = nullptr, uint32_t ray_bias = 0) {
   f32x4 act[NK];
 #pragma unroll
   for (int t = 0; t < NK; ++t)
@@ -121,8 +194,15 @@ MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const
   const int D = net.L.n_trunk - 1;
   for (int l = 0; l < D; ++l) {
     const bool last = sigma_only && l == D - 1;
+    if constexpr (LONG0) {
+      if (l == 0) {                                        // (D >= 2: layer 1 follows)
+        trunk_layer0_long<NK, kStepsNerfXyz>(net, act, embx, st, carry, id, next_trunk(net, 1));
+        st.tl.stamp(10, id);
+        continue;
+      }
+    }
     trunk_layer<NK, kStepsNerfXyz, DUMP>(net, l, act, embx, st, carry, id,
-                                               last ? follow : ((FOLD && l == D - 1) ? next_extra(net) : next_trunk(net, l + 1)),
+                                               last ? follow : ((FOLD && l == D - 1) ? next_extra_fold(net, ray_bias) : next_trunk(net, l + 1)),
                                                dump_row ? dump_row + l * net.L.W : nullptr, mask_row ? mask_row + l * 8 : nullptr);
     st.tl.stamp(10 + l, id);
   }
@@ -138,6 +218,8 @@ MF_D void nerf_eval(const NetDev& net, const float (&embx)[kStepsNerfXyz], const
   }
   st.tl.stamp(31, id);
   f32x4 e[NK / 2];
+  if constexpr (FOLD) extra_layer_fold<NK>(net, act, e, ray_bias, st, carry, id, follow);
+  else
   extra_layer<NK, DUMP>(net, act, ext, e, st, carry, id, follow, dump_row ? dump_row + (D + 1) * net.L.W : nullptr,
                         mask_row ? mask_row + (D + 1) * 8 : nullptr);
   st.tl.stamp(33, id);

@@ -5,7 +5,8 @@
 // need.  It is a pure permutation + zero padding: every packed float is either one source
 // weight or 0 -- with ONE exception, the folded fp32 stream (mf_nerf_pack_fold): its extra_encoding
 // panels hold W' = W_e[:, :W] W_f and its extra bias b' = b_e + W_e[:, :W] b_f, which fold_final_kernel
-// computes in front of the pack (float64 sums in ascending k, rounded once).  One kernel writes every stream from a region list (PackJob, mf_layout.hpp):
+// computes in front of the pack (float64 sums in ascending k, rounded once); the extra block's columns W_e[:, W:] are not in
+// that stream's panels but behind them in natural order, for the folded kernels' per-ray bias.  One kernel writes every stream from a region list (PackJob, mf_layout.hpp):
 // the forward's here, each backward chain's -- the same layout of W^T -- next to the kernel
 // that reads it (mf_backward.hip, mf_nofgrad.hip, mf_backward_bf16.hip, mf_nofgrad_bf16.hip).
 #include <hip/hip_fp16.h>
@@ -141,12 +142,18 @@ __global__ void pack_ind_kernel(IndJob job) {
 // Wp[n][k] = sum_j We[n][j] Wf[j][k], the first W / 2 threads also bp[n] = be[n] + sum_j We[n][j] bf[j].  Every product of two
 // floats is exact in float64; the sums run over j ascending in float64 and are rounded to fp32 once.  No atomics: two packs of
 // the same weights are bit-identical.
-struct FoldJob { const float *We, *Wf, *be, *bf; int W, ld_e; float *Wp, *bp; };
+// The first (W / 2) * xcols threads also copy the extra block's columns: Wx[n][c] = We[n][W + c], 0 past the block's `ext` columns
+// (FoldLayout::off_x: what the folded kernels' per-ray bias phase reads).
+struct FoldJob { const float *We, *Wf, *be, *bf; int W, ld_e; float *Wp, *bp; float* Wx; int xcols, ext; };
 
 __global__ void fold_final_kernel(FoldJob job) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const int half = job.W / 2;
   if (idx >= half * job.W) return;
+  if (idx < half * job.xcols) {
+    const int n = idx / job.xcols, c = idx % job.xcols;
+    job.Wx[idx] = c < job.ext ? job.We[(long long)n * job.ld_e + job.W + c] : 0.f;
+  }
   const int n = idx / job.W, k = idx % job.W;
   const float* we = job.We + (long long)n * job.ld_e;
   double acc = 0.0;
@@ -232,10 +239,10 @@ static int32_t nerf_pack(const mf_nerf_desc* d, int32_t precision, void* packed,
     const float* W = d->extra_w;
     if (!W) return fail(MF_E_INVALID, "mf_nerf_pack: missing extra_encoding weight");
     const int kind = d->extra_feat_type == MF_EXTRA_DIR ? kEmbDir : (d->extra_feat_type == MF_EXTRA_IND ? kEmbInd : kEmbNone);
-    job.add(L.NP / 2, extra_groups(L),
-            fold ? PackBlock{fold_w, L.W, 1, kPackHidden, hidden_batches(L), 1, L.W}
-                 : PackBlock{W, L.W + ext, 1, kPackHidden, hidden_batches(L), ((L.hsplit_mask >> L.n_trunk) & 1) ? L.terms : 1, L.W},
-            PackBlock{W + L.W, L.W + ext, 1, kind, L.extra_steps / equad, esplit, ext});
+    if (fold) job.add(L.NP / 2, fold_extra_groups(L), PackBlock{fold_w, L.W, 1, kPackHidden, hidden_batches(L), 1, L.W});   // hidden block only
+    else job.add(L.NP / 2, extra_groups(L),
+                 PackBlock{W, L.W + ext, 1, kPackHidden, hidden_batches(L), ((L.hsplit_mask >> L.n_trunk) & 1) ? L.terms : 1, L.W},
+                 PackBlock{W + L.W, L.W + ext, 1, kind, L.extra_steps / equad, esplit, ext});
     if (fold && (!d->extra_b || !d->final_b)) return fail(MF_E_INVALID, "mf_nerf_pack: missing bias pointer of the folded layers");
     rj.c[rj.n++] = ResCopy{fold ? fold_b : d->extra_b, L.off_bias_extra, L.W / 2};
   }
@@ -257,7 +264,8 @@ static int32_t nerf_pack(const mf_nerf_desc* d, int32_t precision, void* packed,
   if (job.total_groups * kGroupBytes != panel_bytes) return fail(MF_E_INVALID, "mf_nerf_pack: layout mismatch");
   if (fold) {
     const int ext = d->extra_feat_type == MF_EXTRA_NONE ? 0 : d->extra_feat_dim;
-    const FoldJob fj{d->extra_w, d->final_w, d->extra_b, d->final_b, L.W, L.W + ext, fold_w, fold_b};
+    const FoldJob fj{d->extra_w, d->final_w, d->extra_b, d->final_b, L.W, L.W + ext, fold_w, fold_b,
+                     reinterpret_cast<float*>(static_cast<char*>(packed) + F.off_x), fold_ext_cols(L), ext};
     hipLaunchKernelGGL(fold_final_kernel, dim3((L.W / 2) * L.W / 256), dim3(256), 0, static_cast<hipStream_t>(stream), fj);
     if (int e = check_launch("mf_nerf_pack_fold")) return e;
   }

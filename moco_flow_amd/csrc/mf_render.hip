@@ -47,19 +47,34 @@ struct RenderParams {
   float* dump_nof_acts; long long dump_nof_stride; float* dump_nof_emb; float* dump_nof_out;   // per chain step
   uint32_t nof_plane_pack;     // plane of step k = (pack >> 3k) & 7   (a packed scalar: no runtime index into the kernarg)
 };
+// render_fold_kernel's parameters: RenderParams (the other kernels' kernarg stays what it was) and the group's per-ray bias table
+// of extra_encoding, b' + W_e[:, W:] PE(ext): G rows of W/2 floats at rbias_off, behind them the rays' encodings (kRayPeFloats
+// each); fold_wx = W_e[:, W:] in the packed buffer (FoldLayout::off_x), fold_xcols floats per row.  fold_wx null: no table
+// (sigma-only pass, no extra block) -- every lane reads the layer's shared bias b'.
+struct FoldRenderParams : RenderParams {
+  const float* fold_wx; int fold_xcols;
+  uint32_t rbias_off;
+};
+constexpr int kRayPeFloats = 32;          // an extra block's encoding, natural feature order, zero-padded (fold_ext_cols <= 32)
+constexpr int kFoldHalf = 128;            // W / 2 of the folded kernels (W = 256 only)
 
+// MF_BODY_FOLD: the body's text for the folded kernels (preprocessor, not `if constexpr`: it names FoldRenderParams' fields)
 template <bool MOCO, bool DUMP>
 __global__ __launch_bounds__(kThreads, 2) void render_kernel(RenderParams p) {
   constexpr bool FOLD = false;
+#define MF_BODY_FOLD 0
 #include "mf_render_body.hpp"
+#undef MF_BODY_FOLD
 }
 
 // the two inference instantiations over the folded stream (MF_F_FOLDED_FINAL: nerf_eval<.., FOLD> skips xyz_encoding_final);
 // kernels of their own name, so that render_kernel<MOCO, DUMP> keeps its names
 template <bool MOCO>
-__global__ __launch_bounds__(kThreads, 2) void render_fold_kernel(RenderParams p) {
+__global__ __launch_bounds__(kThreads, 2) void render_fold_kernel(FoldRenderParams p) {
   constexpr bool DUMP = false, FOLD = true;
+#define MF_BODY_FOLD 1
 #include "mf_render_body.hpp"
+#undef MF_BODY_FOLD
 }
 
 int render_pass_bf16(const mf_render_args* a, hipStream_t st, bool prepare_only);   // mf_render_bf16.hip
@@ -135,7 +150,7 @@ static int32_t check_render_args(const mf_render_args* a, NetLayout (&L)[3]) {
 static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3], hipStream_t st) {
   const bool moco = a->nof_bw != nullptr;
   const bool chains = a->flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL);
-  RenderParams p{};
+  FoldRenderParams p{};                    // (the unfolded kernels take its RenderParams)
   fill_render_io(p, a);
   p.dbg = debug_flags();
   LdsPlan plan;
@@ -153,8 +168,28 @@ static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3],
   plan.ring(p.ring_off, p.buf_bytes);
   uint32_t lds = plan.lds;                 // the group's sample buffers go behind the ring
 
-  if (int e = plan_ray_groups(a->n_rays, a->n_samples, kTile, lds, p.G, p.n_groups)) return e;
+  // the folded kernels' per-ray bias table: one row of W/2 floats and one encoding per ray of the group, beside the 20 bytes per
+  // staged sample -- where that leaves no room for the ray sets a group had, plan_ray_groups takes fewer
+  FoldLayout F{};
+  NetLayout Lf;
+  const bool ray_table = (a->flags & MF_F_FOLDED_FINAL) && !(a->flags & MF_F_SIGMA_ONLY) &&
+                         a->nerf->extra_feat_type != MF_EXTRA_NONE && nerf_fold_layout(*a->nerf, Lf, F);
+  uint32_t ray_bytes = ray_table ? (kFoldHalf + kRayPeFloats) * 4 : 0;
+  // A ray so long that its samples leave no room for one row (the envelope: S up to all the LDS behind the ring): the group is
+  // that single ray, and its row and encoding live in the resident block's bias slot of xyz_encoding_final (W floats), which the
+  // folded kernels never read.
+  const bool home_row = ray_table && lds < kRenderLdsCap && (long long)a->n_samples * 20 + ray_bytes > (long long)(kRenderLdsCap - lds);
+  if (home_row) ray_bytes = 0;
+  if (int e = plan_ray_groups(a->n_rays, a->n_samples, kTile, lds, p.G, p.n_groups, ray_bytes)) return e;
+  if (home_row) { p.G = 1; p.n_groups = a->n_rays; }
   place_sample_buffers(p, lds);
+  if (ray_table) {
+    static_assert((kFoldHalf + kRayPeFloats) <= 2 * kFoldHalf, "one row and one encoding fit a W-float bias slot");
+    p.fold_wx = reinterpret_cast<const float*>(static_cast<const char*>(a->nerf_packed) + F.off_x);
+    p.fold_xcols = fold_ext_cols(Lf);
+    if (home_row) p.rbias_off = p.nerf.res_lds + (uint32_t)(p.nerf.L.off_bias_trunk + (p.nerf.L.n_trunk - 1) * p.nerf.L.W) * 4;
+    else { p.rbias_off = lds; lds += (uint32_t)p.G * ray_bytes; }      // G rows, then G encodings
+  }
 
   if (int e = check_dump_rows(a, p.nerf.L)) return e;
   if (int e = check_dump_mask(a, p.nerf.L)) return e;
@@ -168,11 +203,13 @@ static int32_t render_pass_f32(const mf_render_args* a, const NetLayout (&L)[3],
   }
   p.dump_nof_acts = a->dump_nof_acts; p.dump_nof_stride = a->dump_nof_stride; p.dump_nof_emb = a->dump_nof_emb; p.dump_nof_out = a->dump_nof_out;
   const bool dump = a->dump_acts || a->dump_rgbsigma || a->dump_xyz || a->dump_nof_acts;
-  void (*kern)(RenderParams) =
-      dump ? (moco ? render_kernel<true, true> : render_kernel<false, true>)
-           : (a->flags & MF_F_FOLDED_FINAL) ? (moco ? render_fold_kernel<true> : render_fold_kernel<false>)
-           : (moco ? render_kernel<true, false> : render_kernel<false, false>);
-  return launch_lds(kern, persistent_grid(p.n_groups), kThreads, lds, st, p, "mf_render_pass", "mf_render_pass");
+  if (!dump && (a->flags & MF_F_FOLDED_FINAL))
+    return launch_lds(moco ? render_fold_kernel<true> : render_fold_kernel<false>, persistent_grid(p.n_groups), kThreads, lds, st, p,
+                      "mf_render_pass", "mf_render_pass");
+  void (*kern)(RenderParams) = dump ? (moco ? render_kernel<true, true> : render_kernel<false, true>)
+                                    : (moco ? render_kernel<true, false> : render_kernel<false, false>);
+  return launch_lds(kern, persistent_grid(p.n_groups), kThreads, lds, st, static_cast<const RenderParams&>(p), "mf_render_pass",
+                    "mf_render_pass");
 }
 
 static int32_t render_entry(const mf_render_args* a, void* stream, bool prepare_only) {

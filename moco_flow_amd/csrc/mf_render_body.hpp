@@ -3,6 +3,7 @@
 // is the folded stream of mf_nerf_pack_fold, inference only).  A body and not a function template: render_kernel<MOCO, DUMP>
 // keeps its names and compiles to the code it had before the folded kernels existed -- behind a forced-inline call the same
 // source came out with another register allocation in all four instantiations.
+// MF_BODY_FOLD (0 | 1, defined around the #include): the text of the folded kernels alone -- `p` is their FoldRenderParams there.
   const LaneId id;
   const NetDev nerf = p.nerf;
   const WgClock wg;
@@ -11,7 +12,7 @@
     load_resident(p.bw, id);
     if (p.flags & (MF_F_CHAIN_LOCAL | MF_F_CHAIN_GLOBAL)) load_resident(p.fw, id);
   }
-  emb_tables_to_lds(p);
+  emb_tables_to_lds<RenderParams>(p);
   const uint32_t par_nerf_xyz = p.par_off, par_nerf_ext = p.par_off + 128, par_nof_xyz = p.par_off + 256,
                  par_nof_ind = p.par_off + 384;
   Stream st;
@@ -19,9 +20,16 @@
   st.open(p.ring_off, p.buf_bytes, MF_TIMING_FLAGS ? p.dbg : 0);
   st.tl.start(p.alphas, id);
   // the panel program of a tile: [bw NoF, fw NoF chains,] NeRF, then around again
+#if MF_BODY_FOLD   // (the NeRF-only folded kernel streams layer 0 in long panels: trunk_layer0_long, mf_nets.hpp; behind the NoF chains
+                   //  the MoCo kernel keeps the short ones -- with long panels it spilled 7 VGPRs)
+  const NextLayer prog_first = MOCO ? follow_of(p.bw) : follow_of_long(nerf);
+  if (MOCO) start_program(p.bw, st, carry, id);
+  else start_program_long(nerf, st, carry, id);
+#else
   const NextLayer prog_first = MOCO ? follow_of(p.bw) : follow_of(nerf);
   if (MOCO) start_program(p.bw, st, carry, id);
   else start_program(nerf, st, carry, id);
+#endif
 
   const int S = p.S;
   const bool sigma_only = p.flags & MF_F_SIGMA_ONLY;
@@ -33,6 +41,65 @@
     const int nr = (int)((p.n_rays - ray0) < p.G ? (p.n_rays - ray0) : p.G);
     const int nsamp = nr * S;
     const int ntiles = (nsamp + kTile - 1) / kTile;
+
+#if MF_BODY_FOLD
+    {
+      // The extra block of extra_encoding (rendering.py:133-142) is the same for every sample of a ray: once per group,
+      //   row[r][o] = b'[o] + sum_k W_e[o, W + k] PE(ext_r)[k]      (fp32 fmaf from b', k ascending in the reference's column order)
+      // for the group's rays, which the tiles' lanes take as their accumulators' initial value (nerf_eval's ray_bias).
+      if (p.fold_wx) {
+        const int t = threadIdx.x;
+        const uint32_t rpe_off = p.rbias_off + (uint32_t)p.G * (kFoldHalf * 4);         // the encodings sit behind the G rows
+        // (thread t's row o = t % (W/2) of W_e[:, W:], asked for first: the loads fly while the encodings are evaluated)
+        const int o = t & (kFoldHalf - 1);
+        f32x4 w4[kRayPeFloats / 4];
+#pragma unroll
+        for (int q = 0; q < kRayPeFloats / 4; ++q) {
+          w4[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (4 * q < p.fold_xcols) w4[q] = *reinterpret_cast<const f32x4*>(p.fold_wx + o * p.fold_xcols + 4 * q);
+        }
+        // 1. the rays' encodings by the text the per-sample path evaluated: thread 4 r + g = lane group g's slots of ray r
+        for (int r = t >> 2; r < nr; r += kThreads / 4) {
+          const int g = t & 3;
+          const float* rp = p.rays + (ray0 + r) * p.ray_stride;
+          float e[kStepsExtraMax];
+#pragma unroll
+          for (int s = 0; s < kStepsExtraMax; ++s) e[s] = 0.f;
+          const bool dir = p.extra_type == MF_EXTRA_DIR;
+          if (dir) {
+            const float dd[3] = {rp[3], rp[4], rp[5]};
+            emb_eval_lds<3, 4>(e, dd, par_nerf_ext, g);                                  // rendering.py:138-142
+          } else {
+            const float iv[1] = {rp[8]};
+            emb_eval_lds<1, 2>(e, iv, par_nerf_ext, g);                                  // rendering.py:133-137
+          }
+          float* pe = reinterpret_cast<float*>(smem + rpe_off) + r * kRayPeFloats;
+          const int nfeat = dir ? 27 : 5;
+#pragma unroll
+          for (int s = 0; s < kStepsExtraMax; ++s) {
+            const int f = emb_feature(dir ? kEmbDir : kEmbInd, g, s, 0);
+            if (f >= 0) pe[f] = e[s];
+          }
+          for (int f = nfeat + g; f < kRayPeFloats; f += 4) pe[f] = 0.f;
+        }
+        __syncthreads();
+        // 2. thread (o = t % (W/2), r = t / (W/2) + 4 i): its weight row from registers, the encodings by broadcast reads
+        const float b = lds_f(nerf.res_lds + (nerf.L.off_bias_extra + o) * 4);
+        for (int r = t / kFoldHalf; r < nr; r += kThreads / kFoldHalf) {
+          float acc = b;
+#pragma unroll
+          for (int q = 0; q < kRayPeFloats / 4; ++q) {
+            const f32x4 e4 = lds_f4(rpe_off + (r * kRayPeFloats + 4 * q) * 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc = __builtin_fmaf(w4[q][i], e4[i], acc);
+          }
+          *reinterpret_cast<float*>(smem + p.rbias_off + (r * kFoldHalf + o) * 4) = acc;
+        }
+        // (published by the panel barriers in front of trunk layer D - 1's last panel, where the first row is read; the next
+        //  group's phase runs behind this group's composite barriers)
+      }
+    }
+#endif
 
     for (int tile = 0; tile < ntiles; ++tile) {
       st.tl.stamp(1, id);
@@ -136,6 +203,18 @@
       for (int e = 0; e < kStepsExtraMax; ++e) ext[e] = 0.f;
       float* dump_row = nullptr;
       unsigned* mask_row = nullptr;
+      uint32_t ray_bias = 0;                   // FOLD: LDS byte offset of the lane's row of the group's bias table
+#if MF_BODY_FOLD
+      {
+        const Where w = where();
+#ifdef MF_RAYBIAS_BREAK_ROW   // (the deliberately broken build tests/test_gpu_ray_bias.py must reject: every lane reads the group's first row)
+        const int rr = 0 * (int)(w.ray - ray0);
+#else
+        const int rr = (int)(w.ray - ray0);
+#endif
+        ray_bias = p.fold_wx ? p.rbias_off + (uint32_t)rr * (kFoldHalf * 4) : nerf.res_lds + nerf.L.off_bias_extra * 4;
+      }
+#else
       {
         const Where w = where();
         if (!sigma_only) {
@@ -154,9 +233,12 @@
           if (p.dump_mask) mask_row = p.dump_mask + (w.ray * S + w.si) * p.dump_mask_stride;   // (uniformly non-null when asked for)
         }
       }
+#endif
       st.tl.stamp(4, id);
       float sigma, rgb[3] = {0.f, 0.f, 0.f};
       st.keep2 = 0;      // the first panel's barrier drains everything (see Stream::sync_and_dma)
+      if constexpr (FOLD) nerf_eval<16, DUMP, FOLD, !MOCO>(nerf, embx, ext, sigma_only, st, carry, id, prog_first, sigma, rgb, nullptr, nullptr, ray_bias);
+      else
       nerf_eval<16, DUMP, FOLD>(nerf, embx, ext, sigma_only, st, carry, id, prog_first, sigma, rgb, dump_row, mask_row);
       {
         const Where w = where();
