@@ -52,7 +52,8 @@ extern "C" {
  *     mf_raster_resolve, mf_raster_interpolate, mf_raster_shade; mf_resize_u8 (+ mf_resize_u8_scratch_bytes), mf_composite_rows,
  *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter;
  *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit;
- *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes) */
+ *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes); mf_rings_mesh_plan / mf_rings_mesh_emit
+ *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -716,6 +717,52 @@ int32_t mf_simplify_mesh_plan(const float* verts, int64_t V, const int64_t* tris
 int32_t mf_simplify_mesh_emit(const float* verts, int64_t V, const int64_t* tris, int64_t T, const double* lo, const double* hi,
                               double cell, int64_t n0, int64_t n1, int64_t n2, int64_t Vk, int64_t Tk, void* scratch, void* sums,
                               float* verts_k, int64_t* tris_k, int64_t* first, int64_t* cluster, void* stream);
+
+/* ---- vertex adjacency and smoothing: what follows an isosurface at a fixed threshold, whose lattice-scale ripple (and the
+ * faceting a clustering grid leaves) a user otherwise removes on the host after copying the mesh there.  The reference has no
+ * counterpart; tests/mesh_smooth_oracle.py restates both contracts in numpy.  Nothing is allocated, everything runs on `stream`,
+ * nothing synchronises; every output is a pure function of the input, bit-identical from run to run. */
+#define MF_MESH_MAX_TRIANGLES_PER_VERTEX 2048
+
+/* mf_rings_mesh_plan (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259: the mesh visualize_mesh extracts): the
+ * one-ring of every vertex of tris (T, 3) int64 over V vertices.  A triangle that names a vertex outside [0, V) is counted into
+ * `bad` and never dereferenced.  A triangle with two equal indices is skipped entirely and contributes no edge.  m(i, j) = the
+ * number of remaining triangles that contain both i and j, i != j.  ring(i) = { j : m(i, j) >= 1 }, ascending by j, each j once
+ * (the same triangle twice, or in both windings, changes m and not the ring).  boundary[i] = 1 iff some j has m(i, j) == 1: an
+ * edge in three or more triangles does not make its ends boundary; a vertex in no kept triangle has an empty ring and is not
+ * boundary.  V < 2^31 and 6 T < 2^31 (R <= 6 T), else MF_E_INVALID -- from mf_rings_mesh_scratch_bytes already, a host function,
+ * before anything is allocated.  A vertex in more than MF_MESH_MAX_TRIANGLES_PER_VERTEX kept triangles is counted into
+ * `over_cap` by the counting pass; with bad or over_cap non-zero no segment is sorted (no lane does work quadratic in an unbounded
+ * degree), offsets and boundary hold nothing of use and the caller rejects the mesh.
+ * Writes counts (device int64[3]) = [bad, over_cap, R], offsets (V + 1) int64 (offsets[V] = R) and boundary (V) uint8; the
+ * sorted, de-duplicated segments stay in scratch.  Raw half-edges are counted and placed by integer atomics, each segment is
+ * sorted before anything is read from it: the order in which the atomics land shows in no output.  V = 0 or T = 0 is legal
+ * (offsets all zero; tris, boundary and scratch may be NULL where empty).  Up to ten launches. */
+int64_t mf_rings_mesh_scratch_bytes(int64_t V, int64_t T);
+int32_t mf_rings_mesh_plan(const int64_t* tris, int64_t T, int64_t V, int64_t* counts, int64_t* offsets, uint8_t* boundary,
+                           void* scratch, void* stream);
+/* mf_rings_mesh_emit (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259): after mf_rings_mesh_plan on the same
+ * stream with the same V, T, scratch and offsets, and with counts read (bad = over_cap = 0): ring (R) int64,
+ * ring[offsets[i] .. offsets[i + 1]) = ring(i).  Nothing is written at or beyond R.  R = 0 launches nothing.  Two launches. */
+int32_t mf_rings_mesh_emit(int64_t V, int64_t T, int64_t R, void* scratch, const int64_t* offsets, int64_t* ring, void* stream);
+
+/* mf_smooth_mesh (serves trainer_moco_flow.py:490-538, trainer_nerf.py:200-259): Laplacian (taubin = 0: `iterations` steps with
+ * factor lam) or Taubin lambda|mu smoothing (taubin = 1: `iterations` times a lam step, then a mu step) of verts (V, 3) fp32
+ * over the rings mf_rings_mesh_* wrote (offsets (V + 1), ring (R), both int64) -> out (V, 3) fp32; out must not alias verts.
+ * One step with factor f: every vertex reads the positions of the PREVIOUS step (Jacobi, two buffers).  A vertex that moves, with
+ * ring j0 < j1 < ... < j(n-1), per component in fp32, every operation rounded once: s = p[j0]; s = s + p[jk] for k = 1 .. n-1 in
+ * that order; m = s / float(n); d = m - p_i; p_i' = p_i + f d (the product rounded, then the sum).  A vertex that does not move
+ * -- an empty ring, or boundary[i] != 0 where boundary is given (NULL: boundary vertices move like any other) -- is copied byte
+ * for byte.  Positions that are not finite propagate by IEEE rules: nothing is checked, nothing is clamped.
+ * The steps run on private copies in scratch (mf_smooth_mesh_scratch_bytes(V, R); V, R in [0, 2^31), else MF_E_INVALID):
+ * positions as 16-byte rows, offsets and ring as int32.  While copying, offsets are clamped to [0, R] and a ring entry outside
+ * [0, V) becomes 0, so rings that are not mf_rings_mesh_*'s give positions without meaning but no access outside the buffers.
+ * iterations in [0, 2^20], lam (and mu with taubin) finite, else MF_E_INVALID.  iterations = 0 or R = 0: out = verts, a copy.
+ * V = 0 launches nothing.  One call enqueues the packing, every step and the unpacking: 2 + the number of steps launches. */
+int64_t mf_smooth_mesh_scratch_bytes(int64_t V, int64_t R);
+int32_t mf_smooth_mesh(const float* verts, int64_t V, const int64_t* offsets, const int64_t* ring, int64_t R,
+                       const uint8_t* boundary, int32_t iterations, float lam, float mu, int32_t taubin, float* out, void* scratch,
+                       void* stream);
 
 /* ---- validation metrics: models/metrics.py:4-22 (mse, psnr, ssim), called per validation image by val_step
  * (trainer_moco_flow.py:453-473).  The reference's ssim is kornia 0.6.5's kornia.metrics.ssim.ssim(img1, img2, window_size,

@@ -21,7 +21,7 @@ from .nerf import NeRF
 from .nof import NoF
 from .points import query_radiance, query_sigma, query_sigma_lattice
 from .mesh import (export_obj, export_ply, extract_colored_mesh, extract_mesh, filter_components, marching_cubes, mesh_components,
-                   simplify_mesh, vertex_normals)
+                   simplify_mesh, smooth_mesh, vertex_normals, vertex_rings)
 from . import metrics
 from .metrics import image_metrics
 from . import vis
@@ -41,7 +41,7 @@ from .rendering import render_rays, resample_merge, sample_pdf, set_precision, s
 
 __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "sample_pdf",
            "resample_merge", "set_precision", "set_wgrad_precision", "set_dx_precision", "set_train_forward_precision", "query_sigma", "MSELoss",
-           "marching_cubes", "mesh_components", "filter_components", "simplify_mesh", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
+           "marching_cubes", "mesh_components", "filter_components", "simplify_mesh", "vertex_rings", "smooth_mesh", "extract_mesh", "export_obj", "query_radiance", "extract_colored_mesh", "vertex_normals", "export_ply", "metrics", "image_metrics",
            "vis", "visualize_depth", "decode_results", "frame_sheet", "write_png", "batch", "FrameRays",
            "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
            "occupancy", "OccupancyGrid", "query_sigma_lattice",

@@ -225,6 +225,12 @@ SYMBOLS = {
                                           C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp]),
     "mf_simplify_mesh_emit": (C.c_int32, [_fp, C.c_int64, _fp, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                           C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mf_rings_mesh_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_rings_mesh_plan": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
+    "mf_rings_mesh_emit": (C.c_int32, [C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp]),
+    "mf_smooth_mesh_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mf_smooth_mesh": (C.c_int32, [_fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int32, C.c_float, C.c_float, C.c_int32, _fp, _fp,
+                                   _fp]),
     "mf_ssim_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mf_ssim": (C.c_int32, [_fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp]),

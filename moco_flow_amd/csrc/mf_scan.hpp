@@ -1,10 +1,11 @@
 // mf_scan.hpp -- the ordered integer prefix of the library, written once.  Users: mf_sample.hip (compact_*_kernel: mf_compact_mask),
 // mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add), mf_regions.hip (reg_table_*_kernel),
-// mf_mesh_simplify.hip (the survivors' and the used cells' ranks).
+// mf_mesh_simplify.hip (the survivors' and the used cells' ranks), mf_mesh_smooth.hip (the raw and the compact ring offsets).
 // Integer arithmetic: the order of the additions is free.  THE CONTRACT IS WHO RANKS BEFORE WHOM AND WHO SYNCHRONISES; "bit-
 // identical, no atomics, original order kept" (the ray batch) rests on it.  Workgroups are 1-D, whole waves (lane =
 // threadIdx.x & 63, wave = threadIdx.x >> 6); lower lanes rank before higher ones, lower waves and lower threads' shares likewise.
-//   wave_popcount, wave_rank, wave_prefix_small, wave_sum_i64   every lane of the wave calls them (converged); no LDS, no barrier
+//   wave_popcount, wave_rank, wave_prefix_small, wave_prefix_i64, wave_sum_i64   every lane of the wave calls them (converged); no
+//                                 LDS, no barrier
 //   block_sum_i64<THREADS>        every thread of the workgroup calls it and receives the sum.  Owns THREADS / 64 words of LDS and
 //                                 opens with the barrier that lets it be called again: the caller places none
 //   block_offsets<THREADS, COLS>  every thread calls it and receives, per column, the sum of the totals of the waves in front of
@@ -39,6 +40,16 @@ __device__ __forceinline__ int wave_prefix_small(int v, int& total) {
     total += __popcll(m) << bit;
   }
   return before;
+}
+
+// the exclusive prefix over the lanes of any integer v, and the wave's sum: six shuffles (wave_prefix_small is cheaper for a
+// count of a few bits)
+__device__ __forceinline__ long long wave_prefix_i64(long long v, long long& total) {
+  long long incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(incl, d); if ((threadIdx.x & 63) >= d) incl += u; }
+  total = __shfl(incl, 63);
+  return incl - v;
 }
 
 __device__ __forceinline__ long long wave_sum_i64(long long v) {         // every lane receives the sum

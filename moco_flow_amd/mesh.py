@@ -3,9 +3,11 @@
 without the volume leaving the device -- and what a coloured mesh adds: vertex normals from the same volume
 (mf_mc_normals), vertex colours from the radiance field (query_radiance), a PLY writer that carries both; and the mesh
 clean-up that follows an isosurface at a fixed threshold: connected components (mf_mesh_label, mf_mesh_table_*) and the
-filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device; and the
-reduction of the triangle count by vertex clustering (simplify_mesh: mf_simplify_mesh_*)."""
+filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device; the
+reduction of the triangle count by vertex clustering (simplify_mesh: mf_simplify_mesh_*); and vertex adjacency with the
+smoothing built on it (vertex_rings: mf_rings_mesh_*, smooth_mesh: mf_smooth_mesh)."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -343,6 +345,155 @@ def _simplify_emit(verts, tris, grid, scratch, Vk, Tk, mean):
     return verts_k, tris_k, first, cluster
 
 
+MAX_TRIANGLES_PER_VERTEX = 2048          # include/mocoflow_hip.h MF_MESH_MAX_TRIANGLES_PER_VERTEX
+
+
+def _rings(tris, V, what):
+    """vertex_rings on a checked, contiguous (T, 3) int64 device tensor; one device -> host read ([bad, over_cap, R])."""
+    lib, dev, T = L.lib(), tris.device, tris.shape[0]
+    need = int(lib.mf_rings_mesh_scratch_bytes(V, T))
+    if need < 0:                                     # V or 6 T beyond 32-bit indexing: rejected before anything is allocated
+        L.check(need, "mf_rings_mesh_scratch_bytes")
+    scratch = _bytes(need, dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    offsets = torch.empty(V + 1, dtype=torch.int64, device=dev)
+    boundary = torch.empty(V, dtype=torch.bool, device=dev)
+    with torch.cuda.device(dev):
+        stream = L.current_stream(dev)
+        L.check(lib.mf_rings_mesh_plan(L.ptr(tris) if T else None, T, V, counts.data_ptr(), offsets.data_ptr(),
+                                       L.ptr(boundary) if V else None, scratch.data_ptr(), stream), "mf_rings_mesh_plan")
+        bad, over, R = (int(x) for x in counts.tolist())
+        if bad:
+            raise RuntimeError(f"{what}: {bad} triangles name a vertex outside [0, {V})")
+        if over:
+            raise RuntimeError(f"{what}: {over} vertices are in more than MAX_TRIANGLES_PER_VERTEX = "
+                               f"{MAX_TRIANGLES_PER_VERTEX} triangles")
+        ring = torch.empty(R, dtype=torch.int64, device=dev)
+        L.check(lib.mf_rings_mesh_emit(V, T, R, scratch.data_ptr(), offsets.data_ptr(), L.ptr(ring) if R else None, stream),
+                "mf_rings_mesh_emit")
+    return offsets, ring, boundary
+
+
+def vertex_rings(tris, n_verts):
+    """The one-ring of every vertex of an indexed mesh as a CSR structure: tris (T, 3) int64 on a 'cuda' device over
+    ``n_verts`` = V vertices -> (offsets (V + 1,) int64, ring (R,) int64, boundary (V,) bool) on that device.
+
+    A triangle that names a vertex outside [0, V) makes the call raise RuntimeError with the count: a bad index is counted
+    and never dereferenced, and no ring is written for that call.  A triangle with two equal indices is skipped entirely
+    and contributes no edge; it is not an error (simplify_mesh and real meshes produce them).  m(i, j) is the number of
+    remaining triangles that contain both i and j, i != j.  ring(i) = { j : m(i, j) >= 1 }, stored ascending by j, each j
+    once, at ring[offsets[i] : offsets[i + 1]] -- the same triangle twice, or in both windings, changes m and not the
+    ring.  boundary[i] is true iff some j has m(i, j) == 1: an edge in three or more triangles (non-manifold) does not make
+    its ends boundary; a vertex in no kept triangle has an empty ring and is not boundary.
+
+    Bounds: V < 2^31 and 6 T < 2^31 (R <= 6 T), refused on the host before anything is allocated.  A vertex in more than
+    ``MAX_TRIANGLES_PER_VERTEX`` kept triangles raises RuntimeError naming the count of such vertices: it is found in the
+    counting pass, before any segment is sorted, so no lane does work quadratic in an unbounded degree.  V = 0 and T = 0
+    are legal: offsets all zero, an empty ring.  Every output is a pure function of the input, bit-identical from run to
+    run whatever order the atomics land in (include/mocoflow_hip.h mf_rings_mesh_plan).  One device -> host read
+    ([bad, over_cap, R])."""
+    _check_tris(tris, "vertex_rings")
+    V = int(n_verts)
+    if V < 0:
+        raise RuntimeError(f"vertex_rings: n_verts={V}")
+    L.require_gpu(tris, "vertex_rings")
+    return _rings(tris.detach().contiguous(), V, "vertex_rings")
+
+
+def _smooth_args(iterations, lam, mu, boundary, what="smooth_mesh"):
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError(f"{what}: iterations={iterations!r} (an integer, at least 0)")
+    if iterations > 1 << 20:
+        raise ValueError(f"{what}: iterations={iterations} (at most 2^20)")
+    for name, x in (("lam", lam), ("mu", mu)):
+        if x is None and name == "mu":
+            continue
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(x):
+            raise ValueError(f"{what}: {name}={x!r} (a finite number)")
+    if boundary not in ("fixed", "free"):
+        raise ValueError(f"{what}: boundary={boundary!r} ('fixed' or 'free')")
+
+
+def smooth_mesh(verts, tris, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", rings=None):
+    """Laplacian / Taubin lambda|mu smoothing on the device: verts (V, 3) float32 and tris (T, 3) int64 on a 'cuda' device
+    -> verts_s (V, 3) float32.  The triangles are unchanged and not returned.  lam = 0.5, mu = -0.53 are Taubin's values as
+    trimesh and Open3D ship them.
+
+    One iteration is a lam step followed by a mu step; ``mu=None`` is plain Laplacian smoothing, ``iterations`` lam steps;
+    ``iterations=0`` returns a copy, byte for byte.  One step with factor f (the Python float rounded to float32): every
+    vertex reads the positions of the PREVIOUS step (Jacobi with two buffers, never in place).  A vertex that moves, with
+    ring j0 < j1 < ... < j(n-1) (vertex_rings), per component in float32, every operation rounded once: s = p[j0];
+    s = s + p[jk] for k = 1 .. n-1 in that order; m = s / float(n); d = m - p_i; p_i' = p_i + f d (the product rounded,
+    then the sum).  A vertex that does not move is copied byte for byte: an empty ring, and boundary[i] under
+    ``boundary="fixed"``; ``boundary="free"`` moves boundary vertices like any other.  Positions that are not finite
+    propagate by IEEE rules: nothing is checked and nothing is clamped.  The result is a pure function of the input,
+    bit-identical from run to run (include/mocoflow_hip.h mf_smooth_mesh).
+
+    ``rings``: a vertex_rings result for the same ``tris``, so that a caller smoothing several vertex sets over one topology
+    builds it once; with it the call reads nothing from the device (``tris`` is then not looked at beyond its shape).
+    Without it the call builds the rings itself, at the cost of vertex_rings' one read.  Rings that are no vertex_rings
+    result give positions without meaning, never an access outside the buffers.  One host entry enqueues every step on the
+    current stream; the two position buffers are allocated per call.
+
+    ValueError before any tensor is looked at: ``iterations`` negative or not an integer, ``lam`` or ``mu`` not finite,
+    ``boundary`` not one of the two strings, a ``rings`` tuple whose offsets length is not V + 1."""
+    _smooth_args(iterations, lam, mu, boundary)
+    if rings is not None:
+        if len(rings) != 3:
+            raise ValueError("smooth_mesh: rings is (offsets, ring, boundary) as vertex_rings returns them")
+        n_off = rings[0].shape[0] if rings[0].dim() == 1 else -1
+        n_v = verts.shape[0] if verts.dim() >= 1 else -1
+        if n_off != n_v + 1:
+            raise ValueError(f"smooth_mesh: rings offsets has shape {tuple(rings[0].shape)} for {n_v} vertices (V + 1 entries)")
+    _check_tris(tris, "smooth_mesh")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError(f"smooth_mesh: verts must be (V, 3), got shape {tuple(verts.shape)}")
+    if verts.dtype != torch.float32:
+        raise RuntimeError(f"smooth_mesh: verts must be float32, got {verts.dtype}")
+    V = verts.shape[0]
+    for t in (tris, verts) + (tuple(rings) if rings is not None else ()):
+        L.require_gpu(t, "smooth_mesh")
+    verts = verts.detach().contiguous()
+    if rings is None:
+        offsets, ring, bnd = _rings(tris.detach().contiguous(), V, "smooth_mesh")
+    else:
+        offsets, ring, bnd = rings
+        if offsets.dtype != torch.int64 or ring.dtype != torch.int64 or ring.dim() != 1:
+            raise RuntimeError("smooth_mesh: rings offsets and ring must be 1-D int64")
+        if bnd.dtype not in (torch.bool, torch.uint8) or bnd.shape != (V,):
+            raise RuntimeError(f"smooth_mesh: rings boundary must be ({V},) bool")
+        offsets, ring, bnd = offsets.contiguous(), ring.contiguous(), bnd.contiguous()
+    if iterations == 0 or V == 0:
+        return verts.clone()
+    lib, dev, R = L.lib(), verts.device, ring.shape[0]
+    need = int(lib.mf_smooth_mesh_scratch_bytes(V, R))
+    if need < 0:
+        L.check(need, "mf_smooth_mesh_scratch_bytes")
+    scratch = _bytes(need, dev)
+    out = torch.empty_like(verts)
+    with torch.cuda.device(dev):
+        L.check(lib.mf_smooth_mesh(verts.data_ptr(), V, offsets.data_ptr(), L.ptr(ring) if R else None, R,
+                                   bnd.data_ptr() if boundary == "fixed" else None, int(iterations), float(lam),
+                                   0.0 if mu is None else float(mu), 0 if mu is None else 1, out.data_ptr(), scratch.data_ptr(),
+                                   L.current_stream(dev)), "mf_smooth_mesh")
+    return out
+
+
+def _smooth_kwargs(smooth, what):
+    """The keywords of smooth_mesh from the ``smooth=`` argument of the extraction calls: an int >= 1 or a dict."""
+    if isinstance(smooth, dict):
+        extra = set(smooth) - {"iterations", "lam", "mu", "boundary"}
+        if extra:
+            raise ValueError(f"{what}: smooth has unknown keys {sorted(extra)}")
+        kw = dict(smooth)
+    elif isinstance(smooth, (int, np.integer)) and not isinstance(smooth, bool) and smooth >= 1:
+        kw = {"iterations": int(smooth)}
+    else:
+        raise ValueError(f"{what}: smooth={smooth!r} (None, an int >= 1, or a dict of smooth_mesh's keywords)")
+    _smooth_args(kw.get("iterations", 10), kw.get("lam", 0.5), kw.get("mu", -0.53), kw.get("boundary", "fixed"), what)
+    return kw
+
+
 def lattice(N_grid, device):
     """visualize_mesh's query points (trainer_moco_flow.py:490-498): np.linspace(-1.5, 1.5, N) in float64 cast to fp32, laid
     out as np.stack(np.meshgrid(x, y, z), -1).reshape(-1, 3) ('xy' indexing: point (a, b, c) is (x[b], y[a], z[c]))."""
@@ -361,7 +512,7 @@ def _sparse_volume(N_grid, nerf, nerf_embedding_xyz, occupancy, margin, bw_nof, 
 
 
 def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                 precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=1, simplify=None):
+                 precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=1, simplify=None, smooth=None):
     """visualize_mesh (trainer_moco_flow.py:490-538) up to the file: raw sigma of the NeRF on the N_grid^3 lattice over
     [-1.5, 1.5]^3 (query_sigma; with ``bw_nof`` / ``nof_embeddings`` / ``ind`` through the backward flow, ``ind`` =
     frame_idx * 2 / num_frames - 1), the isosurface of max(sigma, 0) at ``sigma_threshold``, then the reference's
@@ -380,7 +531,16 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
     ``simplify`` (not in the reference; None leaves the path as it was, byte for byte): the edge of a clustering cell in
     lattice steps, e.g. ``simplify=4``.  simplify_mesh runs on the raw isosurface in index coordinates, after the component
     filter and before the post-processing, with lo = 0 and hi = N_grid - 1 (known on the host: no extra read) and
-    ``placement="mean"``."""
+    ``placement="mean"``.
+
+    ``smooth`` (not in the reference; None leaves the path as it was, byte for byte): ``smooth=k``, an int >= 1, runs
+    smooth_mesh(iterations=k) with its defaults (Taubin, lam = 0.5, mu = -0.53, boundary fixed);
+    ``smooth=dict(iterations=..., lam=..., mu=..., boundary=...)`` passes those keywords.  It runs on the raw isosurface in
+    index coordinates, AFTER the component filter and after ``simplify``, BEFORE the post-processing (the column swap and
+    / N_grid * 3 - 1.5): the bits depend on that order.  The rim a lattice face cuts into the surface is a boundary and
+    stays put under the default.  One more device -> host read (vertex_rings')."""
+    if smooth is not None:
+        smooth = _smooth_kwargs(smooth, "extract_mesh")
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_mesh")
     with torch.no_grad():
@@ -395,13 +555,16 @@ def extract_mesh(nerf, nerf_embedding_xyz, N_grid=256, sigma_threshold=10, bw_no
             verts, tris = filter_components(verts, tris, keep_largest, min_triangles)
         if simplify is not None:
             verts, tris = simplify_mesh(verts, tris, simplify, lo=(0.0,) * 3, hi=(N_grid - 1.0,) * 3, placement="mean")
+        if smooth is not None:
+            verts = smooth_mesh(verts, tris, **smooth)
         verts = verts[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
     return verts, tris
 
 
 def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, bw_nof=None, nof_embeddings=None, ind=None,
-                         precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=2, simplify=None):
+                         precision=None, keep_largest=None, min_triangles=None, occupancy=None, margin=2, simplify=None,
+                         smooth=None):
     """extract_mesh with what a coloured mesh needs: (verts (V, 3), tris (T, 3), normals (V, 3), colors (V, 3)).
 
     verts / tris are extract_mesh's for the same arguments (``nerf_embeddings`` = [xyz, ind | None, dir | None] as
@@ -418,7 +581,15 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
     ``simplify``: as in extract_mesh, positions by ``placement="mean"`` as well; it runs after the filter and before the
     radiance query, so colours are queried at the simplified vertices only (the query gets cheaper by the vertex ratio).
     The normal of a new vertex is the normal of ``first`` -- the row of its cell's smallest original vertex, carried as an
-    attribute byte for byte: a unit vector (or zero) already, not re-normalised and not averaged."""
+    attribute byte for byte: a unit vector (or zero) already, not re-normalised and not averaged.
+
+    ``smooth``: as in extract_mesh, at the same place (after the filter and ``simplify``, before the post-processing).
+    Normals and colours belong to the surface the field defines: vertex_normals is valid only for vertices on their lattice
+    edges, so the normals are carried unchanged, and the colours are queried at the UNSMOOTHED post-processed positions;
+    only the returned positions are smoothed.  Hence ``normals`` and ``colors`` equal those of the same call without
+    ``smooth``, bit for bit, and ``verts`` / ``tris`` equal extract_mesh's with the same keywords."""
+    if smooth is not None:
+        smooth = _smooth_kwargs(smooth, "extract_colored_mesh")
     dev = next(nerf.parameters()).device
     L.require_gpu(next(nerf.parameters()), "extract_colored_mesh")
     with torch.no_grad():
@@ -438,6 +609,7 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
             raw, tris, normals = simplify_mesh(raw, tris, simplify, lo=(0.0,) * 3, hi=(N_grid - 1.0,) * 3, placement="mean",
                                                attrs=(normals,))
         verts = raw[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
+        smoothed = None if smooth is None else smooth_mesh(raw, tris, **smooth)[:, [1, 0, 2]] / N_grid * 3.0 - 1.5
         tris = tris[:, [0, 2, 1]].contiguous()
         if verts.shape[0] == 0:
             return verts, tris, normals, torch.empty((0, 3), dtype=torch.float32, device=dev)
@@ -447,7 +619,7 @@ def extract_colored_mesh(nerf, nerf_embeddings, N_grid=256, sigma_threshold=10, 
             view_dirs = torch.where(zero, normals.new_tensor([0.0, 0.0, -1.0]), -normals)
         colors = query_radiance(verts, nerf, nerf_embeddings, view_dirs=view_dirs, ind=ind, bw_nof=bw_nof,
                                 nof_embeddings=nof_embeddings)[:, :3].contiguous()
-    return verts, tris, normals, colors
+    return (verts if smoothed is None else smoothed), tris, normals, colors
 
 
 def export_ply(path, verts, tris, colors=None, normals=None):

@@ -30,7 +30,17 @@ emit: the same read, 20 B per new vertex + 24 B per kept triangle + 8 B per vert
 device-to-device copy rate -- information only: the table probes and the per-cell atomics are random accesses and no share
 of a peak is claimed.  The numpy oracle (tests/mesh_simplify_oracle.py) on the same mesh in the same process, once, where
 the mesh has at most 8 M triangles (--no-host skips it); it also checks the device's result bit for bit.
-Usage: time_mesh.py [--no-host] [--components-only] [--sparse] [--simplify CELL] [N ...]  (default 256 512)"""
+
+--smooth K: only the smoothing leg (vertex_rings, smooth_mesh) on both meshes of each size (default 512), device times by HIP
+events on the stream, median of 20 after 5 warm-ups: vertex_rings (with its read of [bad, over_cap, R] and its allocations); one
+smoothing step (the difference between 21 and 1 Laplacian steps over given rings, divided by 20: the packing and unpacking
+cancel); smooth_mesh(iterations=K) end to end, building its rings, with its read.  Beside each time the algorithmic bytes
+(rings: 24 B per triangle read + 8 B per ring entry and per offset + 1 B per vertex written; a step: 24 V + 4 R + 4 (V + 1), every
+position read once and written once and the 32-bit private indices read once) over the 4.69 TB/s device-to-device copy rate
+-- information only: the neighbour gathers are cache traffic and no share of a peak is claimed.  The host path it replaces in
+the same process, once: the device -> host copy and the numpy oracle (tests/mesh_smooth_oracle.py), where the mesh has at most
+8 M triangles (--no-host skips it); it also checks the device's result bit for bit.
+Usage: time_mesh.py [--no-host] [--components-only] [--sparse] [--simplify CELL] [--smooth K] [N ...]  (default 256 512)"""
 import os
 import statistics
 import sys
@@ -48,8 +58,9 @@ D2D_COPY_RATE = 4.69e12
 HOST = "--no-host" not in sys.argv
 COMPONENTS_ONLY = "--components-only" in sys.argv
 SIMPLIFY = float(sys.argv[sys.argv.index("--simplify") + 1]) if "--simplify" in sys.argv else None
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--simplify"]
-Ns = [int(a) for a in _args] or ([512] if SIMPLIFY is not None else [256, 512])
+SMOOTH = int(sys.argv[sys.argv.index("--smooth") + 1]) if "--smooth" in sys.argv else None
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--simplify", "--smooth")]
+Ns = [int(a) for a in _args] or ([512] if SIMPLIFY is not None or SMOOTH is not None else [256, 512])
 dev = torch.device("cuda")
 sd = synth.nerf_state(0, regime="dense")
 sd["sigma.weight"] = sd["sigma.weight"] * np.float32(3.0)
@@ -180,6 +191,65 @@ def simplify_leg(what, N, verts, tris, cell):
           f"{'equals it bit for bit' if same else 'DIFFERS'}", flush=True)
 
 
+def smooth_leg(what, N, verts, tris, K):
+    V, T = len(verts), len(tris)
+    ms_rings, rings = time_events(lambda: M.vertex_rings(tris, V))
+    R = len(rings[1])
+    ms_1, _ = time_events(lambda: M.smooth_mesh(verts, tris, iterations=1, mu=None, rings=rings))
+    ms_21, _ = time_events(lambda: M.smooth_mesh(verts, tris, iterations=21, mu=None, rings=rings))
+    ms_step = (ms_21 - ms_1) / 20.0
+    ms_all, out = time_events(lambda: M.smooth_mesh(verts, tris, iterations=K))
+    b_rings, b_step = 24 * T + 8 * R + 8 * (V + 1) + V, 24 * V + 4 * R + 4 * (V + 1)
+    frac = lambda b, ms: b / (ms * 1e-3) / D2D_COPY_RATE
+    print(f"  smooth, {what} {N}^3: V {V} T {T}, R {R} ring entries, {int(rings[2].sum())} boundary vertices")
+    print(f"    vertex_rings  {ms_rings:9.3f} ms  ({b_rings / 1e9:.3f} GB algorithmic = {frac(b_rings, ms_rings):.3f} of the copy rate; with its read)")
+    print(f"    one step      {ms_step:9.3f} ms  ({b_step / 1e9:.3f} GB algorithmic = {frac(b_step, ms_step):.3f} of the copy rate; "
+          f"21 steps {ms_21:.3f} ms, 1 step {ms_1:.3f} ms, packing and unpacking included in both)")
+    print(f"    smooth_mesh(iterations={K}) end to end, rings built inside, with its read: {ms_all:9.3f} ms", flush=True)
+    if not HOST:
+        return
+    if T > 8_000_000:
+        print(f"    host path: not measured ({T} triangles: np.unique on the {6 * T} ring keys needs tens of GB and minutes)", flush=True)
+        return
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import mesh_smooth_oracle as O
+    t0 = time.perf_counter()
+    v, t = verts.cpu().numpy(), tris.cpu().numpy()
+    t1 = time.perf_counter()
+    want_rings = O.rings(t, V)
+    t2 = time.perf_counter()
+    want = O.smooth(v, t, K, rings_=want_rings)
+    t3 = time.perf_counter()
+    same = all(torch.equal(g.cpu(), torch.from_numpy(w)) for g, w in zip(rings, want_rings)) and torch.equal(out.cpu(), torch.from_numpy(want))
+    print(f"    host path: device -> host copy {1e3 * (t1 - t0):8.1f} ms, numpy rings {1e3 * (t2 - t1):10.1f} ms, numpy smooth "
+          f"({K} iterations) {1e3 * (t3 - t2):10.1f} ms; the device's result {'equals it bit for bit' if same else 'DIFFERS'}", flush=True)
+
+
+def both_meshes(N):
+    """(what, verts, tris) of the two meshes of a size, one at a time."""
+    with torch.no_grad():
+        xyz = M.mesh.lattice(N, dev)
+        vol = M.query_sigma(xyz, nerf, emb).view(N, N, N)
+        del xyz
+    yield ("test NeRF sigma at 10",) + M.marching_cubes(vol, 10.0, clamp_zero=True)
+    del vol
+    torch.cuda.empty_cache()
+    ax = torch.linspace(0, 1, N, device=dev)
+    x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+    vol = (torch.sin(6.0 * x + 2.0 * y * y) + torch.sin(5.0 * y + 3.0 * z) + torch.sin(7.0 * z + 4.0 * x * y)).contiguous()
+    del x, y, z
+    yield ("smooth field",) + M.marching_cubes(vol, 0.3)
+
+
+if SMOOTH is not None:
+    print(f"vertex_rings and smooth_mesh ({SMOOTH} Taubin iterations, lam 0.5, mu -0.53, boundary fixed) on the marching-cubes meshes "
+          "of the f32 sigma lattice (threshold 10) and of the smooth field (0.3)")
+    for N in Ns:
+        for what, verts, tris in both_meshes(N):
+            smooth_leg(what, N, verts, tris, SMOOTH)
+            del verts, tris
+            torch.cuda.empty_cache()
+    sys.exit(0)
 if SIMPLIFY is not None:
     print(f"simplify_mesh (vertex clustering, cell {SIMPLIFY} lattice steps) on the marching-cubes meshes of the f32 sigma lattice "
           "(threshold 10) and of the smooth field (0.3)")
