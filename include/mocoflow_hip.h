@@ -53,7 +53,8 @@ extern "C" {
  *     mf_background_plate; mf_lattice_select (+ mf_lattice_select_scratch_bytes), mf_lattice_points, mf_lattice_scatter;
  *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit;
  *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes); mf_rings_mesh_plan / mf_rings_mesh_emit
- *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes) */
+ *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes); mf_voxel_mesh, mf_voxel_fill
+ *     (+ mf_voxel_fill_scratch_bytes), mf_voxel_dilate (+ mf_voxel_dilate_scratch_bytes) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -985,6 +986,49 @@ int32_t mf_occ_build(const float* sigma, int64_t nx, int64_t ny, int64_t nz, int
 int32_t mf_ray_clip(const float* rays, int64_t ray_stride, int64_t n_rays, const uint32_t* bits, int32_t gx, int32_t gy,
                     int32_t gz, const float* lo /* host */, const float* hi /* host */, const float* inv_cell /* host */, float dt,
                     float* t_first, float* t_last, uint8_t* hit, void* stream);
+
+/* ---- occupancy grids from a mesh (csrc/mf_voxelize.hip): the bit grid of mf_occ_build's layout -- (gx, gy, gz) cells over the
+ * box lo .. hi, row (i, j) holding ceil(gz / 32) uint32 words, cell k bit k % 32 of word k / 32, the unused bits of a row's last
+ * word 0 -- built from triangles instead of densities.  The reference labels a point "inside" iff it lies within `thickness` of a
+ * vertex of the posed SMPL mesh (datasets/moco_flow_dataset.py:87-142), derives the frame's AABB from that mesh
+ * (datasets/moco_flow_dataset.py:144-154) and renders every ray of that box's hull (trainer_moco_flow.py:226-268).  All three
+ * entries decide in integers: their results are bit-identical from run to run and equal to tests/voxelize_oracle.py. ----
+ *
+ * mf_voxel_mesh (serves datasets/moco_flow_dataset.py:87-142, datasets/moco_flow_dataset.py:144-154,
+ * trainer_moco_flow.py:226-268): verts (V, 3) fp32 and tris (T, 3) int64 on the device -> the cells the triangles' surfaces meet.
+ * lo, hi, inv_cell: host float[3] each, exactly as mf_ray_clip takes them.  Per vertex coordinate, every fp32 operation rounded
+ * once (no fused multiply-add): u = (p - lo_a) * inv_cell_a (mf_ray_clip's cell rule), q = rintf(u * 64) saturated to
+ * [-2^16, 2^17] -- 64 sub-cell units per cell, 1024 cells below the box to 2048 cells above its origin.  Cell (i, j, k) is set iff
+ * the closed snapped triangle meets the closed box [64 i, 64 i + 64] x [64 j, 64 j + 64] x [64 k, 64 k + 64], decided exactly in
+ * int64 (edge differences < 2^18, normal components < 2^37, a plane test against a box corner < 2^57): a triangle lying in a cell
+ * face sets the cells on both sides, a vertex on a cell corner all eight.  A triangle with an index outside [0, V), a NaN or inf
+ * vertex, or a zero integer normal after snapping is skipped, and counted in dropped_out (device int64[1], optional).  A triangle
+ * that reaches more than 1024 cells outside the box is distorted by the saturation.  The entry clears bits_out itself and then
+ * sets bits with atomic ORs (order-independent).  T = 0 or V = 0: an all-zero grid, only the clear is launched (V = 0: dropped =
+ * T).  Each side 1 .. 1024 and fewer than 2^31 cells, V and T in [0, 2^31), lo_a < hi_a, else MF_E_INVALID. */
+int32_t mf_voxel_mesh(const float* verts, int64_t V, const int64_t* tris, int64_t T, int32_t gx, int32_t gy, int32_t gz,
+                      const float* lo /* host */, const float* hi /* host */, const float* inv_cell /* host */, uint32_t* bits_out,
+                      int64_t* dropped_out, void* stream);
+
+/* mf_voxel_fill (serves datasets/moco_flow_dataset.py:87-142, datasets/moco_flow_dataset.py:144-154,
+ * trainer_moco_flow.py:226-268): a cell of bits_out is set iff it is set in bits, or it is an empty cell that is NOT 6-connected
+ * through empty cells to the outside of the grid (everything beyond the grid counts as empty and connected): a union-find over
+ * the empty cells with one virtual root for the outside (csrc/mf_unionfind.hpp); the result does not depend on the order of the
+ * unions.  An open mesh, or one cut by the box, leaks and fills nothing; a torus's hole stays empty; a closed shell inside a
+ * closed shell is filled through.  scratch: mf_voxel_fill_scratch_bytes bytes (4 per cell).  bits_out may be bits.  Each side
+ * >= 1 and fewer than 2^31 cells, else MF_E_INVALID. */
+int64_t mf_voxel_fill_scratch_bytes(int64_t gx, int64_t gy, int64_t gz);
+int32_t mf_voxel_fill(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, uint32_t* bits_out, void* scratch, void* stream);
+
+/* mf_voxel_dilate (serves datasets/moco_flow_dataset.py:87-142, datasets/moco_flow_dataset.py:144-154,
+ * trainer_moco_flow.py:226-268): cell (i, j, k) of bits_out is set iff some cell of [i - rx, i + rx] x [j - ry, j + ry] x
+ * [k - rz, k + rz], clipped to the grid, is set in bits.  Radii >= 0 of any size.  Separable: z on words (any radius, across
+ * word boundaries), then y, then x; every output word is written by one lane with a plain store, padding bits stay 0.  bits_out
+ * must not be bits.  count_out (device int64[1], optional): the number of set cells, through the fixed-order reduction.
+ * scratch: mf_voxel_dilate_scratch_bytes bytes, always needed.  Each side >= 1 and fewer than 2^31 cells, else MF_E_INVALID. */
+int64_t mf_voxel_dilate_scratch_bytes(int64_t gx, int64_t gy, int64_t gz);
+int32_t mf_voxel_dilate(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, int32_t rx, int32_t ry, int32_t rz,
+                        uint32_t* bits_out, int64_t* count_out, void* scratch, void* stream);
 
 /* ---- sparse lattice queries: sigma only where a bit grid is occupied.  visualize_mesh (trainer_moco_flow.py:490-538,
  * trainer_nerf.py:200-259) evaluates every point of its lattice, and so does the lattice behind mf_occ_build; a body fills about a

@@ -252,6 +252,12 @@ SYMBOLS = {
     "mf_occ_build": (C.c_int32, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int32, _fp, _fp, _fp, _fp]),
     "mf_ray_clip": (C.c_int32, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp, _fp]),
+    "mf_voxel_mesh": (C.c_int32, [_fp, C.c_int64, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp, _fp]),
+    "mf_voxel_fill_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_voxel_fill": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
+    "mf_voxel_dilate_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_voxel_dilate": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
     "mf_lattice_select_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_lattice_select": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int64,
                                       C.POINTER(C.c_int32), _fp, _fp, _fp, _fp, _fp]),

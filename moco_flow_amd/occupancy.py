@@ -3,11 +3,13 @@
 The reference renders every ray inside the hull of the projected AABB (MoCoFlowTrainer.render, trainer_moco_flow.py:226-268)
 from the nearest to the farthest AABB corner (Camera.make_rays, utils/camera.py:134-148; rendering.py:239-249 spreads the
 coarse samples over that whole interval).  A body fills a fraction of the hull and of the interval.  An ``OccupancyGrid`` is
-one bit per cell of a lattice over the AABB, built from ONE ``query_sigma`` call at a frame's image index; ``clip_rays``
+one bit per cell of a lattice over the AABB, built from ONE ``query_sigma`` call at a frame's image index -- or, without any
+network, from the frame's posed SMPL mesh (``from_mesh`` / ``from_smpl``: mf_voxel_mesh, mf_voxel_fill, mf_voxel_dilate); ``clip_rays``
 marches rays through it, ``cull`` turns the result into a ray table, and ``image.render_image(..., occupancy=grid)`` renders
 only the rays that hit.  A grid belongs to one frame index: it serves that frame's overfit view, its novel view and every
 view of its orbit.  Opt-in: nothing changes for a caller that passes no grid."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -23,6 +25,14 @@ _TIGHTEN = ("none", "near", "both")
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _int3(v, what, least):
+    """An int or a 3-tuple of ints >= ``least`` -> a 3-tuple."""
+    t = (v,) * 3 if isinstance(v, (int, np.integer)) and not isinstance(v, bool) else tuple(v) if isinstance(v, (tuple, list)) else None
+    if t is None or len(t) != 3 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least for x in t):
+        raise RuntimeError(f"OccupancyGrid: {what} must be an int or a 3-tuple of ints >= {least}, got {v!r}")
+    return tuple(int(x) for x in t)
 
 
 class OccupancyGrid:
@@ -197,3 +207,132 @@ class OccupancyGrid:
         if self._count is None:
             self._count = self.to_dense().sum().reshape(1)
         return int(self._count.item()) / float(self.dims[0] * self.dims[1] * self.dims[2])
+
+    # ---- grids from a mesh (csrc/mf_voxelize.hip) -----------------------------------------------------------------------------
+
+    @classmethod
+    def from_mesh(cls, verts, tris, aabb, dims=128, dilate=1, thickness=0.0, solid=True, return_dropped=False):
+        """The grid of a triangle mesh -- ``verts`` (V, 3) fp32 and ``tris`` (T, 3) int64 on a 'cuda' device -- over ``aabb``
+        ((2, 3): min and max corner, as ``from_field`` takes it) in ``dims`` cells (an int or (Gx, Gy, Gz), each 1 .. 1024).
+        Three steps, in this order, every one decided in integers and so bit-identical from run to run:
+
+        1. surface (mf_voxel_mesh): vertices go to grid coordinates by ``clip_rays``' cell rule, u = (p - lo) * inv_cell in fp32,
+           and are snapped to 1/64 cell; a cell is set iff the closed snapped triangle meets the closed cell.  A triangle in a
+           cell face sets the cells on both sides.  Triangles with an index outside [0, V), a NaN or inf vertex, or no area after
+           snapping are skipped (``return_dropped=True`` returns ``(grid, dropped)`` with their number, and synchronises to read
+           it; otherwise nothing synchronises).  Snapped coordinates saturate 1024 cells below the box and 2048 cells above its
+           origin: a triangle that reaches further out than that is distorted.
+        2. fill, if ``solid`` (mf_voxel_fill): + every empty cell that is not 6-connected through empty cells to the outside of the
+           grid.  A mesh that is open, or cut by the box, leaks and fills nothing; a torus's hole stays empty; a closed shell
+           inside a closed shell is filled through.
+        3. box dilation (mf_voxel_dilate) by r_a = dilate_a + ceil(thickness / cell_a) cells along axis a, computed in float64 on
+           the host from the grid's ``cell``: ``dilate`` in cells (an int or a 3-tuple, >= 0), ``thickness`` >= 0 in world units.
+           The box of radii r is a deliberate SUPERSET of the Euclidean shell of ``thickness``: it keeps the contract in integers.
+
+        The build's count lands where ``from_sigma`` puts it (``occupied_fraction`` reads it).
+
+        (a) With the reference's ``thickness`` (0.2, datasets/moco_flow_dataset.py:87-142: a point is "inside" iff it lies
+            within ``thickness`` of an SMPL vertex) and ``dilate >= 1``, every point of the box within ``thickness`` of a vertex,
+            inside the box, of a non-skipped triangle falls, by ``clip_rays``' cell rule, in a set cell: the vertex's cell is set
+            (snapping moves a vertex across a cell boundary only onto it, and a point on a boundary sets both sides), the point
+            is at most ceil(thickness / cell_a) cells from it along axis a, and ``dilate`` absorbs the fp32 rounding of u.
+        (b) The true surface lies within 1/128 cell of the snapped one along every axis, hence ``dilate >= 1`` covers it and
+            meets the ``dilate >= 1`` premise of ``clip_rays``' guarantee.
+        (c) What reaches beyond the SMPL shell by more than ``thickness`` is CULLED -- loose clothing and hair are the likely
+            cases.  Check a few frames against an unculled render; no thickness has been validated on a trained checkpoint."""
+        L.require_gpu(verts, "OccupancyGrid.from_mesh")
+        L.require_gpu(tris, "OccupancyGrid.from_mesh")
+        if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+            raise RuntimeError(f"OccupancyGrid.from_mesh: verts must be fp32 (V, 3), got {tuple(verts.shape)} {verts.dtype}")
+        if tris.dim() != 2 or tris.shape[1] != 3 or tris.dtype != torch.int64:
+            raise RuntimeError(f"OccupancyGrid.from_mesh: tris must be int64 (T, 3), got {tuple(tris.shape)} {tris.dtype}")
+        if tris.device != verts.device:
+            raise RuntimeError(f"OccupancyGrid.from_mesh: verts on {verts.device}, tris on {tris.device}")
+        box = np.asarray(aabb, dtype=np.float64)
+        if box.shape != (2, 3):
+            raise RuntimeError(f"OccupancyGrid.from_mesh: aabb must be (2, 3), got {box.shape}")
+        dims = _int3(dims, "dims", 1)
+        dilate = _int3(dilate, "dilate", 0)
+        thickness = float(thickness)
+        if not (0.0 <= thickness < math.inf):
+            raise RuntimeError(f"OccupancyGrid.from_mesh: thickness={thickness} must be finite and >= 0")
+        dev = verts.device
+        v, t = verts.detach().contiguous(), tris.detach().contiguous()
+        bits = torch.empty((dims[0], dims[1], (dims[2] + 31) // 32), dtype=torch.int32, device=dev)
+        surface = cls(bits, dims, box[0], box[1])                         # its lo, hi and inv_cell are what the kernel is given
+        dropped = torch.empty(1, dtype=torch.int64, device=dev) if return_dropped else None
+        V, T = int(v.shape[0]), int(t.shape[0])
+        with torch.cuda.device(dev):
+            L.check(L.lib().mf_voxel_mesh(v.data_ptr() if V else None, V, t.data_ptr() if T else None, T, *dims, _f3(surface.lo),
+                                          _f3(surface.hi), _f3(surface.inv_cell), bits.data_ptr(), L.ptr(dropped),
+                                          L.current_stream(dev)), "mf_voxel_mesh")
+        grid = surface.filled() if solid else surface
+        radii = tuple(dilate[a] + int(math.ceil(thickness / float(surface.cell[a]))) for a in range(3))
+        grid = grid.dilated(radii)
+        return (grid, int(dropped.item())) if return_dropped else grid
+
+    @classmethod
+    def from_smpl(cls, smpl, pose, betas, aabb, **kw):
+        """``from_mesh`` on the posed body: ``smpl(pose, betas)[0]`` and ``smpl.faces`` (``smpl.SMPL``, skinned on the device),
+        bit-identical to those two steps by hand.  ``kw``: ``from_mesh``'s keywords."""
+        faces = getattr(smpl, "faces", None)
+        if faces is None:
+            raise RuntimeError("OccupancyGrid.from_smpl: the SMPL model carries no faces (its 'f' array)")
+        with torch.no_grad():
+            verts = smpl(pose, betas)[0]
+        return cls.from_mesh(verts, faces, aabb, **kw)
+
+    def filled(self):
+        """A new grid over the same box: this one plus every empty cell that is not 6-connected through empty cells to the outside
+        of the grid (mf_voxel_fill).  No synchronisation; the count is left to ``occupied_fraction``."""
+        lib = L.lib()
+        need = int(lib.mf_voxel_fill_scratch_bytes(*self.dims))
+        if need < 0:
+            L.check(need, "mf_voxel_fill_scratch_bytes")
+        dev = self.device
+        src = self.bits.contiguous()
+        out = torch.empty_like(src)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mf_voxel_fill(src.data_ptr(), *self.dims, out.data_ptr(), scratch.data_ptr(), L.current_stream(dev)),
+                    "mf_voxel_fill")
+        return OccupancyGrid(out, self.dims, self.lo, self.hi)
+
+    def dilated(self, radii):
+        """A new grid over the same box: cell (i, j, k) is set iff a cell of [i - rx, i + rx] x [j - ry, j + ry] x [k - rz, k + rz],
+        clipped to the grid, is set here (mf_voxel_dilate).  ``radii``: an int or (rx, ry, rz), >= 0, of any size.  Works on any
+        grid, one from a field included.  No synchronisation; the new grid carries its count."""
+        radii = _int3(radii, "radii", 0)
+        if any(r >= 1 << 31 for r in radii):
+            raise RuntimeError(f"OccupancyGrid.dilated: radii {radii} do not fit 32 bits")
+        lib = L.lib()
+        need = int(lib.mf_voxel_dilate_scratch_bytes(*self.dims))
+        if need < 0:
+            L.check(need, "mf_voxel_dilate_scratch_bytes")
+        dev = self.device
+        src = self.bits.contiguous()
+        out = torch.empty_like(src)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mf_voxel_dilate(src.data_ptr(), *self.dims, *radii, out.data_ptr(), count.data_ptr(), scratch.data_ptr(),
+                                        L.current_stream(dev)), "mf_voxel_dilate")
+        return OccupancyGrid(out, self.dims, self.lo, self.hi, count)
+
+    def _same_grid(self, other, what):
+        if not isinstance(other, OccupancyGrid):
+            raise RuntimeError(f"OccupancyGrid.{what}: the other operand is {type(other).__name__}, not an OccupancyGrid")
+        if other.dims != self.dims or other.device != self.device or not (np.array_equal(other.lo, self.lo) and np.array_equal(other.hi, self.hi)):
+            raise RuntimeError(f"OccupancyGrid.{what}: grids differ: {self.dims} over {self.lo.tolist()} .. {self.hi.tolist()} on "
+                               f"{self.device} and {other.dims} over {other.lo.tolist()} .. {other.hi.tolist()} on {other.device}")
+
+    def __and__(self, other):
+        """The cells set in both grids (same ``dims``, box and device, else RuntimeError): the SMPL shell cut with a field's grid,
+        say.  Word-wise on ``bits``; the count is left to ``occupied_fraction``."""
+        self._same_grid(other, "__and__")
+        return OccupancyGrid(self.bits & other.bits, self.dims, self.lo, self.hi)
+
+    def __or__(self, other):
+        """The cells set in either grid; as ``&``."""
+        self._same_grid(other, "__or__")
+        return OccupancyGrid(self.bits | other.bits, self.dims, self.lo, self.hi)

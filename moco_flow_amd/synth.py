@@ -174,6 +174,25 @@ def smpl_model(seed=0, n_verts=6890):
                 parent=np.array(SMPL_PARENTS, dtype=np.int64))
 
 
+def smpl_faces(verts, n_faces=13776):
+    """Synthetic triangles (n_faces, 3) int64 over a vertex cloud, SMPL's face count by default: every vertex with its first and
+    second, then with its second and third nearest neighbour -- triangles as local as a skinned body's, NOT a closed surface
+    (``smpl_model`` has no "f": pass ``dict(smpl_model(...), f=smpl_faces(...))`` to ``smpl.SMPL``)."""
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    V = len(v)
+    near = np.empty((V, 3), dtype=np.int64)
+    for s in range(0, V, 256):
+        d = ((v[s:s + 256, None, :] - v[None, :, :]) ** 2).sum(-1)
+        d[np.arange(len(d)), np.arange(s, s + len(d))] = np.inf
+        three = np.argpartition(d, 3, axis=1)[:, :3]
+        near[s:s + 256] = np.take_along_axis(three, np.argsort(np.take_along_axis(d, three, 1), axis=1, kind="stable"), 1)
+    own = np.arange(V)
+    faces = np.concatenate([np.stack([own, near[:, 0], near[:, 1]], 1), np.stack([own, near[:, 1], near[:, 2]], 1)])
+    if n_faces > len(faces):
+        raise ValueError(f"smpl_faces: {n_faces} faces asked of {V} vertices (at most {len(faces)})")
+    return faces[:n_faces]
+
+
 def smpl_pose(seed=0, batch=1, scale=0.4):
     """(pose (B,72) axis-angle, betas (B,10)) float32."""
     p = normal(_stream_seed(seed, "smpl.pose"), batch * 72).reshape(batch, 72) * scale
