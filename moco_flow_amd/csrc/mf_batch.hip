@@ -18,20 +18,9 @@ constexpr int kCompactTile = kCompactThreads * kCompactPerLane;          // 4096
 constexpr int kCompactMaxBlocks = 1024;                                  // the grid stops growing: longer masks take more trips
 constexpr int kBatchThreads = 256;
 
-struct MaskCompactPlan { long long per; int nblocks; };
-
-// workgroup b owns the bytes [b per, min(n, (b + 1) per)), per a multiple of the tile
-inline MaskCompactPlan mask_compact_plan(long long n) {
-  const long long tiles = (n + kCompactTile - 1) / kCompactTile;
-  const long long nb0 = tiles < kCompactMaxBlocks ? tiles : kCompactMaxBlocks;
-  if (nb0 == 0) return {kCompactTile, 0};
-  const long long per = (tiles + nb0 - 1) / nb0 * kCompactTile;
-  return {per, (int)((n + per - 1) / per)};
-}
-
 struct MaskCompactParams {
   const unsigned char* mask;
-  long long n, per;
+  long long n, per;      // workgroup b owns the bytes [b per, min(n, (b + 1) per)), per a multiple of the tile (share_of)
   int nblocks;
   long long* blk;        // (nblocks) non-zero bytes of each workgroup's share
   long long* inds;
@@ -40,8 +29,8 @@ struct MaskCompactParams {
 
 // launch 1: the per-workgroup counts
 __global__ __launch_bounds__(kCompactThreads) void mask_count_kernel(const MaskCompactParams p) {
-  const long long lo = blockIdx.x * p.per, hi = lo + p.per < p.n ? lo + p.per : p.n;
-  long long c = 0;
+  long long lo, hi, c = 0;
+  share_range(p.per, p.n, lo, hi);
   for (long long i = lo + threadIdx.x; i < hi; i += kCompactThreads) c += p.mask[i] != 0;
   c = block_sum_i64<kCompactThreads>(c);
   if (threadIdx.x == 0) p.blk[blockIdx.x] = c;
@@ -63,7 +52,8 @@ __global__ __launch_bounds__(kCompactThreads) void mask_scatter_kernel(const Mas
     all = block_sum_i64<kCompactThreads>(all);
     if (threadIdx.x == 0) *p.count = all;
   }
-  const long long lo = blockIdx.x * p.per, hi = lo + p.per < p.n ? lo + p.per : p.n;
+  long long lo, hi;
+  share_range(p.per, p.n, lo, hi);
   for (long long tile = lo; tile < hi; tile += kCompactTile) {           // lo, hi: the same for every thread of the workgroup
     const long long wbase = tile + (long long)w * (64 * kCompactPerLane);
     unsigned flags = 0;
@@ -205,7 +195,7 @@ using namespace mf;
 
 extern "C" int64_t mf_mask_compact_scratch_bytes(int64_t n) {
   if (n < 0) { fail(MF_E_INVALID, "mf_mask_compact_scratch_bytes: negative n=%lld", (long long)n); return -1; }
-  return (int64_t)mask_compact_plan(n).nblocks * 8;
+  return (int64_t)share_of(n, kCompactTile, kCompactMaxBlocks).nblocks * 8;
 }
 
 extern "C" int32_t mf_mask_compact(const uint8_t* mask, int64_t n, int64_t* inds_out, int64_t* count, void* scratch, void* stream) {
@@ -225,7 +215,7 @@ extern "C" int32_t mf_mask_compact(const uint8_t* mask, int64_t n, int64_t* inds
     return check_launch("mf_mask_compact (identity)");
   }
   if (!scratch) return fail(MF_E_INVALID, "mf_mask_compact: scratch is null");
-  const MaskCompactPlan plan = mask_compact_plan(n);
+  const Share plan = share_of(n, kCompactTile, kCompactMaxBlocks);
   MaskCompactParams p{mask, (long long)n, plan.per, plan.nblocks, static_cast<long long*>(scratch), inds, cnt};
   hipLaunchKernelGGL(mask_count_kernel, dim3((unsigned)plan.nblocks), dim3(kCompactThreads), 0, s, p);
   hipLaunchKernelGGL(mask_scatter_kernel, dim3((unsigned)plan.nblocks), dim3(kCompactThreads), 0, s, p);

@@ -5,6 +5,7 @@
 #include <cstdio>
 
 #include "../../include/mocoflow_hip.h"
+#include "mf_shares.hpp"   // kIndexLimit, align_up, share_of, Carver
 
 namespace mf {
 
@@ -49,7 +50,12 @@ inline long long capped_blocks(long long n, long long per_block, long long cap, 
 }
 
 inline bool is_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of 2
-inline long long align_up(long long x, long long a) { return (x + a - 1) & ~(a - 1); }
+// the vertex and triangle counts of a unit that indexes a mesh with 32-bit integers
+inline int mesh_index_shape(const char* what, int64_t V, int64_t T) {
+  if (V < 0 || T < 0 || V >= kIndexLimit || T >= kIndexLimit)
+    return fail(MF_E_INVALID, "%s: V=%lld T=%lld (32-bit indexing: both in [0, 2^31))", what, (long long)V, (long long)T);
+  return MF_OK;
+}
 // torch.nn.Softplus(): beta 1, threshold 20 (the render pass, the composite, mf_point_loss_partials, the occupancy grid)
 __device__ __forceinline__ float softplus_torch(float s) { return s > 20.f ? s : log1pf(expf(s)); }
 

@@ -220,14 +220,13 @@ int mc_shape(const char* what, int64_t n0, int64_t n1, int64_t n2, McParams& p) 
   return MF_OK;
 }
 
-// scratch: off int64 [2 nb] | blk int32 [2 nb] | map int32 [P]
-int64_t mc_scratch(const McParams& p) { return 16LL * p.nblocks + 8LL * p.nblocks + 4LL * p.P; }
-
-void mc_bind(McParams& p, void* scratch) {
-  char* base = static_cast<char*>(scratch);
-  p.off = reinterpret_cast<long long*>(base);
-  p.blk = reinterpret_cast<int*>(base + 16LL * p.nblocks);
-  p.map = reinterpret_cast<int*>(base + 24LL * p.nblocks);
+// scratch: off int64 [2 nb] | blk int32 [2 nb] | map int32 [P], unpadded.  Binds the three and returns the size
+int64_t mc_bind(McParams& p, void* scratch) {
+  Carver c(scratch);
+  p.off = c.take<long long>(2LL * p.nblocks);
+  p.blk = c.take<int>(2LL * p.nblocks, 8);
+  p.map = c.take<int>(p.P, 4);
+  return c.bytes();
 }
 
 // ---- vertex normals from the volume (mf_mc_normals): one thread per vertex, a gather of at most 12 values
@@ -305,7 +304,7 @@ bool vec_rows(const McParams& p) { return p.n2 % 4 == 0 && is_aligned(p.vol, 16)
 extern "C" int64_t mf_mc_scratch_bytes(int64_t n0, int64_t n1, int64_t n2) {
   McParams p{};
   const int rc = mc_shape("mf_mc_scratch_bytes", n0, n1, n2, p);
-  return rc != MF_OK ? rc : mc_scratch(p);
+  return rc != MF_OK ? rc : mc_bind(p, nullptr);
 }
 
 extern "C" int32_t mf_mc_count(const float* vol, int64_t n0, int64_t n1, int64_t n2, float iso, int32_t clamp_zero,

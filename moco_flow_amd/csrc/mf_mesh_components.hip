@@ -31,19 +31,10 @@ constexpr int kMaxBlocks = 2048;                 // grid-stride loops: the grid 
 // components) 1.32 / 1.68 / 1.88 ms, the random test NeRF's sigma (100 M triangles in 1.5 M components) 12.0 / 8.6 / 8.0 ms;
 // a trained field's surface is the first kind.
 constexpr int kUnionBlocks = 512;
-constexpr long long kIndexLimit = 1LL << 31;     // 32-bit internal indexing
 
 inline unsigned grid_for(long long n, int cap = kMaxBlocks) { return (unsigned)capped_blocks(n, kThreads, cap, 1); }
 
 using namespace mf::uf;                          // ld / st, find_root, unite, WaveCount / wave_count / wave_count_flush
-
-__device__ __forceinline__ bool in_range(long long i, long long n) { return (unsigned long long)i < (unsigned long long)n; }
-
-// sum over the wave, added once to a device counter; every lane of the wave calls it
-__device__ __forceinline__ void wave_add(long long* counter, long long v) {
-  v = wave_sum_i64(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
-}
 
 __global__ __launch_bounds__(kThreads) void init_kernel(int* parent, long long V) {
   for (long long v = (long long)blockIdx.x * kThreads + threadIdx.x; v < V; v += (long long)gridDim.x * kThreads) parent[v] = (int)v;
@@ -134,15 +125,14 @@ __global__ __launch_bounds__(kThreads) void table_gather_kernel(const long long*
 struct TableScratch { int* tcount; int* vcount; unsigned char* is_root; long long* slot; void* compact; long long bytes; };
 
 inline TableScratch table_scratch(void* scratch, long long V) {
-  char* base = static_cast<char*>(scratch);
+  Carver c(scratch);
   TableScratch s;
-  long long o = 0;
-  s.tcount = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.vcount = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.is_root = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
-  s.slot = reinterpret_cast<long long*>(base + o); o += 16;
-  s.compact = base + o; o += align_up(mf_mask_compact_scratch_bytes(V), 16);
-  s.bytes = o;
+  s.tcount = c.take<int>(V);
+  s.vcount = c.take<int>(V);
+  s.is_root = c.take<unsigned char>(V);
+  s.slot = c.take<long long>(1);
+  s.compact = c.take<char>(mf_mask_compact_scratch_bytes(V));
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -220,17 +210,16 @@ __global__ __launch_bounds__(kThreads) void reindex_kernel(const long long* tris
 struct FilterScratch { unsigned char* keep_root; unsigned char* vflag; unsigned char* tflag; int* remap; long long* slot; void* compact; long long bytes; };
 
 inline FilterScratch filter_scratch(void* scratch, long long V, long long T) {
-  char* base = static_cast<char*>(scratch);
+  Carver c(scratch);
   FilterScratch s;
-  long long o = 0;
-  s.keep_root = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
-  s.vflag = reinterpret_cast<unsigned char*>(base + o); o += align_up(V, 16);
-  s.tflag = reinterpret_cast<unsigned char*>(base + o); o += align_up(T, 16);
-  s.remap = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.slot = reinterpret_cast<long long*>(base + o); o += 16;
+  s.keep_root = c.take<unsigned char>(V);
+  s.vflag = c.take<unsigned char>(V);
+  s.tflag = c.take<unsigned char>(T);
+  s.remap = c.take<int>(V);
+  s.slot = c.take<long long>(1);
   const long long cv = mf_mask_compact_scratch_bytes(V), ct = mf_mask_compact_scratch_bytes(T);   // not monotonic in n
-  s.compact = base + o; o += align_up(cv > ct ? cv : ct, 16);
-  s.bytes = o;
+  s.compact = c.take<char>(cv > ct ? cv : ct);
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -246,25 +235,19 @@ __global__ __launch_bounds__(kThreads) void gather_rows_kernel(const W* src, lon
   }
 }
 
-int mesh_shape(const char* what, int64_t V, int64_t T) {
-  if (V < 0 || T < 0 || V >= kIndexLimit || T >= kIndexLimit)
-    return fail(MF_E_INVALID, "%s: V=%lld T=%lld (32-bit indexing: both in [0, 2^31))", what, (long long)V, (long long)T);
-  return MF_OK;
-}
-
 }  // namespace cc
 }  // namespace mf
 
 using namespace mf::cc;
 
 extern "C" int64_t mf_mesh_label_scratch_bytes(int64_t V, int64_t T) {
-  const int rc = mesh_shape("mf_mesh_label_scratch_bytes", V, T);
+  const int rc = mesh_index_shape("mf_mesh_label_scratch_bytes", V, T);
   return rc != MF_OK ? rc : align_up(4 * V, 16);
 }
 
 extern "C" int32_t mf_mesh_label(const int64_t* tris, int64_t T, int64_t V, int64_t* labels, int64_t* bad, void* scratch,
                                  void* stream) {
-  const int rc = mesh_shape("mf_mesh_label", V, T);
+  const int rc = mesh_index_shape("mf_mesh_label", V, T);
   if (rc != MF_OK) return rc;
   if (!bad) return fail(MF_E_INVALID, "mf_mesh_label: bad is null");
   if (T > 0 && !tris) return fail(MF_E_INVALID, "mf_mesh_label: tris is null");
@@ -282,13 +265,13 @@ extern "C" int32_t mf_mesh_label(const int64_t* tris, int64_t T, int64_t V, int6
 }
 
 extern "C" int64_t mf_mesh_table_scratch_bytes(int64_t V, int64_t T) {
-  const int rc = mesh_shape("mf_mesh_table_scratch_bytes", V, T);
+  const int rc = mesh_index_shape("mf_mesh_table_scratch_bytes", V, T);
   return rc != MF_OK ? rc : table_scratch(nullptr, V).bytes;
 }
 
 extern "C" int32_t mf_mesh_table_count(const int64_t* tris, int64_t T, int64_t V, const int64_t* labels, int64_t* counts,
                                        void* scratch, void* stream) {
-  const int rc = mesh_shape("mf_mesh_table_count", V, T);
+  const int rc = mesh_index_shape("mf_mesh_table_count", V, T);
   if (rc != MF_OK) return rc;
   if (!counts) return fail(MF_E_INVALID, "mf_mesh_table_count: counts is null");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -308,7 +291,7 @@ extern "C" int32_t mf_mesh_table_count(const int64_t* tris, int64_t T, int64_t V
 
 extern "C" int32_t mf_mesh_table_emit(int64_t V, int64_t C, void* scratch, int64_t* ids, int64_t* tri_counts, int64_t* vert_counts,
                                       void* stream) {
-  const int rc = mesh_shape("mf_mesh_table_emit", V, 0);
+  const int rc = mesh_index_shape("mf_mesh_table_emit", V, 0);
   if (rc != MF_OK) return rc;
   if (C < 0 || C > V) return fail(MF_E_INVALID, "mf_mesh_table_emit: C=%lld of V=%lld", (long long)C, (long long)V);
   if (C == 0) return MF_OK;
@@ -323,13 +306,13 @@ extern "C" int32_t mf_mesh_table_emit(int64_t V, int64_t C, void* scratch, int64
 }
 
 extern "C" int64_t mf_mesh_filter_scratch_bytes(int64_t V, int64_t T) {
-  const int rc = mesh_shape("mf_mesh_filter_scratch_bytes", V, T);
+  const int rc = mesh_index_shape("mf_mesh_filter_scratch_bytes", V, T);
   return rc != MF_OK ? rc : filter_scratch(nullptr, V, T).bytes;
 }
 
 extern "C" int32_t mf_mesh_filter_plan(const int64_t* tris, int64_t T, int64_t V, const int64_t* labels, const int64_t* ids,
                                        const uint8_t* keep, int64_t C, int64_t* counts, void* scratch, void* stream) {
-  const int rc = mesh_shape("mf_mesh_filter_plan", V, T);
+  const int rc = mesh_index_shape("mf_mesh_filter_plan", V, T);
   if (rc != MF_OK) return rc;
   if (C < 0 || C > V) return fail(MF_E_INVALID, "mf_mesh_filter_plan: C=%lld of V=%lld", (long long)C, (long long)V);
   if (!counts) return fail(MF_E_INVALID, "mf_mesh_filter_plan: counts is null");
@@ -354,7 +337,7 @@ extern "C" int32_t mf_mesh_filter_plan(const int64_t* tris, int64_t T, int64_t V
 
 extern "C" int32_t mf_mesh_filter_emit(const int64_t* tris, int64_t T, int64_t V, int64_t Vk, int64_t Tk, void* scratch,
                                        int64_t* vert_inds, int64_t* tri_inds, int64_t* tris_out, void* stream) {
-  const int rc = mesh_shape("mf_mesh_filter_emit", V, T);
+  const int rc = mesh_index_shape("mf_mesh_filter_emit", V, T);
   if (rc != MF_OK) return rc;
   if (Vk < 0 || Vk > V || Tk < 0 || Tk > T)
     return fail(MF_E_INVALID, "mf_mesh_filter_emit: Vk=%lld of V=%lld, Tk=%lld of T=%lld", (long long)Vk, (long long)V, (long long)Tk, (long long)T);

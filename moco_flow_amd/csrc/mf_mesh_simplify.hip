@@ -40,29 +40,12 @@ namespace sm {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;                 // as mf_mesh_components.hip: the grid stops growing at 8 waves per SIMD of 256 CUs
-constexpr long long kIndexLimit = 1LL << 31;     // 32-bit internal indexing: V, T, cells and slots
-constexpr int kEmpty = -1;
+constexpr int kEmpty = -1;                       // (kIndexLimit, mf_shares.hpp, bounds V, T, cells and slots)
 constexpr double kFrac = 1048576.0;              // 2^20 fixed-point steps per cell
 
 using namespace mf::uf;                          // ld, WaveCount / wave_count / wave_count_flush
 
 inline unsigned grid_for(long long n) { return (unsigned)capped_blocks(n, kThreads, kMaxBlocks, 1); }
-
-// a kernel whose ranks follow the input order gives every workgroup one contiguous share of whole tiles
-struct Share { int nblocks; long long per; };
-inline Share share_of(long long n) {
-  Share s;
-  s.nblocks = (int)capped_blocks(n, kThreads, kMaxBlocks, 0);
-  s.per = s.nblocks ? align_up((n + s.nblocks - 1) / s.nblocks, kThreads) : 0;
-  return s;
-}
-
-__device__ __forceinline__ bool in_range(long long i, long long n) { return (unsigned long long)i < (unsigned long long)n; }
-
-__device__ __forceinline__ void wave_add(long long* counter, long long v) {
-  v = wave_sum_i64(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
-}
 
 // sums[3 key + a] += q[a] for every valid lane, summed on chip first where lanes of the wave share the key (a mesh's vertices
 // come sorted by lattice edge: neighbours share a cell): per distinct key one add per axis of the lanes' sum, as uf::wave_count
@@ -124,7 +107,7 @@ struct Params {
   int* wprefix;                 // [nwords] used cells in the words in front
   long long* blk_t;             // [kMaxBlocks] survivors of each workgroup's share, then their exclusive prefix
   long long* blk_w;             // [kMaxBlocks] used cells of each workgroup's share of the words, then the prefix
-  Share st, sw;
+  Share st, sw;                 // contiguous shares of the triangles and of the words: the ranks follow the input order
   long long* counts;            // [Vk, Tk, bad]
   // emit
   long long Vk, Tk;
@@ -203,8 +186,8 @@ __device__ __forceinline__ int lookup(const Params& p, const Key& k) {
 }
 
 __global__ __launch_bounds__(kThreads) void survive_kernel(const Params p) {
-  const long long lo = blockIdx.x * p.st.per, hi = lo + p.st.per < p.T ? lo + p.st.per : p.T;
-  long long n = 0;
+  long long lo, hi, n = 0;
+  share_range(p.st.per, p.T, lo, hi);
   for (long long t = lo + threadIdx.x; t < hi; t += kThreads) {
     Key k; bool bad;
     const bool s = tri_key(p, t, k, bad) && lookup(p, k) == (int)t;
@@ -221,8 +204,8 @@ __global__ __launch_bounds__(kThreads) void survive_kernel(const Params p) {
 }
 
 __global__ __launch_bounds__(kThreads) void word_count_kernel(const Params p) {
-  const long long lo = blockIdx.x * p.sw.per, hi = lo + p.sw.per < p.nwords ? lo + p.sw.per : p.nwords;
-  long long n = 0;
+  long long lo, hi, n = 0;
+  share_range(p.sw.per, p.nwords, lo, hi);
   for (long long w = lo + threadIdx.x; w < hi; w += kThreads) n += __popc(p.mask[w]);
   n = block_sum_i64<kThreads>(n);
   if (threadIdx.x == 0) p.blk_w[blockIdx.x] = n;
@@ -239,8 +222,8 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(const Params p) {
 }
 
 __global__ __launch_bounds__(kThreads) void word_prefix_kernel(const Params p) {
-  const long long lo = blockIdx.x * p.sw.per, hi = lo + p.sw.per < p.nwords ? lo + p.sw.per : p.nwords;
-  long long base = p.blk_w[blockIdx.x];
+  long long lo, hi, base = p.blk_w[blockIdx.x];
+  share_range(p.sw.per, p.nwords, lo, hi);
   for (long long tile = lo; tile < hi; tile += kThreads) {               // lo, hi: the same for every thread of the workgroup
     const long long w = tile + threadIdx.x;
     const int c = w < hi ? __popc(p.mask[w]) : 0;                        // 0 .. 32: six bits
@@ -306,8 +289,8 @@ __global__ __launch_bounds__(kThreads) void mean_kernel(const Params p) {
 }
 
 __global__ __launch_bounds__(kThreads) void tris_kernel(const Params p) {
-  const long long lo = blockIdx.x * p.st.per, hi = lo + p.st.per < p.T ? lo + p.st.per : p.T;
-  long long base = p.blk_t[blockIdx.x];
+  long long lo, hi, base = p.blk_t[blockIdx.x];
+  share_range(p.st.per, p.T, lo, hi);
   for (long long tile = lo; tile < hi; tile += kThreads) {
     const long long t = tile + threadIdx.x;
     const bool s = t < hi && p.tflag[t] != 0;
@@ -332,23 +315,21 @@ __global__ __launch_bounds__(kThreads) void tris_kernel(const Params p) {
 struct Scratch { int* cellid; unsigned char* tflag; unsigned* mask; int* wprefix; long long* blk_t; long long* blk_w; int* table; long long bytes; };
 
 inline Scratch scratch_of(void* scratch, long long V, long long T, long long nwords, long long slots) {
-  char* base = static_cast<char*>(scratch);
+  Carver c(scratch);
   Scratch s;
-  long long o = 0;
-  s.cellid = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.tflag = reinterpret_cast<unsigned char*>(base + o); o += align_up(T, 16);
-  s.mask = reinterpret_cast<unsigned*>(base + o); o += align_up(4 * nwords, 16);
-  s.wprefix = reinterpret_cast<int*>(base + o); o += align_up(4 * nwords, 16);
-  s.blk_t = reinterpret_cast<long long*>(base + o); o += 8 * kMaxBlocks;
-  s.blk_w = reinterpret_cast<long long*>(base + o); o += 8 * kMaxBlocks;
-  s.table = reinterpret_cast<int*>(base + o); o += align_up(4 * slots, 16);
-  s.bytes = o;
+  s.cellid = c.take<int>(V);
+  s.tflag = c.take<unsigned char>(T);
+  s.mask = c.take<unsigned>(nwords);
+  s.wprefix = c.take<int>(nwords);
+  s.blk_t = c.take<long long>(kMaxBlocks);
+  s.blk_w = c.take<long long>(kMaxBlocks);
+  s.table = c.take<int>(slots);
+  s.bytes = c.bytes();
   return s;
 }
 
 int shape(const char* what, int64_t V, int64_t T, int64_t n0, int64_t n1, int64_t n2, long long& ncells) {
-  if (V < 0 || T < 0 || V >= kIndexLimit || T >= kIndexLimit)
-    return fail(MF_E_INVALID, "%s: V=%lld T=%lld (32-bit indexing: both in [0, 2^31))", what, (long long)V, (long long)T);
+  if (const int rc = mesh_index_shape(what, V, T); rc != MF_OK) return rc;
   if (n0 < 1 || n1 < 1 || n2 < 1 || n0 >= kIndexLimit || n1 >= kIndexLimit || n2 >= kIndexLimit || n0 * n1 >= kIndexLimit ||
       n0 * n1 * n2 >= kIndexLimit)
     return fail(MF_E_INVALID, "%s: %lld x %lld x %lld cells (each axis at least 1, the product below 2^31)", what, (long long)n0,
@@ -416,7 +397,7 @@ extern "C" int32_t mf_simplify_mesh_plan(const float* verts, int64_t V, const in
   p.slot_mask = (unsigned)(slots - 1);
   p.cellid = sc.cellid; p.table = sc.table; p.tflag = sc.tflag; p.mask = sc.mask; p.wprefix = sc.wprefix;
   p.blk_t = sc.blk_t; p.blk_w = sc.blk_w;
-  p.st = share_of(T); p.sw = share_of(nwords);
+  p.st = share_of(T, kThreads, kMaxBlocks); p.sw = share_of(nwords, kThreads, kMaxBlocks);
   p.counts = reinterpret_cast<long long*>(counts);
   if (V > 0) hipLaunchKernelGGL(cell_kernel, dim3(grid_for(V)), dim3(kThreads), 0, s, p);
   if (T == 0) return check_launch(what);                                  // no survivor: Vk = Tk = 0, the emit step launches nothing
@@ -458,7 +439,7 @@ extern "C" int32_t mf_simplify_mesh_emit(const float* verts, int64_t V, const in
   p.tris = reinterpret_cast<const long long*>(tris); p.T = T;
   p.ncells = ncells; p.nwords = nwords;
   p.cellid = sc.cellid; p.tflag = sc.tflag; p.mask = sc.mask; p.wprefix = sc.wprefix; p.blk_t = sc.blk_t; p.blk_w = sc.blk_w;
-  p.st = share_of(T); p.sw = share_of(nwords);
+  p.st = share_of(T, kThreads, kMaxBlocks); p.sw = share_of(nwords, kThreads, kMaxBlocks);
   p.Vk = Vk; p.Tk = Tk;
   p.sums = static_cast<long long*>(sums);
   p.members = sums ? reinterpret_cast<int*>(p.sums + 3 * Vk) : nullptr;

@@ -44,28 +44,11 @@ namespace rg {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;                 // as mf_mesh_components.hip: the grid stops growing at 8 waves per SIMD of 256 CUs
-constexpr long long kIndexLimit = 1LL << 31;     // 32-bit internal indexing: V and 6 T
-constexpr int kShort = 32;                       // raw entries a single lane sorts
+constexpr int kShort = 32;                       // raw entries a single lane sorts (kIndexLimit, mf_shares.hpp, bounds V and 6 T)
 constexpr int kMaxRaw = 2 * MF_MESH_MAX_TRIANGLES_PER_VERTEX;   // raw entries of a vertex at the cap: the LDS of the long path
 static_assert(kMaxRaw == 4096 && (kMaxRaw & (kMaxRaw - 1)) == 0, "the bitonic network sorts a power of two");
 
 inline unsigned grid_for(long long n) { return (unsigned)capped_blocks(n, kThreads, kMaxBlocks, 1); }
-
-// a kernel whose prefix follows the vertex order gives every workgroup one contiguous share of whole tiles
-struct Share { int nblocks; long long per; };
-inline Share share_of(long long n) {
-  Share s;
-  s.nblocks = (int)capped_blocks(n, kThreads, kMaxBlocks, 0);
-  s.per = s.nblocks ? align_up((n + s.nblocks - 1) / s.nblocks, kThreads) : 0;
-  return s;
-}
-
-__device__ __forceinline__ bool in_range(long long i, long long n) { return (unsigned long long)i < (unsigned long long)n; }
-
-__device__ __forceinline__ void wave_add(long long* counter, long long v) {
-  v = wave_sum_i64(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
-}
 
 struct Params {
   const long long* tris; long long T, V;
@@ -77,8 +60,8 @@ struct Params {
   long long* blk;               // [kMaxBlocks] totals of the shares, then their exclusive prefix
   int* list; long long list_cap;
   int* raw;                     // [6 T]
-  Share sv;
   long long* offsets;           // [V + 1] public
+  Share sv;                     // contiguous shares of the vertices: the prefix follows the vertex order
   unsigned char* boundary;      // [V] public
   long long* ring; long long R; // emit
 };
@@ -107,8 +90,8 @@ __global__ __launch_bounds__(kThreads) void ring_count_kernel(const Params p) {
 // phase 0 scans deg into raw_off, phase 1 scans ucount into offsets
 __global__ __launch_bounds__(kThreads) void ring_sum_kernel(const Params p, const int phase) {
   const int* vals = phase ? p.ucount : p.deg;
-  const long long lo = blockIdx.x * p.sv.per, hi = lo + p.sv.per < p.V ? lo + p.sv.per : p.V;
-  long long n = 0, over = 0;
+  long long lo, hi, n = 0, over = 0;
+  share_range(p.sv.per, p.V, lo, hi);
   for (long long v = lo + threadIdx.x; v < hi; v += kThreads) {
     const int d = vals[v];
     n += d;
@@ -131,8 +114,8 @@ __global__ __launch_bounds__(kThreads) void ring_top_kernel(const Params p, cons
 
 __global__ __launch_bounds__(kThreads) void ring_prefix_kernel(const Params p, const int phase) {
   const int* vals = phase ? p.ucount : p.deg;
-  const long long lo = blockIdx.x * p.sv.per, hi = lo + p.sv.per < p.V ? lo + p.sv.per : p.V;
-  long long base = p.blk[blockIdx.x];
+  long long lo, hi, base = p.blk[blockIdx.x];
+  share_range(p.sv.per, p.V, lo, hi);
   for (long long tile = lo; tile < hi; tile += kThreads) {                 // lo, hi: the same for every thread of the workgroup
     const long long v = tile + threadIdx.x;
     const int d = v < hi ? vals[v] : 0;
@@ -277,23 +260,23 @@ __global__ __launch_bounds__(kThreads) void ring_emit_long_kernel(const Params p
 struct Scratch { int* hdr; int* deg; int* raw_off; int* ucount; long long* blk; int* list; long long list_cap; int* raw; long long bytes; };
 
 inline Scratch scratch_of(void* scratch, long long V, long long T) {
-  const uintptr_t base = reinterpret_cast<uintptr_t>(scratch);    // integers: a size query passes null
+  Carver c(scratch);
   Scratch s;
-  long long o = 0;
   s.list_cap = std::min(V, 6 * T / (kShort + 1) + 1);
-  s.hdr = reinterpret_cast<int*>(base + o); o += 16;
-  s.deg = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.raw_off = reinterpret_cast<int*>(base + o); o += align_up(4 * (V + 1), 16);
-  s.ucount = reinterpret_cast<int*>(base + o); o += align_up(4 * V, 16);
-  s.blk = reinterpret_cast<long long*>(base + o); o += 8 * kMaxBlocks;
-  s.list = reinterpret_cast<int*>(base + o); o += align_up(4 * s.list_cap, 16);
-  s.raw = reinterpret_cast<int*>(base + o); o += align_up(24 * T, 16);
-  s.bytes = o;
+  s.hdr = c.take<int>(4);
+  s.deg = c.take<int>(V);
+  s.raw_off = c.take<int>(V + 1);
+  s.ucount = c.take<int>(V);
+  s.blk = c.take<long long>(kMaxBlocks);
+  s.list = c.take<int>(s.list_cap);
+  s.raw = c.take<int>(6 * T);
+  s.bytes = c.bytes();
   return s;
 }
 
 int shape(const char* what, int64_t V, int64_t T) {
-  if (V < 0 || T < 0 || V >= kIndexLimit || T >= kIndexLimit || 6 * T >= kIndexLimit)
+  if (const int rc = mesh_index_shape(what, V, T); rc != MF_OK) return rc;
+  if (6 * T >= kIndexLimit)
     return fail(MF_E_INVALID, "%s: V=%lld T=%lld (32-bit indexing: V and 6 T in [0, 2^31))", what, (long long)V, (long long)T);
   return MF_OK;
 }
@@ -303,7 +286,7 @@ Params params_of(const Scratch& sc, const int64_t* tris, int64_t T, int64_t V) {
   p.tris = reinterpret_cast<const long long*>(tris); p.T = T; p.V = V;
   p.hdr = sc.hdr; p.deg = sc.deg; p.raw_off = sc.raw_off; p.ucount = sc.ucount; p.blk = sc.blk;
   p.list = sc.list; p.list_cap = sc.list_cap; p.raw = sc.raw;
-  p.sv = share_of(V);
+  p.sv = share_of(V, kThreads, kMaxBlocks);
   return p;
 }
 
@@ -369,14 +352,13 @@ __global__ __launch_bounds__(kThreads) void smooth_unpack_kernel(const float4* _
 struct SmoothScratch { float4* a; float4* b; int* off32; int* ring32; long long bytes; };
 
 inline SmoothScratch smooth_scratch_of(void* scratch, long long V, long long R) {
-  const uintptr_t base = reinterpret_cast<uintptr_t>(scratch);    // integers: a size query passes null
+  Carver c(scratch);
   SmoothScratch s;
-  long long o = 0;
-  s.a = reinterpret_cast<float4*>(base + o); o += 16 * V;
-  s.b = reinterpret_cast<float4*>(base + o); o += 16 * V;
-  s.off32 = reinterpret_cast<int*>(base + o); o += align_up(4 * (V + 1), 16);
-  s.ring32 = reinterpret_cast<int*>(base + o); o += align_up(4 * R, 16);
-  s.bytes = o;
+  s.a = c.take<float4>(V);
+  s.b = c.take<float4>(V);
+  s.off32 = c.take<int>(V + 1);
+  s.ring32 = c.take<int>(R);
+  s.bytes = c.bytes();
   return s;
 }
 

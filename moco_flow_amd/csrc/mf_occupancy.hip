@@ -72,10 +72,7 @@ __global__ __launch_bounds__(kOccThreads) void occ_build_kernel(const OccBuildPa
 }
 
 __global__ __launch_bounds__(kOccThreads) void occ_count_finish_kernel(const double* parts, long long n_parts, long long* count) {
-  __shared__ double total[1];
-  gather_sum_d<kOccThreads, 1>(parts, n_parts, total);                     // integers below 2^31: exact in any order
-  __syncthreads();
-  if (threadIdx.x == 0) *count = (long long)total[0];
+  count_finish<kOccThreads>(parts, n_parts, count);
 }
 
 struct RayClipParams {

@@ -2,6 +2,8 @@
 //   mf_loss.hip       loss_partials_kernel / loss_finish_kernel               12 slots
 //   mf_supervise.hip  point_loss_partials_kernel / point_loss_finish_kernel    5 slots
 //   mf_metrics.hip    ssim_kernel, sqerr_kernel / metrics_finish_kernel        2 slots
+//   mf_occupancy.hip  occ_build_kernel / occ_count_finish_kernel               1 slot (count_finish)
+//   mf_voxelize.hip   voxel_dilate_rows_kernel / voxel_count_finish_kernel     1 slot (count_finish)
 // THE CONTRACT IS THE ORDER OF THE ADDITIONS; "two runs are bit-identical, no atomics"  rests on it:
 //   a thread      adds its own elements (or, in a finish, the partial rows t, t + THREADS, t + 2 THREADS, ...) in ascending order
 //   wave_sum_d    adds the 64 lanes of a wave in the fixed tree below
@@ -75,6 +77,16 @@ __device__ inline void gather_sum_d(const double* parts, long long n_parts, doub
     for (int k = 0; k < SLOTS; ++k) v[k] += parts[i * SLOTS + k];
   }
   block_sum_d<THREADS, SLOTS>(v, dst);
+}
+
+// The finishing workgroup of a cell count (occ_count_finish_kernel, voxel_count_finish_kernel): the partials are popcounts,
+// integers whose sum stays below 2^31, so the float64 sum is exact in any order.
+template <int THREADS>
+__device__ inline void count_finish(const double* parts, long long n_parts, long long* count) {
+  __shared__ double total[1];
+  gather_sum_d<THREADS, 1>(parts, n_parts, total);
+  __syncthreads();
+  if (threadIdx.x == 0) *count = (long long)total[0];
 }
 
 }  // namespace mf

@@ -40,7 +40,6 @@ constexpr int kRegTileW = 64;                   // one wave spans a tile row
 constexpr int kRegThreads = 256;
 constexpr int kRegMaxBlocks = 2048;             // grid-stride loops: the grid stops growing at 8 waves per SIMD of 256 CUs
 constexpr int kRegWaves = kRegThreads / 64;
-constexpr long long kIndexLimit = 1LL << 31;    // 32-bit internal indexing
 static_assert(kRegTileW == 64, "a wave's ballot is a tile row");
 
 typedef unsigned long long u64;
@@ -195,51 +194,53 @@ __global__ __launch_bounds__(kRegThreads) void reg_flatten_kernel(const Geom g, 
   wave_count_flush(area, wc);
 }
 
-// workgroup b owns the pixels [b per, min(N, (b + 1) per)), per a multiple of the workgroup
-struct SharePlan { long long per; int nblocks; };
-
-inline SharePlan share_plan(long long n) {
-  const long long rounds = (n + kRegThreads - 1) / kRegThreads;
-  const long long nb0 = rounds < kRegMaxBlocks ? rounds : kRegMaxBlocks;
-  if (nb0 == 0) return {kRegThreads, 0};
-  const long long per = (rounds + nb0 - 1) / nb0 * kRegThreads;
-  return {per, (int)((n + per - 1) / per)};
+__device__ __forceinline__ bool is_root(const Geom& g, const int* labels, long long i, int& f, int& l) {
+  l = labels[i];
+  f = (int)(i / g.HW);
+  return l >= 0 && l == (int)(i - (long long)f * g.HW);
 }
 
-// best[f] = max over the roots of (area << 32) | ~label: the largest area, ties to the smaller label; 0 without a member.
-// Adds to one word are served one at a time, so a wave walks a contiguous share and carries (frame, per-lane maximum) until the
-// frame changes: a few atomics per wave, not one per 64 pixels.
-__global__ __launch_bounds__(kRegThreads) void reg_best_kernel(const Geom g, const int* labels, const int* area, u64* best, long long per) {
-  const int lane = threadIdx.x & 63;
-  const long long lo = blockIdx.x * per, hi = lo + per < g.N ? lo + per : g.N;
-  u64 acc = 0;
+// One value per frame from the roots of the stack.  Atomics to one word are served one at a time, so a wave walks a contiguous
+// share and carries (frame, per-lane accumulator) until the frame changes: a few atomics per wave, not one per 64 pixels.
+// value(i, label): what the root at pixel i gives; combine(acc, v): into the lane's accumulator, which starts at T(0);
+// flush(frame, acc): every lane of the wave calls it, it reduces the lanes and sends the result to the frame's word.
+template <class T, class Value, class Combine, class Flush>
+__device__ __forceinline__ void carry_frames(const Geom& g, const int* labels, long long per, Value value, Combine combine, Flush flush) {
+  long long lo, hi;
+  share_range(per, g.N, lo, hi);
+  T acc = 0;
   int fa = -1;                                                           // wave-uniform
-  auto flush = [&]() {
-    u64 v = acc;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(v, d); v = o > v ? o : v; }
-    if (lane == 0 && fa >= 0 && v) atomicMax(best + fa, v);
-    acc = 0;
-  };
   for (long long b = lo; b < hi; b += kRegThreads) {                     // b: the same for the whole wave
     const long long i = b + threadIdx.x;
-    u64 v = 0;
-    int f = -1;
-    if (i < hi) {
-      const int l = labels[i];
-      f = (int)(i / g.HW);
-      if (l >= 0 && l == (int)(i - (long long)f * g.HW)) v = ((u64)(unsigned)area[i] << 32) | (unsigned)~l;
-    }
-    u64 have = __ballot(v != 0);
+    int f = -1, l;
+    const bool root = i < hi && is_root(g, labels, i, f, l);
+    const T v = root ? value(i, l) : T(0);
+    u64 have = __ballot(root);
     while (have) {                                                       // the frames of the wave's roots, in order
       const int f0 = __shfl(f, __ffsll((long long)have) - 1);
-      const bool mine = v != 0 && f == f0;
-      if (f0 != fa) { flush(); fa = f0; }
-      if (mine && v > acc) acc = v;
+      const bool mine = root && f == f0;
+      if (f0 != fa) {
+        if (fa >= 0) flush(fa, acc);
+        acc = 0;
+        fa = f0;
+      }
+      if (mine) combine(acc, v);
       have &= ~__ballot(mine);
     }
   }
-  flush();
+  if (fa >= 0) flush(fa, acc);
+}
+
+// best[f] = max over the roots of (area << 32) | ~label: the largest area, ties to the smaller label; 0 without a member.
+__global__ __launch_bounds__(kRegThreads) void reg_best_kernel(const Geom g, const int* labels, const int* area, u64* best, long long per) {
+  carry_frames<u64>(g, labels, per,
+                    [&](long long i, int l) { return ((u64)(unsigned)area[i] << 32) | (unsigned)~l; },
+                    [](u64& acc, u64 v) { if (v > acc) acc = v; },
+                    [&](int f, u64 v) {
+#pragma unroll
+                      for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(v, d); v = o > v ? o : v; }
+                      if ((threadIdx.x & 63) == 0 && v) atomicMax(best + f, v);
+                    });
 }
 
 __global__ __launch_bounds__(kRegThreads) void reg_select_kernel(const Geom g, const int* labels, const int* area, const u64* best,
@@ -279,37 +280,10 @@ __global__ __launch_bounds__(kRegThreads) void reg_hole_fill_kernel(const Geom g
 }
 
 // ---- table
-__device__ __forceinline__ bool is_root(const Geom& g, const int* labels, long long i, int& f, int& l) {
-  l = labels[i];
-  f = (int)(i / g.HW);
-  return l >= 0 && l == (int)(i - (long long)f * g.HW);
-}
-
 // counts[f] += roots of frame f; a wave carries (frame, per-lane count) along its contiguous share, as reg_best_kernel does
 __global__ __launch_bounds__(kRegThreads) void reg_table_count_kernel(const Geom g, const int* labels, long long* counts, long long per) {
-  const int lane = threadIdx.x & 63;
-  const long long lo = blockIdx.x * per, hi = lo + per < g.N ? lo + per : g.N;
-  long long acc = 0;
-  int fa = -1;
-  auto flush = [&]() {
-    const long long v = wave_sum_i64(acc);
-    if (lane == 0 && fa >= 0 && v) atomicAdd(reinterpret_cast<u64*>(counts + fa), (u64)v);
-    acc = 0;
-  };
-  for (long long b = lo; b < hi; b += kRegThreads) {
-    const long long i = b + threadIdx.x;
-    int f = -1, l;
-    const bool root = i < hi && is_root(g, labels, i, f, l);
-    u64 have = __ballot(root);
-    while (have) {
-      const int f0 = __shfl(f, __ffsll((long long)have) - 1);
-      const bool mine = root && f == f0;
-      if (f0 != fa) { flush(); fa = f0; }
-      acc += mine;
-      have &= ~__ballot(mine);
-    }
-  }
-  flush();
+  carry_frames<long long>(g, labels, per, [](long long, int) { return 1LL; }, [](long long& acc, long long v) { acc += v; },
+                          [&](int f, long long v) { wave_add(counts + f, v); });
 }
 
 // workgroup b owns the pixels [b per, min(N, (b + 1) per)), per a multiple of the workgroup: rank of a root = the roots of the
@@ -329,9 +303,9 @@ struct TableParams {
 
 __global__ __launch_bounds__(kRegThreads) void reg_table_area_kernel(const TableParams p) {
   const Geom& g = p.g;
-  const long long lo = blockIdx.x * p.per, hi = lo + p.per < g.N ? lo + p.per : g.N;
+  long long lo, hi, c = 0;
+  share_range(p.per, g.N, lo, hi);
   WaveCount wc{0, 0};
-  long long c = 0;
   for (long long b = lo; b < hi; b += kRegThreads) {
     const long long i = b + threadIdx.x;
     int f = 0, l = -1;
@@ -347,8 +321,8 @@ __global__ __launch_bounds__(kRegThreads) void reg_table_rows_kernel(const Table
   const Geom& g = p.g;
   long long front = 0;
   for (int b = threadIdx.x; b < (int)blockIdx.x; b += kRegThreads) front += p.blk[b];
-  long long base = block_sum_i64<kRegThreads>(front);
-  const long long lo = blockIdx.x * p.per, hi = lo + p.per < g.N ? lo + p.per : g.N;
+  long long lo, hi, base = block_sum_i64<kRegThreads>(front);
+  share_range(p.per, g.N, lo, hi);
   for (long long b = lo; b < hi; b += kRegThreads) {                     // lo, hi: the same for every thread of the workgroup
     const long long i = b + threadIdx.x;
     int f = 0, l = -1;
@@ -378,7 +352,8 @@ __global__ __launch_bounds__(kRegThreads) void reg_table_rows_kernel(const Table
 __global__ __launch_bounds__(kRegThreads) void reg_table_bbox_kernel(const TableParams p) {
   const Geom& g = p.g;
   const int lane = threadIdx.x & 63;
-  const long long lo = blockIdx.x * p.per, hi = lo + p.per < g.N ? lo + p.per : g.N;
+  long long lo, hi;
+  share_range(p.per, g.N, lo, hi);
   int ck = -1, cx0 = INT_MAX, cy0 = INT_MAX, cx1 = -1, cy1 = -1;        // ck: the same for the whole wave
   auto emit = [&](int kk, int x0, int y0, int x1, int y1) {             // every lane calls it; lane 0 holds the result
 #pragma unroll
@@ -438,16 +413,13 @@ __global__ __launch_bounds__(kRegThreads) void reg_table_bbox_kernel(const Table
 struct Scratch { int* parent; int* area; u64* best; long long* blk; long long bytes; };
 
 inline Scratch scratch_of(void* scratch, const Geom& g) {             // scratch null: the size alone
-  const long long o_area = align_up(4 * g.N, 16), o_best = o_area + align_up(4 * g.N, 16);
-  const long long o_blk = o_best + align_up(8LL * g.F, 16);
-  Scratch s{nullptr, nullptr, nullptr, nullptr, o_blk + 8LL * kRegMaxBlocks};
-  if (scratch) {
-    char* base = static_cast<char*>(scratch);
-    s.parent = reinterpret_cast<int*>(base);
-    s.area = reinterpret_cast<int*>(base + o_area);
-    s.best = reinterpret_cast<u64*>(base + o_best);
-    s.blk = reinterpret_cast<long long*>(base + o_blk);
-  }
+  Carver c(scratch);
+  Scratch s;
+  s.parent = c.take<int>(g.N);
+  s.area = c.take<int>(g.N);
+  s.best = c.take<u64>(g.F);
+  s.blk = c.take<long long>(kRegMaxBlocks);
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -515,7 +487,7 @@ extern "C" int32_t mf_mask_select(const int32_t* labels, int64_t F, int64_t H, i
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Scratch sc = scratch_of(scratch, g);
   if (hipMemsetAsync(sc.best, 0, (size_t)(8LL * g.F), s) != hipSuccess) return fail(MF_E_LAUNCH, "mf_mask_select: hipMemsetAsync failed");
-  const SharePlan plan = share_plan(g.N);
+  const Share plan = share_of(g.N, kRegThreads, kRegMaxBlocks);
   if (largest) hipLaunchKernelGGL(reg_best_kernel, dim3((unsigned)plan.nblocks), dim3(kRegThreads), 0, s, g, labels, sc.area, sc.best, plan.per);
   hipLaunchKernelGGL(reg_select_kernel, dim3(grid_for(g.N)), dim3(kRegThreads), 0, s, g, labels, sc.area, sc.best, (int)(largest != 0),
                      (long long)min_area, out);
@@ -550,7 +522,7 @@ extern "C" int32_t mf_mask_table_count(const int32_t* labels, int64_t F, int64_t
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(counts, 0, (size_t)(8 * F), s) != hipSuccess) return fail(MF_E_LAUNCH, "mf_mask_table_count: hipMemsetAsync failed");
   if (g.N == 0) return MF_OK;
-  const SharePlan plan = share_plan(g.N);
+  const Share plan = share_of(g.N, kRegThreads, kRegMaxBlocks);
   hipLaunchKernelGGL(reg_table_count_kernel, dim3((unsigned)plan.nblocks), dim3(kRegThreads), 0, s, g, labels, reinterpret_cast<long long*>(counts),
                      plan.per);
   return check_launch("mf_mask_table_count");
@@ -569,7 +541,7 @@ extern "C" int32_t mf_mask_table_emit(const int32_t* labels, int64_t F, int64_t 
     return fail(MF_E_INVALID, "mf_mask_table_emit: labels and table must be 4-byte, scratch 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Scratch sc = scratch_of(scratch, g);
-  const SharePlan plan = share_plan(g.N);
+  const Share plan = share_of(g.N, kRegThreads, kRegMaxBlocks);
   TableParams p{g, labels, plan.per, plan.nblocks, (int)frame0, (long long)C, sc.blk, sc.area, sc.parent, table};
   if (hipMemsetAsync(sc.area, 0, (size_t)(4 * g.N), s) != hipSuccess || hipMemsetAsync(table, 0, (size_t)(28 * C), s) != hipSuccess)
     return fail(MF_E_LAUNCH, "mf_mask_table_emit: hipMemsetAsync failed");

@@ -1,6 +1,8 @@
 // mf_scan.hpp -- the ordered integer prefix of the library, written once.  Users: mf_sample.hip (compact_*_kernel: mf_compact_mask),
-// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (cc::wave_add), mf_regions.hip (reg_table_*_kernel),
-// mf_mesh_simplify.hip (the survivors' and the used cells' ranks), mf_mesh_smooth.hip (the raw and the compact ring offsets).
+// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (in_range, wave_add),
+// mf_regions.hip (reg_best_kernel, reg_table_*_kernel), mf_mesh_simplify.hip (the survivors' and the used cells' ranks), mf_mesh_smooth.hip
+// (the raw and the compact ring offsets), mf_lattice.hip (lat_*_kernel).  The four units that walk contiguous shares (mf_shares.hpp:
+// share_of) take their range from share_range.
 // Integer arithmetic: the order of the additions is free.  THE CONTRACT IS WHO RANKS BEFORE WHOM AND WHO SYNCHRONISES; "bit-
 // identical, no atomics, original order kept" (the ray batch) rests on it.  Workgroups are 1-D, whole waves (lane =
 // threadIdx.x & 63, wave = threadIdx.x >> 6); lower lanes rank before higher ones, lower waves and lower threads' shares likewise.
@@ -14,10 +16,20 @@
 //                                 of a tile loop's body): without it a fast wave rewrites a total that a slow one still reads
 //   scan_totals<THREADS, COLS>    the single-workgroup pass, once per kernel: every thread calls it and receives the grand
 //                                 totals; it stores the offsets, the caller stores what it needs of the totals
+//   wave_add                      every lane of the wave calls it: the wave's sum goes to a device counter in one atomic add
+//   share_range                   the workgroup's [lo, hi) of a share_of plan: the same for every thread of the workgroup
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace mf {
+
+__device__ __forceinline__ bool in_range(long long i, long long n) { return (unsigned long long)i < (unsigned long long)n; }   // 0 <= i < n
+
+// workgroup b of a share_of plan (mf_shares.hpp) owns [b per, min(n, (b + 1) per))
+__device__ __forceinline__ void share_range(long long per, long long n, long long& lo, long long& hi) {
+  lo = blockIdx.x * per;
+  hi = lo + per < n ? lo + per : n;
+}
 
 __device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }   // lane 0 .. 63; 0 for lane 0
 __device__ __forceinline__ int wave_popcount(bool m) { return __popcll(__ballot(m)); }                  // the wave's set lanes
@@ -56,6 +68,12 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {         // ever
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
   return v;
+}
+
+// the wave's sum of v, added once to a device counter (an integer sum: any order); nothing is sent for a sum of 0
+__device__ __forceinline__ void wave_add(long long* counter, long long v) {
+  v = wave_sum_i64(v);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)v);
 }
 
 template <int THREADS>

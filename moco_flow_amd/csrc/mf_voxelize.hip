@@ -369,10 +369,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_dilate_rows_kernel(const Vo
 }
 
 __global__ __launch_bounds__(kVoxThreads) void voxel_count_finish_kernel(const double* parts, long long n_parts, long long* count) {
-  __shared__ double total[1];
-  gather_sum_d<kVoxThreads, 1>(parts, n_parts, total);               // integers below 2^31: exact in any order
-  __syncthreads();
-  if (threadIdx.x == 0) *count = (long long)total[0];
+  count_finish<kVoxThreads>(parts, n_parts, count);
 }
 
 inline bool vox_grid_ok(long long gx, long long gy, long long gz, long long max_side) {
@@ -383,6 +380,16 @@ inline bool vox_grid_ok(long long gx, long long gy, long long gz, long long max_
 inline long long vox_words(long long gx, long long gy, long long gz) { return gx * gy * ((gz + 31) / 32); }
 inline long long vox_blocks(long long n_words) { return (n_words + kVoxThreads - 1) / kVoxThreads; }
 constexpr long long kVoxAnySide = (1LL << 31) - 1;
+
+// scratch of the dilation: the z and the y pass's words uint32 [n_words] each | the count's partials float64 [blocks], unpadded.
+// Returns its size.
+inline long long vox_dilate_scratch(void* scratch, long long n_words, unsigned* (&tmp)[2], double*& parts) {
+  Carver c(scratch);
+  tmp[0] = c.take<unsigned>(n_words);
+  tmp[1] = c.take<unsigned>(n_words);
+  parts = c.take<double>(vox_blocks(n_words), 8);
+  return c.bytes();
+}
 
 }  // namespace mf
 
@@ -451,8 +458,9 @@ extern "C" int64_t mf_voxel_dilate_scratch_bytes(int64_t gx, int64_t gy, int64_t
   if (!vox_grid_ok(gx, gy, gz, kVoxAnySide))
     return fail(MF_E_INVALID, "mf_voxel_dilate_scratch_bytes: grid of %lld x %lld x %lld cells (each side >= 1, fewer than 2^31 cells)",
                 (long long)gx, (long long)gy, (long long)gz);
-  const long long n_words = vox_words(gx, gy, gz);
-  return 2 * align_up(n_words * 4, 16) + vox_blocks(n_words) * (int64_t)sizeof(double);   // two passes' words, the count's partials
+  unsigned* tmp[2];
+  double* parts;
+  return vox_dilate_scratch(nullptr, vox_words(gx, gy, gz), tmp, parts);
 }
 
 extern "C" int32_t mf_voxel_dilate(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, int32_t rx, int32_t ry, int32_t rz,
@@ -465,9 +473,9 @@ extern "C" int32_t mf_voxel_dilate(const uint32_t* bits, int32_t gx, int32_t gy,
   VoxDilateParams p{};
   p.gx = gx; p.gy = gy; p.gz = gz; p.wz = (gz + 31) / 32;
   p.n_words = vox_words(gx, gy, gz);
-  const long long slab = align_up(p.n_words * 4, 16);
-  unsigned* tmp[2] = {static_cast<unsigned*>(scratch), reinterpret_cast<unsigned*>(static_cast<char*>(scratch) + slab)};
-  double* parts = reinterpret_cast<double*>(static_cast<char*>(scratch) + 2 * slab);
+  unsigned* tmp[2];
+  double* parts;
+  vox_dilate_scratch(scratch, p.n_words, tmp, parts);
   const long long blocks = vox_blocks(p.n_words);
   const dim3 grid((unsigned)blocks), block(kVoxThreads);
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -1095,3 +1095,144 @@ def test_lazy_vectors_host_logic():
     assert float(torch.mean(v)) == 2.0 and float(cache["local"][0]) == 6.0
     two = torch.cat([v, v], 0)                                       # chunks: sum of sums / sum of counts
     assert float(torch.mean(two)) == pytest.approx(2.0)
+
+
+# What every *_scratch_bytes entry of the units that carve a scratch buffer returned before csrc/mf_shares.hpp carried the carving
+# (recorded from that build, never from the code under test): callers size their buffers with these entries, and the plan and emit
+# halves of an operation find each other's fields by the layout.  Shapes: 0, 1, around one tile (256 elements; 4096 mask bytes)
+# and around the sizes where a grid stops growing (2048 tiles; 1024 mask tiles); -1: refused.
+SCRATCH_BYTES = {
+    "mf_mesh_label_scratch_bytes": [
+        ((0, 0), 0), ((1, 1), 16), ((255, 255), 1024), ((256, 256), 1024), ((257, 257), 1040), ((4095, 4095), 16384),
+        ((4096, 4096), 16384), ((4097, 4097), 16400), ((524287, 524287), 2097152), ((524288, 524288), 2097152),
+        ((524289, 524289), 2097168), ((4194303, 4194303), 16777216), ((4194304, 4194304), 16777216), ((4194305, 4194305), 16777232),
+        ((255, 7), 1024), ((256, 7), 1024), ((257, 7), 1040), ((4095, 7), 16384), ((4096, 7), 16384), ((4097, 7), 16400),
+        ((524287, 7), 2097152), ((524288, 7), 2097152), ((524289, 7), 2097168), ((4194303, 7), 16777216), ((4194304, 7), 16777216),
+        ((4194305, 7), 16777232), ((7, 255), 32), ((7, 256), 32), ((7, 257), 32), ((7, 4095), 32), ((7, 4096), 32), ((7, 4097), 32),
+        ((7, 524287), 32), ((7, 524288), 32), ((7, 524289), 32), ((7, 4194303), 32), ((7, 4194304), 32), ((7, 4194305), 32),
+        ((547600, 1092242), 2190400), ((-1, 0), -1), ((0, 2147483648), -1),
+    ],
+    "mf_mesh_table_scratch_bytes": [
+        ((0, 0), 16), ((1, 1), 80), ((255, 255), 2336), ((256, 256), 2336), ((257, 257), 2384), ((4095, 4095), 36896),
+        ((4096, 4096), 36896), ((4097, 4097), 36944), ((524287, 524287), 4719632), ((524288, 524288), 4719632),
+        ((524289, 524289), 4719696), ((4194303, 4194303), 37756944), ((4194304, 4194304), 37756944), ((4194305, 4194305), 37752912),
+        ((255, 7), 2336), ((256, 7), 2336), ((257, 7), 2384), ((4095, 7), 36896), ((4096, 7), 36896), ((4097, 7), 36944),
+        ((524287, 7), 4719632), ((524288, 7), 4719632), ((524289, 7), 4719696), ((4194303, 7), 37756944), ((4194304, 7), 37756944),
+        ((4194305, 7), 37752912), ((7, 255), 112), ((7, 256), 112), ((7, 257), 112), ((7, 4095), 112), ((7, 4096), 112),
+        ((7, 4097), 112), ((7, 524287), 112), ((7, 524288), 112), ((7, 524289), 112), ((7, 4194303), 112), ((7, 4194304), 112),
+        ((7, 4194305), 112), ((547600, 1092242), 4929488), ((-1, 0), -1), ((0, 2147483648), -1),
+    ],
+    "mf_mesh_filter_scratch_bytes": [
+        ((0, 0), 16), ((1, 1), 96), ((255, 255), 1824), ((256, 256), 1824), ((257, 257), 1888), ((4095, 4095), 28704),
+        ((4096, 4096), 28704), ((4097, 4097), 28768), ((524287, 524287), 3671056), ((524288, 524288), 3671056),
+        ((524289, 524289), 3671136), ((4194303, 4194303), 29368336), ((4194304, 4194304), 29368336), ((4194305, 4194305), 29364320),
+        ((255, 7), 1584), ((256, 7), 1584), ((257, 7), 1632), ((4095, 7), 24624), ((4096, 7), 24624), ((4097, 7), 24672),
+        ((524287, 7), 3146784), ((524288, 7), 3146784), ((524289, 7), 3146848), ((4194303, 7), 25174048), ((4194304, 7), 25174048),
+        ((4194305, 7), 25170016), ((7, 255), 352), ((7, 256), 352), ((7, 257), 368), ((7, 4095), 4192), ((7, 4096), 4192),
+        ((7, 4097), 4208), ((7, 524287), 525392), ((7, 524288), 525392), ((7, 524289), 525424), ((7, 4194303), 4202576),
+        ((7, 4194304), 4202576), ((7, 4194305), 4198512), ((547600, 1092242), 4380016), ((-1, 0), -1), ((0, 2147483648), -1),
+    ],
+    "mf_rings_mesh_scratch_bytes": [
+        ((0, 0), 16416), ((1, 1), 16496), ((255, 255), 25792), ((256, 256), 25824), ((257, 257), 25888), ((4095, 4095), 166832),
+        ((4096, 4096), 166864), ((4097, 4097), 166928), ((524287, 524287), 19272064), ((524288, 524288), 19272096),
+        ((524289, 524289), 19272160), ((4194303, 4194303), 154061744), ((4194304, 4194304), 154061776),
+        ((4194305, 4194305), 154061840), ((255, 7), 19664), ((256, 7), 19680), ((257, 7), 19712), ((4095, 7), 65744),
+        ((4096, 7), 65760), ((4097, 7), 65792), ((524287, 7), 6308048), ((524288, 7), 6308064), ((524289, 7), 6308096),
+        ((4194303, 7), 50348240), ((4194304, 7), 50348256), ((4194305, 7), 50348288), ((7, 255), 22656), ((7, 256), 22672),
+        ((7, 257), 22704), ((7, 4095), 114816), ((7, 4096), 114832), ((7, 4097), 114864), ((7, 524287), 12599424),
+        ((7, 524288), 12599440), ((7, 524289), 12599472), ((7, 4194303), 100679808), ((7, 4194304), 100679824),
+        ((7, 4194305), 100679856), ((547600, 1092242), 33595792), ((-1, 0), -1), ((0, 2147483648), -1),
+        ((5, 357913941), 8589951120), ((5, 357913942), -1),
+    ],
+    "mf_smooth_mesh_scratch_bytes": [
+        ((0, 0), 16), ((1, 1), 64), ((255, 255), 10208), ((256, 256), 10256), ((257, 257), 10304), ((4095, 4095), 163808),
+        ((4096, 4096), 163856), ((4097, 4097), 163904), ((524287, 524287), 20971488), ((524288, 524288), 20971536),
+        ((524289, 524289), 20971584), ((4194303, 4194303), 167772128), ((4194304, 4194304), 167772176),
+        ((4194305, 4194305), 167772224), ((255, 7), 9216), ((256, 7), 9264), ((257, 7), 9296), ((4095, 7), 147456),
+        ((4096, 7), 147504), ((4097, 7), 147536), ((524287, 7), 18874368), ((524288, 7), 18874416), ((524289, 7), 18874448),
+        ((4194303, 7), 150994944), ((4194304, 7), 150994992), ((4194305, 7), 150995024), ((7, 255), 1280), ((7, 256), 1280),
+        ((7, 257), 1296), ((7, 4095), 16640), ((7, 4096), 16640), ((7, 4097), 16656), ((7, 524287), 2097408),
+        ((7, 524288), 2097408), ((7, 524289), 2097424), ((7, 4194303), 16777472), ((7, 4194304), 16777472),
+        ((7, 4194305), 16777488), ((547600, 1092242), 24082592), ((-1, 0), -1), ((0, 2147483648), -1),
+    ],
+    "mf_simplify_mesh_scratch_bytes": [
+        ((0, 0, 1, 32, 1, 1), 32816), ((1, 1, 1, 32, 1, 2), 32848), ((255, 255, 255, 32, 1, 256), 37120),
+        ((256, 256, 256, 32, 1, 512), 38144), ((257, 257, 257, 32, 1, 512), 38208), ((4095, 4095, 4095, 32, 1, 4096), 102400),
+        ((4096, 4096, 4096, 32, 1, 8192), 118784), ((4097, 4097, 4097, 32, 1, 8192), 118848),
+        ((524287, 524287, 524287, 32, 1, 524288), 8945664), ((524288, 524288, 524288, 32, 1, 1048576), 11042816),
+        ((524289, 524289, 524289, 32, 1, 1048576), 11042880), ((4194303, 4194303, 4194303, 32, 1, 4194304), 71335936),
+        ((4194304, 4194304, 4194304, 32, 1, 8388608), 88113152), ((4194305, 4194305, 4194305, 32, 1, 8388608), 88113216),
+        ((255, 7, 3, 5, 7, 8), 33872), ((256, 7, 3, 5, 7, 8), 33872), ((257, 7, 3, 5, 7, 8), 33888), ((4095, 7, 3, 5, 7, 8), 49232),
+        ((4096, 7, 3, 5, 7, 8), 49232), ((4097, 7, 3, 5, 7, 8), 49248), ((524287, 7, 3, 5, 7, 8), 2130000),
+        ((524288, 7, 3, 5, 7, 8), 2130000), ((524289, 7, 3, 5, 7, 8), 2130016), ((4194303, 7, 3, 5, 7, 8), 16810064),
+        ((4194304, 7, 3, 5, 7, 8), 16810064), ((4194305, 7, 3, 5, 7, 8), 16810080), ((7, 255, 1, 1, 1, 256), 34112),
+        ((7, 256, 1, 1, 1, 512), 35136), ((7, 257, 1, 1, 1, 512), 35152), ((7, 4095, 1, 1, 1, 4096), 53312),
+        ((7, 4096, 1, 1, 1, 8192), 69696), ((7, 4097, 1, 1, 1, 8192), 69712), ((7, 524287, 1, 1, 1, 524288), 2654272),
+        ((7, 524288, 1, 1, 1, 1048576), 4751424), ((7, 524289, 1, 1, 1, 1048576), 4751440),
+        ((7, 4194303, 1, 1, 1, 4194304), 21004352), ((7, 4194304, 1, 1, 1, 8388608), 37781568),
+        ((7, 4194305, 1, 1, 1, 8388608), 37781584), ((547600, 1092242, 64, 64, 64, 2097152), 11769568), ((9, 9, 3, 3, 3, 8), -1),
+        ((9, 9, 0, 3, 3, 16), -1),
+    ],
+    "mf_mask_label_scratch_bytes": [
+        ((1, 1, 0), 16400), ((1, 1, 1), 16432), ((1, 1, 255), 18448), ((1, 1, 256), 18448), ((1, 1, 257), 18480),
+        ((1, 1, 4095), 49168), ((1, 1, 4096), 49168), ((1, 1, 4097), 49200), ((1, 1, 524287), 4210704), ((1, 1, 524288), 4210704),
+        ((1, 1, 524289), 4210736), ((1, 1, 4194303), 33570832), ((1, 1, 4194304), 33570832), ((1, 1, 4194305), 33570864),
+        ((1, 255, 1), 18448), ((1, 256, 1), 18448), ((1, 257, 1), 18480), ((1, 4095, 1), 49168), ((1, 4096, 1), 49168),
+        ((1, 4097, 1), 49200), ((1, 524287, 1), 4210704), ((1, 524288, 1), 4210704), ((1, 524289, 1), 4210736),
+        ((1, 4194303, 1), 33570832), ((1, 4194304, 1), 33570832), ((1, 4194305, 1), 33570864), ((0, 5, 5), 16384),
+        ((2, 17, 33), 25392), ((3, 540, 960), 12458016), ((7, 1, 1), 16512), ((-1, 1, 1), -1), ((2, 65536, 32768), -1),
+    ],
+    "mf_mask_compact_scratch_bytes": [
+        ((0,), 0), ((1,), 8), ((255,), 8), ((256,), 8), ((257,), 8), ((4095,), 8), ((4096,), 8), ((4097,), 16), ((524287,), 1024),
+        ((524288,), 1024), ((524289,), 1032), ((4194303,), 8192), ((4194304,), 8192), ((4194305,), 4104), ((-1,), -1),
+        ((8589934592,), 8192),
+    ],
+    "mf_mc_scratch_bytes": [
+        ((2, 2, 2), 56), ((3, 3, 3), 132), ((2, 2, 255), 4104), ((2, 2, 256), 4120), ((2, 2, 257), 4160), ((2, 2, 513), 8280),
+        ((33, 35, 37), 171948), ((128, 128, 128), 8437760), ((2, 2, 131071), 2109424), ((2, 2, 131072), 2109440),
+        ((2, 2, 131073), 2109480), ((512, 512, 512), 540016640), ((1, 2, 2), -1), ((2048, 2048, 512), -1),
+    ],
+    "mf_voxel_fill_scratch_bytes": [
+        ((1, 1, 1), 16), ((1, 1, 32), 144), ((1, 1, 33), 144), ((3, 5, 7), 432), ((128, 128, 128), 8388624), ((0, 1, 1), -1),
+        ((2048, 2048, 512), -1), ((1, 1, 1), 16), ((255, 1, 1), 1024), ((256, 1, 1), 1040), ((257, 1, 1), 1040),
+        ((4095, 1, 1), 16384), ((4096, 1, 1), 16400), ((4097, 1, 1), 16400), ((524287, 1, 1), 2097152), ((524288, 1, 1), 2097168),
+        ((524289, 1, 1), 2097168), ((4194303, 1, 1), 16777216), ((4194304, 1, 1), 16777232), ((4194305, 1, 1), 16777232),
+        ((1, 255, 33), 33664), ((1, 256, 33), 33808), ((1, 257, 33), 33936), ((1, 4095, 33), 540544), ((1, 4096, 33), 540688),
+        ((1, 4097, 33), 540816), ((1, 524287, 33), 69205888), ((1, 524288, 33), 69206032), ((1, 524289, 33), 69206160),
+        ((1, 4194303, 33), 553648000), ((1, 4194304, 33), 553648144), ((1, 4194305, 33), 553648272),
+    ],
+    "mf_voxel_dilate_scratch_bytes": [
+        ((1, 1, 1), 40), ((1, 1, 32), 40), ((1, 1, 33), 40), ((3, 5, 7), 136), ((128, 128, 128), 526336), ((0, 1, 1), -1),
+        ((2048, 2048, 512), -1), ((1, 1, 1), 40), ((255, 1, 1), 2056), ((256, 1, 1), 2056), ((257, 1, 1), 2096),
+        ((4095, 1, 1), 32896), ((4096, 1, 1), 32896), ((4097, 1, 1), 32936), ((524287, 1, 1), 4210688), ((524288, 1, 1), 4210688),
+        ((524289, 1, 1), 4210728), ((4194303, 1, 1), 33685504), ((4194304, 1, 1), 33685504), ((4194305, 1, 1), 33685544),
+        ((1, 255, 33), 4112), ((1, 256, 33), 4112), ((1, 257, 33), 4152), ((1, 4095, 33), 65792), ((1, 4096, 33), 65792),
+        ((1, 4097, 33), 65832), ((1, 524287, 33), 8421376), ((1, 524288, 33), 8421376), ((1, 524289, 33), 8421416),
+        ((1, 4194303, 33), 67371008), ((1, 4194304, 33), 67371008), ((1, 4194305, 33), 67371048),
+    ],
+}
+
+
+def test_scratch_sizes_are_the_recorded_ones():
+    import moco_flow_amd._lib as L
+    lib = L.lib()
+    for name, rows in SCRATCH_BYTES.items():
+        fn = getattr(lib, name)
+        for args, want in rows:
+            assert fn(*args) == want, (name, args, fn(*args), want)
+
+
+def test_shares_header_under_the_sanitizers(tmp_path):
+    """csrc/mf_shares.hpp alone, in a program of its own (tests/shares_check.cpp): the size query carves from a null base, which
+    must be free of undefined behaviour, a real buffer gives base + offset, and share_of keeps its invariants at the edges."""
+    import subprocess
+    cxx = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        pytest.skip("ROCm's clang++ not available")
+    exe = str(tmp_path / "shares_check")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-I", os.path.join(ROOT, "moco_flow_amd", "csrc"), os.path.join(ROOT, "tests", "shares_check.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and "shares ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
