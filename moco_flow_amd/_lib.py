@@ -329,6 +329,48 @@ def current_stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def ptr0(t):
+    """Device pointer of a tensor, NULL for None and for an empty one (the ABI takes NULL for a zero count)."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def call(name: str, *args):
+    """A host-only entry point: no stream, no device; the status checked under the symbol's name."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def enqueue(device, name: str, *args):
+    """A launching entry point on ``device``'s current stream -- the last argument of every one of them -- the status
+    checked under the symbol's name.  Enters no device context: for use inside a ``with torch.cuda.device(device):``
+    block that covers several launches or a host read."""
+    check(getattr(lib(), name)(*args, current_stream(device)), name)
+
+
+def launch(device, name: str, *args):
+    """``enqueue`` inside a device context of its own: the single-launch case."""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args, current_stream(device)), name)
+
+
+def need(name: str, *dims) -> int:
+    """A ``*_scratch_bytes`` / ``*_workspace_bytes`` query.  A refusal (a negative size) raises with the library's own
+    message and code, before anything is allocated."""
+    n = int(getattr(lib(), name)(*dims))
+    if n < 0:
+        check(n, name)
+    return n
+
+
+SCRATCH_FLOOR = 16   # a zero-byte torch.empty has a null data_ptr(); 16 is the alignment the library's carvers assume
+
+
+def scratch(device, name: str, *dims):
+    """The uint8 scratch tensor a size query asks for, never below SCRATCH_FLOOR bytes."""
+    import torch
+    return torch.empty(max(need(name, *dims), SCRATCH_FLOOR), dtype=torch.uint8, device=device)
+
+
 def require_gpu(t, what: str):
     if not t.is_cuda:
         raise RuntimeError(

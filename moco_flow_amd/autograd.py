@@ -67,10 +67,8 @@ def nof_backward_hip(m, emb_desc, P, pts, acts, stride, g_out, gpre, g_pts):
     x3 = (DX_PRECISION == "bf16x3" and stride % 4 == 0 and acts.data_ptr() % 16 == 0 and gpre.data_ptr() % 16 == 0
           and m.in_channels_xyz + m.extra_feat_dim >= 64)
     desc, buf = m.packed_bwd3() if x3 else m.packed_bwd()
-    fn, what = (L.lib().mf_nof_backward3, "mf_nof_backward3") if x3 else (L.lib().mf_nof_backward, "mf_nof_backward")
-    with torch.cuda.device(dev):
-        L.check(fn(C.byref(desc), buf.data_ptr(), C.byref(emb_desc), P, pts.data_ptr(), acts.data_ptr(), stride,
-                   g_out.data_ptr(), gpre.data_ptr(), L.ptr(g_pts), L.current_stream(dev)), what)
+    L.launch(dev, "mf_nof_backward3" if x3 else "mf_nof_backward", C.byref(desc), buf.data_ptr(), C.byref(emb_desc), P,
+             pts.data_ptr(), acts.data_ptr(), stride, g_out.data_ptr(), gpre.data_ptr(), L.ptr(g_pts))
 
 
 def nerf_backward_hip(m, g_out, acts, rgbsig, want_emb=False):
@@ -87,18 +85,14 @@ def nerf_backward_hip(m, g_out, acts, rgbsig, want_emb=False):
         mask = getattr(acts, "_mf_mask", None)          # the forward's ReLU bit-mask rows, when it wrote them (rendering.py)
         if mask is not None and (mask.shape[0] != P or mask.shape[1] < (m.D + 2) * 8):
             mask = None
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_nerf_backward3(C.byref(desc), buf.data_ptr(), P, g_out.data_ptr(), acts.data_ptr(), stride,
-                                              rgbsig.data_ptr(), gpre.data_ptr(), ghead.data_ptr(), L.ptr(g_emb),
-                                              L.ptr(mask), mask.shape[1] if mask is not None else 0,
-                                              L.current_stream(dev)), "mf_nerf_backward3")
+        L.launch(dev, "mf_nerf_backward3", C.byref(desc), buf.data_ptr(), P, g_out.data_ptr(), acts.data_ptr(), stride,
+                 rgbsig.data_ptr(), gpre.data_ptr(), ghead.data_ptr(), L.ptr(g_emb), L.ptr(mask),
+                 mask.shape[1] if mask is not None else 0)
         return gpre[:P], ghead, g_emb
     desc, buf = m.packed_bwd()
     g_emb = torch.empty((P, 64), device=dev, dtype=torch.float32) if want_emb else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_nerf_backward_x(C.byref(desc), buf.data_ptr(), P, g_out.data_ptr(), acts.data_ptr(), stride,
-                                           rgbsig.data_ptr(), gpre.data_ptr(), ghead.data_ptr(), L.ptr(g_emb),
-                                           L.current_stream(dev)), "mf_nerf_backward")
+    L.launch(dev, "mf_nerf_backward_x", C.byref(desc), buf.data_ptr(), P, g_out.data_ptr(), acts.data_ptr(), stride,
+             rgbsig.data_ptr(), gpre.data_ptr(), ghead.data_ptr(), L.ptr(g_emb))
     return gpre[:P], ghead, g_emb
 
 
@@ -108,10 +102,8 @@ def embed_backward_hip(emb, emb_vals, g_emb):
     P, dev = g_emb.shape[0], g_emb.device
     desc = emb.descriptor()
     g_x = torch.empty((P, emb.in_channels), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_embedding_backward(C.byref(desc), g_emb.data_ptr(), g_emb.stride(0), emb_vals.data_ptr(),
-                                              emb_vals.stride(0), P, g_x.data_ptr(), L.current_stream(dev)),
-                "mf_embedding_backward")
+    L.launch(dev, "mf_embedding_backward", C.byref(desc), g_emb.data_ptr(), g_emb.stride(0), emb_vals.data_ptr(),
+             emb_vals.stride(0), P, g_x.data_ptr())
     return g_x
 
 
@@ -124,9 +116,7 @@ class EmbeddingModule(torch.autograd.Function):
         xc = x.detach().contiguous().float()
         out = torch.empty((xc.shape[0], emb.out_channels), device=xc.device, dtype=torch.float32)
         d = emb.descriptor()
-        with torch.cuda.device(xc.device):
-            L.check(L.lib().mf_embedding_forward(d, L.ptr(xc), xc.shape[0], L.ptr(out), L.current_stream(xc.device)),
-                    "mf_embedding_forward")
+        L.launch(xc.device, "mf_embedding_forward", d, L.ptr(xc), xc.shape[0], L.ptr(out))
         ctx.emb = emb
         ctx.save_for_backward(out)
         return out.clone()
@@ -193,14 +183,12 @@ def weight_grads(jobs, P, dev):
         it.X, it.x_stride, it.n_in = X.data_ptr(), X.stride(0), n_in
         it.dW, it.db = dW.data_ptr(), (db.data_ptr() if bias else None)
         outs.append((dW, db))
-    lib = L.lib()
     prec = L.PRECISIONS[WGRAD_PRECISION]
-    nbytes = lib.mf_weight_grads_scratch_bytes_p(prec, items, n, P)
-    if nbytes < 0:
-        L.check(-3, "mf_weight_grads")
-    scratch = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_weight_grads_p(prec, items, n, P, scratch.data_ptr(), L.current_stream(dev)), "mf_weight_grads")
+    # (L.scratch, spelled out: this module allocates the partials itself, where tests/test_gpu_parity.py puts every
+    #  allocation of this function between sentinel bands)
+    scratch = torch.empty(max(L.need("mf_weight_grads_scratch_bytes_p", prec, items, n, P), L.SCRATCH_FLOOR), dtype=torch.uint8,
+                          device=dev)
+    L.launch(dev, "mf_weight_grads_p", prec, items, n, P, scratch.data_ptr())
     return outs
 
 
@@ -221,7 +209,7 @@ def _nof_slot_columns(dev):
     key = str(dev)
     if key not in _SLOT_COLS:
         feats = (C.c_int32 * 80)()
-        L.check(L.lib().mf_nof_emb_slot_features(feats), "mf_nof_emb_slot_features")
+        L.call("mf_nof_emb_slot_features", feats)
         where = [0] * 66
         for c, f in enumerate(feats):
             if f >= 0:
@@ -291,10 +279,8 @@ class NofModule(torch.autograd.Function):
         pts = xyz.detach().float().contiguous()
         out = torch.empty((B, 3), device=dev, dtype=torch.float32)
         acts = torch.empty((B, stride), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_nof_forward_dump(C.byref(desc), buf.data_ptr(), x.data_ptr(), x.stride(0), pts.data_ptr(), B,
-                                                out.data_ptr(), acts.data_ptr(), stride, L.current_stream(dev)),
-                    "mf_nof_forward_dump")
+        L.launch(dev, "mf_nof_forward_dump", C.byref(desc), buf.data_ptr(), x.data_ptr(), x.stride(0), pts.data_ptr(), B,
+                 out.data_ptr(), acts.data_ptr(), stride)
         ctx.m, ctx.stride = m, stride
         ctx.save_for_backward(x, pts, acts)
         return out
@@ -333,11 +319,8 @@ class NofPoints(torch.autograd.Function):
         acts = torch.empty((P, stride), device=dev, dtype=torch.float32)
         emb = torch.empty((P, 80), device=dev, dtype=torch.float32)
         ex, ei = nof_embs[0].descriptor(), nof_embs[1].descriptor()
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_nof_points_dump(C.byref(desc), buf.data_ptr(), C.byref(ex), C.byref(ei), pts.data_ptr(),
-                                               ray_ind.data_ptr(), ray_ind.stride(0), S, P, out.data_ptr(),
-                                               acts.data_ptr(), stride, emb.data_ptr(), L.current_stream(dev)),
-                    "mf_nof_points_dump")
+        L.launch(dev, "mf_nof_points_dump", C.byref(desc), buf.data_ptr(), C.byref(ex), C.byref(ei), pts.data_ptr(),
+                 ray_ind.data_ptr(), ray_ind.stride(0), S, P, out.data_ptr(), acts.data_ptr(), stride, emb.data_ptr())
         ctx.m, ctx.ex, ctx.stride = m, ex, stride
         ctx.save_for_backward(pts, acts, emb)
         return out
@@ -581,9 +564,7 @@ class NerfModule(torch.autograd.Function):
         acts = torch.empty((B, stride), device=dev, dtype=torch.float32)
         out = torch.empty((B, 4), device=dev, dtype=torch.float32)
         desc, buf = m.packed()
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_nerf_forward_dump(desc, buf.data_ptr(), L.ptr(x), x.stride(0), B, L.ptr(out), L.ptr(acts),
-                                                 stride, L.current_stream(dev)), "mf_nerf_forward_dump")
+        L.launch(dev, "mf_nerf_forward_dump", desc, buf.data_ptr(), L.ptr(x), x.stride(0), B, L.ptr(out), L.ptr(acts), stride)
         ctx.m, ctx.sigma_only, ctx.in_grad, ctx.in_width = m, bool(sigma_only), inputs.requires_grad, inputs.shape[1]
         ctx.save_for_backward(acts, out, x)
         return out[:, 3:4].clone() if sigma_only else out.clone()
@@ -714,10 +695,8 @@ class LossPartials(torch.autograd.Function):
             grads += [g_rgb, g_rl, g_rg]
         while len(grads) < len(ctx.shapes):
             grads.append(None)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_loss_partials_backward(C.byref(descs[0]), C.byref(descs[1]) if len(descs) > 1 else None,
-                                                      L.ptr(target), N, out12.data_ptr(), g12.data_ptr(),
-                                                      L.current_stream(dev)), "mf_loss_partials_backward")
+        L.launch(dev, "mf_loss_partials_backward", C.byref(descs[0]), C.byref(descs[1]) if len(descs) > 1 else None,
+                 L.ptr(target), N, out12.data_ptr(), g12.data_ptr())
         return (None, None, None, None) + tuple(grads)
 
 
@@ -755,9 +734,7 @@ class ConsensusMean(torch.autograd.Function):
             d.recon_local, d.g_recon_local = L.ptr(recon), L.ptr(g_recon)
         else:
             d.recon_global, d.g_recon_global = L.ptr(recon), L.ptr(g_recon)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_loss_partials_backward(C.byref(d), None, None, N, out12.data_ptr(), g12.data_ptr(),
-                                                      L.current_stream(dev)), "mf_loss_partials_backward")
+        L.launch(dev, "mf_loss_partials_backward", C.byref(d), None, None, N, out12.data_ptr(), g12.data_ptr())
         return None, None, None, None, None, g_recon
 
 
@@ -797,11 +774,7 @@ class CompositeSamples(torch.autograd.Function):
         noise = noise.contiguous() if ctx.has_noise else None
         background = background.contiguous() if ctx.has_bg else None
         g = torch.empty((N * S, 4), device=dev, dtype=torch.float32)
-        ptr = lambda t: None if t is None else t.data_ptr()
         act = L.MF_ACT_RELU if ctx.activation == "relu" else L.MF_ACT_SOFTPLUS
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_composite_backward(rays.data_ptr(), rays.stride(0), N, S, z_vals.data_ptr(),
-                                                  rgbsig.data_ptr(), ptr(noise), act, ptr(background), ptr(g_rgb),
-                                                  ptr(g_depth), ptr(g_opacity), g.data_ptr(), L.current_stream(dev)),
-                    "mf_composite_backward")
+        L.launch(dev, "mf_composite_backward", rays.data_ptr(), rays.stride(0), N, S, z_vals.data_ptr(), rgbsig.data_ptr(),
+                 L.ptr(noise), act, L.ptr(background), L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_opacity), g.data_ptr())
         return g, None, None, None, None, None, None, None, None

@@ -110,17 +110,14 @@ class FrameRays:
         if n == 0:
             self.val_inds, self.n_valid = torch.empty(0, dtype=torch.int64, device=dev), 0
             return
-        lib = L.lib()
         mask = None
         if rays_msk is not None:
             mask = rays_msk.to(dev).contiguous()
             mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
         inds = torch.empty(n, dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(max(int(lib.mf_mask_compact_scratch_bytes(n)), 8), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_mask_compact(L.ptr(mask), n, inds.data_ptr(), count.data_ptr(), scratch.data_ptr(),
-                                        L.current_stream(dev)), "mf_mask_compact")
+        scratch = L.scratch(dev, "mf_mask_compact_scratch_bytes", n)
+        L.launch(dev, "mf_mask_compact", L.ptr(mask), n, inds.data_ptr(), count.data_ptr(), scratch.data_ptr())
         self.n_valid = int(count.item())                    # the one device -> host read of a frame
         self.val_inds = inds if self.n_valid == n else inds[:self.n_valid].clone()     # keep 8 n_valid bytes, not 8 H W
 
@@ -173,6 +170,5 @@ class FrameRays:
         a.image, a.image_kind = L.ptr(image), image_kind
         a.background, a.background_kind = L.ptr(background), background_kind
         a.rays_out, a.rgbs_out, a.background_out, a.sel_out = rays.data_ptr(), L.ptr(rgbs), L.ptr(bkgd), sel.data_ptr()
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_ray_batch(C.byref(a), L.current_stream(dev)), "mf_ray_batch")
+        L.launch(dev, "mf_ray_batch", C.byref(a))
         return rays, rgbs, bkgd, sel

@@ -82,11 +82,8 @@ def make_rays(H, W, focal, center, c2w, near, far, idx, device="cuda"):
     if c2w is not None:
         m = np.asarray(c2w, dtype=np.float64)[:3, :4].astype(np.float32)      # camera.py:141 .float()
         mat = (C.c_float * 12)(*m.reshape(-1).tolist())
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_make_rays(H, W, float(np.float32(focal)), float(np.float32(center[0])),
-                                     float(np.float32(center[1])), mat, float(np.float32(near)),
-                                     float(np.float32(far)), float(np.float32(idx)), out.data_ptr(),
-                                     L.current_stream(dev)), "mf_make_rays")
+    L.launch(dev, "mf_make_rays", H, W, float(np.float32(focal)), float(np.float32(center[0])), float(np.float32(center[1])), mat,
+             float(np.float32(near)), float(np.float32(far)), float(np.float32(idx)), out.data_ptr())
     return out
 
 
@@ -119,7 +116,5 @@ def valid_rays_mask(aabb_verts, c2w, K, size, device="cuda"):
     pix = np.ascontiguousarray(project_aabb(aabb_verts, c2w, K).reshape(-1, 2), dtype=np.int32)
     out = torch.empty(H * W, device=dev, dtype=torch.uint8)
     arr = (C.c_int32 * pix.size)(*pix.reshape(-1).tolist())
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_valid_rays_mask(H, W, arr, pix.shape[0], out.data_ptr(), L.current_stream(dev)),
-                "mf_valid_rays_mask")
+    L.launch(dev, "mf_valid_rays_mask", H, W, arr, pix.shape[0], out.data_ptr())
     return out.bool()

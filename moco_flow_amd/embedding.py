@@ -61,9 +61,7 @@ class Embedding(nn.Module):
         xc = x.detach().contiguous().float()
         B = x.shape[0] * repeat
         out = torch.empty((B, width), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            L.check(L.lib().mf_embedding_forward_rows(self.descriptor(), L.ptr(xc), B, repeat, L.ptr(out), width,
-                                                      L.current_stream(x.device)), "mf_embedding_forward_rows")
+        L.launch(x.device, "mf_embedding_forward_rows", self.descriptor(), L.ptr(xc), B, repeat, L.ptr(out), width)
         return out
 
     def forward(self, x):
@@ -76,7 +74,5 @@ class Embedding(nn.Module):
         xc = x.detach().contiguous().float()
         out = torch.empty((x.shape[0], self.out_channels), device=x.device, dtype=torch.float32)
         d = self.descriptor()
-        with torch.cuda.device(x.device):
-            L.check(L.lib().mf_embedding_forward(d, L.ptr(xc), x.shape[0], L.ptr(out),
-                                                 L.current_stream(x.device)), "mf_embedding_forward")
+        L.launch(x.device, "mf_embedding_forward", d, L.ptr(xc), x.shape[0], L.ptr(out))
         return out

@@ -105,16 +105,13 @@ def resize(images, size):
     stack = stack.contiguous()
     xb, xk, xks = _device_tables(W0, W, dev) if W != W0 else (None, None, 0)
     yb, yk, yks = _device_tables(H0, H, dev) if H != H0 else (None, None, 0)
-    lib = L.lib()
     chunk = max(1, min(F, (_INDEX_LIMIT - 1) // per_frame))
-    scratch = None
-    if W != W0 and H != H0:
-        scratch = torch.empty(int(lib.mf_resize_u8_scratch_bytes(chunk, H0, W0, C, H, W)), dtype=torch.uint8, device=dev)
+    scratch = L.scratch(dev, "mf_resize_u8_scratch_bytes", chunk, H0, W0, C, H, W) if W != W0 and H != H0 else None
     with torch.cuda.device(dev):
         for f0 in range(0, F, chunk):
             n = min(chunk, F - f0)
-            L.check(lib.mf_resize_u8(stack[f0].data_ptr(), n, H0, W0, C, H, W, L.ptr(xb), L.ptr(xk), xks, L.ptr(yb), L.ptr(yk), yks,
-                                     out[f0].data_ptr(), L.ptr(scratch), L.current_stream(dev)), "mf_resize_u8")
+            L.enqueue(dev, "mf_resize_u8", stack[f0].data_ptr(), n, H0, W0, C, H, W, L.ptr(xb), L.ptr(xk), xks, L.ptr(yb), L.ptr(yk),
+                      yks, out[f0].data_ptr(), L.ptr(scratch))
     return out if images.dim() == 4 else out[0]
 
 
@@ -162,9 +159,8 @@ def composite(image, background=None):
         return rows
     image = image.contiguous()
     background = None if background is None else background.contiguous()
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_composite_rows(image.data_ptr(), L.MF_IMAGE_U8_RGBA if C == 4 else L.MF_IMAGE_U8_RGB, H, W,
-                                          L.ptr(background), kind, rows.data_ptr(), L.current_stream(dev)), "mf_composite_rows")
+    L.launch(dev, "mf_composite_rows", image.data_ptr(), L.MF_IMAGE_U8_RGBA if C == 4 else L.MF_IMAGE_U8_RGB, H, W,
+             L.ptr(background), kind, rows.data_ptr())
     return rows
 
 
@@ -217,9 +213,7 @@ def background_plate(frames, masks, q=0.8, path="auto"):
     if H * W == 0:
         return out
     frames, masks = frames.contiguous(), masks.contiguous()
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_background_plate(frames.data_ptr(), masks.data_ptr(), F, H, W, C, k, _PLATE_PATHS[path], out.data_ptr(),
-                                            L.current_stream(dev)), "mf_background_plate")
+    L.launch(dev, "mf_background_plate", frames.data_ptr(), masks.data_ptr(), F, H, W, C, k, _PLATE_PATHS[path], out.data_ptr())
     return out
 
 
@@ -283,20 +277,18 @@ def clean_mask(alpha, thres=196, largest=True, min_area=0, fill_holes=False):
     dev = stack.device
     out = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
     if out.numel() > 0:
-        lib = L.lib()
         chunk = _region_chunk(F, H, W)
-        scratch = torch.empty(int(lib.mf_mask_label_scratch_bytes(chunk, H, W)), dtype=torch.uint8, device=dev)
+        scratch = L.scratch(dev, "mf_mask_label_scratch_bytes", chunk, H, W)
         labels = torch.empty((chunk, H, W), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            stream = L.current_stream(dev)
             for f0 in range(0, F, chunk):
                 n = min(chunk, F - f0)
-                L.check(lib.mf_mask_label(ptr + f0 * H * W * stride, stride, n, H, W, int(thres), 0, 8, labels.data_ptr(),
-                                          scratch.data_ptr(), stream), "mf_mask_label")
-                L.check(lib.mf_mask_select(labels.data_ptr(), n, H, W, int(bool(largest)), int(min_area), out[f0].data_ptr(),
-                                           scratch.data_ptr(), stream), "mf_mask_select")
+                L.enqueue(dev, "mf_mask_label", ptr + f0 * H * W * stride, stride, n, H, W, int(thres), 0, 8, labels.data_ptr(),
+                          scratch.data_ptr())
+                L.enqueue(dev, "mf_mask_select", labels.data_ptr(), n, H, W, int(bool(largest)), int(min_area), out[f0].data_ptr(),
+                          scratch.data_ptr())
                 if fill_holes:
-                    L.check(lib.mf_mask_fill_holes(out[f0].data_ptr(), n, H, W, scratch.data_ptr(), stream), "mf_mask_fill_holes")
+                    L.enqueue(dev, "mf_mask_fill_holes", out[f0].data_ptr(), n, H, W, scratch.data_ptr())
     return out[0] if single else out
 
 
@@ -313,16 +305,14 @@ def mask_regions(alpha, thres=196, connectivity=8, below=False):
     counts = torch.zeros((F,), dtype=torch.int64, device=dev)
     if labels.numel() == 0:
         return Regions(labels[0] if single else labels, counts, torch.empty((0, 7), dtype=torch.int32, device=dev))
-    lib = L.lib()
     chunk = _region_chunk(F, H, W)
-    scratch = torch.empty(int(lib.mf_mask_label_scratch_bytes(chunk, H, W)), dtype=torch.uint8, device=dev)
+    scratch = L.scratch(dev, "mf_mask_label_scratch_bytes", chunk, H, W)
     with torch.cuda.device(dev):
-        stream = L.current_stream(dev)
         for f0 in range(0, F, chunk):
             n = min(chunk, F - f0)
-            L.check(lib.mf_mask_label(ptr + f0 * H * W * stride, stride, n, H, W, int(thres), int(bool(below)), int(connectivity),
-                                      labels[f0].data_ptr(), scratch.data_ptr(), stream), "mf_mask_label")
-            L.check(lib.mf_mask_table_count(labels[f0].data_ptr(), n, H, W, counts[f0:].data_ptr(), stream), "mf_mask_table_count")
+            L.enqueue(dev, "mf_mask_label", ptr + f0 * H * W * stride, stride, n, H, W, int(thres), int(bool(below)),
+                      int(connectivity), labels[f0].data_ptr(), scratch.data_ptr())
+            L.enqueue(dev, "mf_mask_table_count", labels[f0].data_ptr(), n, H, W, counts[f0:].data_ptr())
         host = counts.cpu().numpy()                                       # the one host read
         table = torch.empty((int(host.sum()), 7), dtype=torch.int32, device=dev)
         row = 0
@@ -330,7 +320,6 @@ def mask_regions(alpha, thres=196, connectivity=8, below=False):
             n = min(chunk, F - f0)
             c = int(host[f0:f0 + n].sum())
             if c > 0:
-                L.check(lib.mf_mask_table_emit(labels[f0].data_ptr(), n, H, W, f0, c, table[row:].data_ptr(), scratch.data_ptr(), stream),
-                        "mf_mask_table_emit")
+                L.enqueue(dev, "mf_mask_table_emit", labels[f0].data_ptr(), n, H, W, f0, c, table[row:].data_ptr(), scratch.data_ptr())
             row += c
     return Regions(labels[0] if single else labels, counts, table)

@@ -26,11 +26,8 @@ def compose_image(rays_msk: Optional[torch.Tensor], opacity, rgb, depth, backgro
         rank = (torch.cumsum(m.to(torch.int64), 0) - 1).contiguous()
     f = lambda t: t.detach().contiguous().float()
     opacity, rgb, depth, bgc = f(opacity), f(rgb), f(depth), f(background)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_image_compose(msk8.data_ptr() if msk8 is not None else None,
-                                         rank.data_ptr() if rank is not None else None, B, opacity.data_ptr(),
-                                         rgb.data_ptr(), depth.data_ptr(), bgc.data_ptr(), img.data_ptr(),
-                                         dep.data_ptr(), L.current_stream(dev)), "mf_image_compose")
+    L.launch(dev, "mf_image_compose", L.ptr(msk8), L.ptr(rank), B, opacity.data_ptr(), rgb.data_ptr(), depth.data_ptr(),
+             bgc.data_ptr(), img.data_ptr(), dep.data_ptr())
     return img, dep
 
 

@@ -28,9 +28,7 @@ class KNN(nn.Module):
                 q = query[bi].float().contiguous()
                 d = torch.empty((q.shape[0], 1), device=q.device, dtype=torch.float32)
                 i = torch.empty((q.shape[0], 1), device=q.device, dtype=torch.int64)
-                with torch.cuda.device(q.device):
-                    L.check(L.lib().mf_knn1(L.ptr(r), r.shape[0], L.ptr(q), q.shape[0], L.ptr(d), L.ptr(i),
-                                            L.current_stream(q.device)), "mf_knn1")
+                L.launch(q.device, "mf_knn1", L.ptr(r), r.shape[0], L.ptr(q), q.shape[0], L.ptr(d), L.ptr(i))
                 D.append(d)
                 I.append(i)
             return torch.stack(D, dim=0), torch.stack(I, dim=0)

@@ -29,24 +29,17 @@ def marching_cubes(volume, isovalue, clamp_zero=False):
     if volume.dim() != 3:
         raise RuntimeError(f"marching_cubes: volume must be 3-D, got shape {tuple(volume.shape)}")
     n0, n1, n2 = volume.shape
-    lib = L.lib()
-    need = int(lib.mf_mc_scratch_bytes(n0, n1, n2))
-    if need < 0:                                     # bad shape: rejected before anything is allocated or copied
-        L.check(need, "mf_mc_scratch_bytes")
+    dev = volume.device
+    scratch = L.scratch(dev, "mf_mc_scratch_bytes", n0, n1, n2)     # a bad shape is rejected here, before anything is copied
     vol = volume.detach().float().contiguous()
-    dev = vol.device
-    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     iso, clamp = float(isovalue), 1 if clamp_zero else 0
     with torch.cuda.device(dev):
-        stream = L.current_stream(dev)
-        L.check(lib.mf_mc_count(vol.data_ptr(), n0, n1, n2, iso, clamp, scratch.data_ptr(), counts.data_ptr(), stream),
-                "mf_mc_count")
+        L.enqueue(dev, "mf_mc_count", vol.data_ptr(), n0, n1, n2, iso, clamp, scratch.data_ptr(), counts.data_ptr())
         V, T = (int(x) for x in counts.tolist())
         verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
         tris = torch.empty((T, 3), dtype=torch.int64, device=dev)
-        L.check(lib.mf_mc_emit(vol.data_ptr(), n0, n1, n2, iso, clamp, scratch.data_ptr(), L.ptr(verts) if V else None,
-                               L.ptr(tris) if T else None, stream), "mf_mc_emit")
+        L.enqueue(dev, "mf_mc_emit", vol.data_ptr(), n0, n1, n2, iso, clamp, scratch.data_ptr(), L.ptr0(verts), L.ptr0(tris))
     return verts, tris
 
 
@@ -62,18 +55,13 @@ def vertex_normals(volume, verts, clamp_zero=False):
     if verts.dim() != 2 or verts.shape[1] != 3:
         raise RuntimeError(f"vertex_normals: verts must be (V, 3), got shape {tuple(verts.shape)}")
     n0, n1, n2 = volume.shape
-    lib = L.lib()
-    need = int(lib.mf_mc_scratch_bytes(n0, n1, n2))
-    if need < 0:                                     # bad shape: rejected before anything is copied
-        L.check(need, "mf_mc_scratch_bytes")
+    L.need("mf_mc_scratch_bytes", n0, n1, n2)        # bad shape: rejected before anything is copied
     vol = volume.detach().float().contiguous()
     dev = vol.device
     v = verts.detach().float().contiguous().to(dev)
     V = v.shape[0]
     normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_mc_normals(vol.data_ptr(), n0, n1, n2, 1 if clamp_zero else 0, L.ptr(v) if V else None, V,
-                                  L.ptr(normals) if V else None, L.current_stream(dev)), "mf_mc_normals")
+    L.launch(dev, "mf_mc_normals", vol.data_ptr(), n0, n1, n2, 1 if clamp_zero else 0, L.ptr0(v), V, L.ptr0(normals))
     return normals
 
 
@@ -84,40 +72,28 @@ def _check_tris(tris, what):
         raise RuntimeError(f"{what}: tris must be int64, got {tris.dtype}")
 
 
-def _bytes(n, dev):
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
-
-
 def _label(tris, V, bad):
     """Launch the labelling of a checked, contiguous (T, 3) int64 device tensor: labels (V,); the bad-index counter goes to
     ``bad`` (device int64 storage).  No host read."""
-    lib, dev, T = L.lib(), tris.device, tris.shape[0]
-    need = int(lib.mf_mesh_label_scratch_bytes(V, T))
-    if need < 0:                                     # V or T beyond 32-bit indexing: rejected before anything is allocated
-        L.check(need, "mf_mesh_label_scratch_bytes")
+    dev, T = tris.device, tris.shape[0]
+    scratch = L.scratch(dev, "mf_mesh_label_scratch_bytes", V, T)    # V or T beyond 32-bit indexing: rejected here
     labels = torch.empty(V, dtype=torch.int64, device=dev)
-    scratch = _bytes(need, dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_mesh_label(L.ptr(tris) if T else None, T, V, L.ptr(labels) if V else None, bad.data_ptr(),
-                                  scratch.data_ptr(), L.current_stream(dev)), "mf_mesh_label")
+    L.launch(dev, "mf_mesh_label", L.ptr0(tris), T, V, L.ptr0(labels), bad.data_ptr(), scratch.data_ptr())
     return labels
 
 
 def _table(tris, V, labels, counts, what):
     """The component table of labelled triangles: (ids, tri_counts, vert_counts).  ``counts``: device int64[3] whose entry
     0 a labelling on the same stream has filled; one device -> host read ([bad, C, bad])."""
-    lib, dev, T = L.lib(), tris.device, tris.shape[0]
-    scratch = _bytes(lib.mf_mesh_table_scratch_bytes(V, T), dev)
+    dev, T = tris.device, tris.shape[0]
+    scratch = L.scratch(dev, "mf_mesh_table_scratch_bytes", V, T)
     with torch.cuda.device(dev):
-        stream = L.current_stream(dev)
-        L.check(lib.mf_mesh_table_count(L.ptr(tris) if T else None, T, V, L.ptr(labels) if V else None, counts.data_ptr() + 8,
-                                        scratch.data_ptr(), stream), "mf_mesh_table_count")
+        L.enqueue(dev, "mf_mesh_table_count", L.ptr0(tris), T, V, L.ptr0(labels), counts.data_ptr() + 8, scratch.data_ptr())
         bad, C, bad2 = (int(x) for x in counts.tolist())
         if bad or bad2:
             raise RuntimeError(f"{what}: {max(bad, bad2)} triangles name a vertex outside [0, {V})")
         ids, tri_counts, vert_counts = (torch.empty(C, dtype=torch.int64, device=dev) for _ in range(3))
-        L.check(lib.mf_mesh_table_emit(V, C, scratch.data_ptr(), L.ptr(ids) if C else None, L.ptr(tri_counts) if C else None,
-                                       L.ptr(vert_counts) if C else None, stream), "mf_mesh_table_emit")
+        L.enqueue(dev, "mf_mesh_table_emit", V, C, scratch.data_ptr(), L.ptr0(ids), L.ptr0(tri_counts), L.ptr0(vert_counts))
     return ids, tri_counts, vert_counts
 
 
@@ -148,14 +124,11 @@ def mesh_components(tris, n_verts):
 
 def gather_rows(src, inds):
     """src[inds] along dim 0 for a contiguous device tensor of any dtype, as a byte copy (mf_gather_rows)."""
-    lib, dev = L.lib(), src.device
-    n = inds.shape[0]
+    dev, n = src.device, inds.shape[0]
     out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
     row_bytes = int(np.prod(src.shape[1:], dtype=np.int64)) * src.element_size()
     if n and row_bytes:
-        with torch.cuda.device(dev):
-            L.check(lib.mf_gather_rows(src.data_ptr(), src.shape[0], row_bytes, inds.data_ptr(), n, out.data_ptr(),
-                                       L.current_stream(dev)), "mf_gather_rows")
+        L.launch(dev, "mf_gather_rows", src.data_ptr(), src.shape[0], row_bytes, inds.data_ptr(), n, out.data_ptr())
     return out
 
 
@@ -207,25 +180,22 @@ def _keep(ids, tri_counts, V, T, keep_largest, min_triangles):
 
 def _filter(verts, tris, labels, ids, keep, attrs=()):
     """The mesh of the components whose ``keep`` (C,) uint8 is set; one device -> host read ([Vk, Tk, bad])."""
-    lib, dev = L.lib(), tris.device
+    dev = tris.device
     V, T, C = verts.shape[0], tris.shape[0], ids.shape[0]
-    scratch = _bytes(lib.mf_mesh_filter_scratch_bytes(V, T), dev)
+    scratch = L.scratch(dev, "mf_mesh_filter_scratch_bytes", V, T)
     counts = torch.empty(3, dtype=torch.int64, device=dev)
-    tp = L.ptr(tris) if T else None
+    tp = L.ptr0(tris)
     with torch.cuda.device(dev):
-        stream = L.current_stream(dev)
-        L.check(lib.mf_mesh_filter_plan(tp, T, V, L.ptr(labels) if V else None, L.ptr(ids) if C else None,
-                                        L.ptr(keep) if C else None, C, counts.data_ptr(), scratch.data_ptr(), stream),
-                "mf_mesh_filter_plan")
+        L.enqueue(dev, "mf_mesh_filter_plan", tp, T, V, L.ptr0(labels), L.ptr0(ids), L.ptr0(keep), C, counts.data_ptr(),
+                  scratch.data_ptr())
         Vk, Tk, bad = (int(x) for x in counts.tolist())
         if bad:
             raise RuntimeError(f"filter_components: {bad} triangles name a vertex outside [0, {V})")
         vert_inds = torch.empty(Vk, dtype=torch.int64, device=dev)
         tri_inds = torch.empty(Tk, dtype=torch.int64, device=dev)
         tris_out = torch.empty((Tk, 3), dtype=torch.int64, device=dev)
-        L.check(lib.mf_mesh_filter_emit(tp, T, V, Vk, Tk, scratch.data_ptr(), L.ptr(vert_inds) if Vk else None,
-                                        L.ptr(tri_inds) if Tk else None, L.ptr(tris_out) if Tk else None, stream),
-                "mf_mesh_filter_emit")
+        L.enqueue(dev, "mf_mesh_filter_emit", tp, T, V, Vk, Tk, scratch.data_ptr(), L.ptr0(vert_inds), L.ptr0(tri_inds),
+                  L.ptr0(tris_out))
     return (gather_rows(verts.detach().contiguous(), vert_inds), tris_out,
             *(gather_rows(a.detach().contiguous(), vert_inds) for a in attrs))
 
@@ -316,32 +286,26 @@ def simplify_mesh(verts, tris, cell, lo=None, hi=None, placement="mean", attrs=(
 def _simplify_plan(verts, tris, grid, slots):
     """Launch the planning step on checked, contiguous device tensors: (scratch, counts), counts = device int64 [Vk, Tk, bad].
     ``grid`` = (lo, hi, cell, n0, n1, n2), lo and hi as ctypes double[3].  No host read."""
-    lib, dev, V, T = L.lib(), tris.device, verts.shape[0], tris.shape[0]
-    need = int(lib.mf_simplify_mesh_scratch_bytes(V, T, *grid[3:], slots))
-    if need < 0:                                     # too many cells, V, T or a bad table size: before anything is allocated
-        L.check(need, "mf_simplify_mesh_scratch_bytes")
-    scratch = _bytes(need, dev)
+    dev, V, T = tris.device, verts.shape[0], tris.shape[0]
+    # too many cells, V, T or a bad table size: rejected before anything is allocated
+    scratch = L.scratch(dev, "mf_simplify_mesh_scratch_bytes", V, T, *grid[3:], slots)
     counts = torch.empty(3, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_simplify_mesh_plan(L.ptr(verts) if V else None, V, L.ptr(tris) if T else None, T, *grid, slots,
-                                          counts.data_ptr(), scratch.data_ptr(), L.current_stream(dev)), "mf_simplify_mesh_plan")
+    L.launch(dev, "mf_simplify_mesh_plan", L.ptr0(verts), V, L.ptr0(tris), T, *grid, slots, counts.data_ptr(),
+             scratch.data_ptr())
     return scratch, counts
 
 
 def _simplify_emit(verts, tris, grid, scratch, Vk, Tk, mean):
     """The emit step after the plan on the same stream, with the counts read: (verts_k or None, tris_k, first, cluster);
     verts_k only for the mean placement."""
-    lib, dev, V, T = L.lib(), tris.device, verts.shape[0], tris.shape[0]
+    dev, V, T = tris.device, verts.shape[0], tris.shape[0]
     verts_k = torch.empty((Vk, 3), dtype=torch.float32, device=dev) if mean else None
-    sums = _bytes(28 * Vk, dev) if mean and Vk else None
+    sums = torch.empty(28 * Vk, dtype=torch.uint8, device=dev) if mean and Vk else None
     tris_k = torch.empty((Tk, 3), dtype=torch.int64, device=dev)
     first = torch.empty(Vk, dtype=torch.int64, device=dev)
     cluster = torch.empty(V, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_simplify_mesh_emit(L.ptr(verts) if V else None, V, L.ptr(tris) if T else None, T, *grid, Vk, Tk,
-                                          scratch.data_ptr(), L.ptr(sums), L.ptr(verts_k) if mean and Vk else None,
-                                          L.ptr(tris_k) if Tk else None, L.ptr(first) if Vk else None,
-                                          L.ptr(cluster) if V else None, L.current_stream(dev)), "mf_simplify_mesh_emit")
+    L.launch(dev, "mf_simplify_mesh_emit", L.ptr0(verts), V, L.ptr0(tris), T, *grid, Vk, Tk, scratch.data_ptr(), L.ptr(sums),
+             L.ptr0(verts_k), L.ptr0(tris_k), L.ptr0(first), L.ptr0(cluster))
     return verts_k, tris_k, first, cluster
 
 
@@ -350,18 +314,14 @@ MAX_TRIANGLES_PER_VERTEX = 2048          # include/mocoflow_hip.h MF_MESH_MAX_TR
 
 def _rings(tris, V, what):
     """vertex_rings on a checked, contiguous (T, 3) int64 device tensor; one device -> host read ([bad, over_cap, R])."""
-    lib, dev, T = L.lib(), tris.device, tris.shape[0]
-    need = int(lib.mf_rings_mesh_scratch_bytes(V, T))
-    if need < 0:                                     # V or 6 T beyond 32-bit indexing: rejected before anything is allocated
-        L.check(need, "mf_rings_mesh_scratch_bytes")
-    scratch = _bytes(need, dev)
+    dev, T = tris.device, tris.shape[0]
+    scratch = L.scratch(dev, "mf_rings_mesh_scratch_bytes", V, T)    # V or 6 T beyond 32-bit indexing: rejected here
     counts = torch.empty(3, dtype=torch.int64, device=dev)
     offsets = torch.empty(V + 1, dtype=torch.int64, device=dev)
     boundary = torch.empty(V, dtype=torch.bool, device=dev)
     with torch.cuda.device(dev):
-        stream = L.current_stream(dev)
-        L.check(lib.mf_rings_mesh_plan(L.ptr(tris) if T else None, T, V, counts.data_ptr(), offsets.data_ptr(),
-                                       L.ptr(boundary) if V else None, scratch.data_ptr(), stream), "mf_rings_mesh_plan")
+        L.enqueue(dev, "mf_rings_mesh_plan", L.ptr0(tris), T, V, counts.data_ptr(), offsets.data_ptr(), L.ptr0(boundary),
+                  scratch.data_ptr())
         bad, over, R = (int(x) for x in counts.tolist())
         if bad:
             raise RuntimeError(f"{what}: {bad} triangles name a vertex outside [0, {V})")
@@ -369,8 +329,7 @@ def _rings(tris, V, what):
             raise RuntimeError(f"{what}: {over} vertices are in more than MAX_TRIANGLES_PER_VERTEX = "
                                f"{MAX_TRIANGLES_PER_VERTEX} triangles")
         ring = torch.empty(R, dtype=torch.int64, device=dev)
-        L.check(lib.mf_rings_mesh_emit(V, T, R, scratch.data_ptr(), offsets.data_ptr(), L.ptr(ring) if R else None, stream),
-                "mf_rings_mesh_emit")
+        L.enqueue(dev, "mf_rings_mesh_emit", V, T, R, scratch.data_ptr(), offsets.data_ptr(), L.ptr0(ring))
     return offsets, ring, boundary
 
 
@@ -465,17 +424,12 @@ def smooth_mesh(verts, tris, iterations=10, lam=0.5, mu=-0.53, boundary="fixed",
         offsets, ring, bnd = offsets.contiguous(), ring.contiguous(), bnd.contiguous()
     if iterations == 0 or V == 0:
         return verts.clone()
-    lib, dev, R = L.lib(), verts.device, ring.shape[0]
-    need = int(lib.mf_smooth_mesh_scratch_bytes(V, R))
-    if need < 0:
-        L.check(need, "mf_smooth_mesh_scratch_bytes")
-    scratch = _bytes(need, dev)
+    dev, R = verts.device, ring.shape[0]
+    scratch = L.scratch(dev, "mf_smooth_mesh_scratch_bytes", V, R)
     out = torch.empty_like(verts)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_smooth_mesh(verts.data_ptr(), V, offsets.data_ptr(), L.ptr(ring) if R else None, R,
-                                   bnd.data_ptr() if boundary == "fixed" else None, int(iterations), float(lam),
-                                   0.0 if mu is None else float(mu), 0 if mu is None else 1, out.data_ptr(), scratch.data_ptr(),
-                                   L.current_stream(dev)), "mf_smooth_mesh")
+    L.launch(dev, "mf_smooth_mesh", verts.data_ptr(), V, offsets.data_ptr(), L.ptr0(ring), R,
+             bnd.data_ptr() if boundary == "fixed" else None, int(iterations), float(lam), 0.0 if mu is None else float(mu),
+             0 if mu is None else 1, out.data_ptr(), scratch.data_ptr())
     return out
 
 

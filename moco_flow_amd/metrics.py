@@ -49,12 +49,9 @@ def _sqerr(a, b, valid_mask, what):
     if valid_mask is not None:
         row_len = _row_len(a.shape, valid_mask, what)
         mask = valid_mask.to(a.device).contiguous().view(torch.uint8)
-    lib = L.lib()
     out = torch.empty(2, dtype=torch.float64, device=a.device)
-    scratch = torch.empty(max(int(lib.mf_sqerr_scratch_bytes(n)), 8), dtype=torch.uint8, device=a.device)
-    with torch.cuda.device(a.device):
-        L.check(lib.mf_sqerr(a.data_ptr(), b.data_ptr(), n, L.ptr(mask), max(row_len, 1), out.data_ptr(), scratch.data_ptr(),
-                             L.current_stream(a.device)), "mf_sqerr")
+    scratch = L.scratch(a.device, "mf_sqerr_scratch_bytes", n)
+    L.launch(a.device, "mf_sqerr", a.data_ptr(), b.data_ptr(), n, L.ptr(mask), max(row_len, 1), out.data_ptr(), scratch.data_ptr())
     return out
 
 
@@ -79,18 +76,12 @@ def psnr(image_pred, image_gt, valid_mask=None, reduction='mean'):
 def _ssim_launch(a, a_strides, b, b_strides, shape, window_size, max_val, want_map):
     """mf_ssim on two strided fp32 images -> (map or None, device double[2] = [sum ssim, sum (a - b)^2])."""
     B, Cn, H, W = shape
-    lib = L.lib()
-    need = int(lib.mf_ssim_scratch_bytes(B, Cn, H, W))
-    if need < 0:
-        L.check(need, "mf_ssim_scratch_bytes")
     dev = a.device
+    scratch = L.scratch(dev, "mf_ssim_scratch_bytes", B, Cn, H, W)
     sums = torch.empty(2, dtype=torch.float64, device=dev)
-    scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     out = torch.empty(shape, dtype=torch.float32, device=dev) if want_map else None
-    with torch.cuda.device(dev):
-        L.check(lib.mf_ssim(a.data_ptr(), (C.c_int64 * 4)(*a_strides), b.data_ptr(), (C.c_int64 * 4)(*b_strides), B, Cn, H, W,
-                            int(window_size), float(max_val), 1e-12, L.ptr(out), sums.data_ptr(), scratch.data_ptr(),
-                            L.current_stream(dev)), "mf_ssim")
+    L.launch(dev, "mf_ssim", a.data_ptr(), (C.c_int64 * 4)(*a_strides), b.data_ptr(), (C.c_int64 * 4)(*b_strides), B, Cn, H, W,
+             int(window_size), float(max_val), 1e-12, L.ptr(out), sums.data_ptr(), scratch.data_ptr())
     return out, sums
 
 

@@ -131,8 +131,6 @@ class NeRF(nn.Module):
             x = x.contiguous()
         B = x.shape[0]
         out = torch.empty((B, 1 if sigma_only else 4), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            L.check(L.lib().mf_nerf_forward(desc, buf.data_ptr(), L.ptr(x), x.stride(0) if B else width, B,
-                                            1 if sigma_only else 0, L.ptr(out), L.current_stream(x.device)),
-                    "mf_nerf_forward")
+        L.launch(x.device, "mf_nerf_forward", desc, buf.data_ptr(), L.ptr(x), x.stride(0) if B else width, B,
+                 1 if sigma_only else 0, L.ptr(out))
         return out

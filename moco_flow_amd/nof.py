@@ -116,7 +116,5 @@ class NoF(nn.Module):
             x = x.contiguous()
         p = xyz.detach().float().contiguous()
         out = torch.empty((B, 3), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            L.check(L.lib().mf_nof_forward(desc, buf.data_ptr(), L.ptr(x), x.stride(0) if B else width, L.ptr(p), B,
-                                           L.ptr(out), L.current_stream(x.device)), "mf_nof_forward")
+        L.launch(x.device, "mf_nof_forward", desc, buf.data_ptr(), L.ptr(x), x.stride(0) if B else width, L.ptr(p), B, L.ptr(out))
         return out

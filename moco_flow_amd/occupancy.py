@@ -68,19 +68,13 @@ class OccupancyGrid:
         if activate_type not in _ACT:
             raise RuntimeError(f"OccupancyGrid.from_sigma: activate_type {activate_type!r} (relu | softplus)")
         nx, ny, nz = (int(n) for n in volume.shape)
-        lib = L.lib()
-        need = int(lib.mf_occ_build_scratch_bytes(nx, ny, nz))
-        if need < 0:                                 # bad shape: rejected before anything is allocated or copied
-            L.check(need, "mf_occ_build_scratch_bytes")
+        dev = volume.device
+        scratch = L.scratch(dev, "mf_occ_build_scratch_bytes", nx, ny, nz)    # a bad shape is rejected here, before anything is copied
         vol = volume.detach().float().contiguous()
-        dev = vol.device
         bits = torch.empty((nx - 1, ny - 1, (nz - 1 + 31) // 32), dtype=torch.int32, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_occ_build(vol.data_ptr(), nx, ny, nz, _ACT[activate_type], float(np.float32(sigma_threshold)),
-                                     int(dilate), bits.data_ptr(), count.data_ptr(), scratch.data_ptr(),
-                                     L.current_stream(dev)), "mf_occ_build")
+        L.launch(dev, "mf_occ_build", vol.data_ptr(), nx, ny, nz, _ACT[activate_type], float(np.float32(sigma_threshold)),
+                 int(dilate), bits.data_ptr(), count.data_ptr(), scratch.data_ptr())
         return cls(bits, (nx - 1, ny - 1, nz - 1), lo, hi, count)
 
     @staticmethod
@@ -169,11 +163,8 @@ class OccupancyGrid:
         t_first = torch.empty(R, dtype=torch.float32, device=dev)
         t_last = torch.empty(R, dtype=torch.float32, device=dev)
         hit = torch.empty(R, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_ray_clip(r.data_ptr() if R else None, stride, R, self.bits.data_ptr(), *self.dims, _f3(self.lo),
-                                        _f3(self.hi), _f3(self.inv_cell), self.step_length(step), L.ptr(t_first) if R else None,
-                                        L.ptr(t_last) if R else None, L.ptr(hit) if R else None, L.current_stream(dev)),
-                    "mf_ray_clip")
+        L.launch(dev, "mf_ray_clip", L.ptr0(r), stride, R, self.bits.data_ptr(), *self.dims, _f3(self.lo), _f3(self.hi),
+                 _f3(self.inv_cell), self.step_length(step), L.ptr0(t_first), L.ptr0(t_last), L.ptr0(hit))
         return t_first, t_last, hit
 
     def cull(self, rays, tighten="none", step=0.5):
@@ -262,10 +253,8 @@ class OccupancyGrid:
         surface = cls(bits, dims, box[0], box[1])                         # its lo, hi and inv_cell are what the kernel is given
         dropped = torch.empty(1, dtype=torch.int64, device=dev) if return_dropped else None
         V, T = int(v.shape[0]), int(t.shape[0])
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_voxel_mesh(v.data_ptr() if V else None, V, t.data_ptr() if T else None, T, *dims, _f3(surface.lo),
-                                          _f3(surface.hi), _f3(surface.inv_cell), bits.data_ptr(), L.ptr(dropped),
-                                          L.current_stream(dev)), "mf_voxel_mesh")
+        L.launch(dev, "mf_voxel_mesh", L.ptr0(v), V, L.ptr0(t), T, *dims, _f3(surface.lo), _f3(surface.hi), _f3(surface.inv_cell),
+                 bits.data_ptr(), L.ptr(dropped))
         grid = surface.filled() if solid else surface
         radii = tuple(dilate[a] + int(math.ceil(thickness / float(surface.cell[a]))) for a in range(3))
         grid = grid.dilated(radii)
@@ -285,17 +274,11 @@ class OccupancyGrid:
     def filled(self):
         """A new grid over the same box: this one plus every empty cell that is not 6-connected through empty cells to the outside
         of the grid (mf_voxel_fill).  No synchronisation; the count is left to ``occupied_fraction``."""
-        lib = L.lib()
-        need = int(lib.mf_voxel_fill_scratch_bytes(*self.dims))
-        if need < 0:
-            L.check(need, "mf_voxel_fill_scratch_bytes")
         dev = self.device
+        scratch = L.scratch(dev, "mf_voxel_fill_scratch_bytes", *self.dims)
         src = self.bits.contiguous()
         out = torch.empty_like(src)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_voxel_fill(src.data_ptr(), *self.dims, out.data_ptr(), scratch.data_ptr(), L.current_stream(dev)),
-                    "mf_voxel_fill")
+        L.launch(dev, "mf_voxel_fill", src.data_ptr(), *self.dims, out.data_ptr(), scratch.data_ptr())
         return OccupancyGrid(out, self.dims, self.lo, self.hi)
 
     def dilated(self, radii):
@@ -305,18 +288,12 @@ class OccupancyGrid:
         radii = _int3(radii, "radii", 0)
         if any(r >= 1 << 31 for r in radii):
             raise RuntimeError(f"OccupancyGrid.dilated: radii {radii} do not fit 32 bits")
-        lib = L.lib()
-        need = int(lib.mf_voxel_dilate_scratch_bytes(*self.dims))
-        if need < 0:
-            L.check(need, "mf_voxel_dilate_scratch_bytes")
         dev = self.device
+        scratch = L.scratch(dev, "mf_voxel_dilate_scratch_bytes", *self.dims)
         src = self.bits.contiguous()
         out = torch.empty_like(src)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_voxel_dilate(src.data_ptr(), *self.dims, *radii, out.data_ptr(), count.data_ptr(), scratch.data_ptr(),
-                                        L.current_stream(dev)), "mf_voxel_dilate")
+        L.launch(dev, "mf_voxel_dilate", src.data_ptr(), *self.dims, *radii, out.data_ptr(), count.data_ptr(), scratch.data_ptr())
         return OccupancyGrid(out, self.dims, self.lo, self.hi, count)
 
     def _same_grid(self, other, what):

@@ -102,8 +102,8 @@ class PackedWeights:
         if key != st[0]:
             desc, keep = build_desc()
             nbytes = bytes_fn(desc, precision)
-            if nbytes <= 0:
-                L.check(-3, what)
+            if nbytes <= 0:                              # a negative size is the library's code; 0 is how the *_packed_bytes
+                L.check(nbytes or -3, what)              # queries say "unsupported configuration" (MF_E_UNSUPPORTED)
             buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
                 order = BuildOrder(dev)

@@ -47,13 +47,10 @@ def query_sigma(xyz, nerf, nerf_embedding_xyz, bw_nof=None, nof_embeddings=None,
                 raise RuntimeError(f"query_sigma: ind must have 1 or {B} elements")
         else:
             ind_s = float(ind)
-    need = int(L.lib().mf_points_sigma_workspace_bytes(prec, fd, 1 if ind_t is not None else 0, B)) if fd is not None else 0
+    need = L.need("mf_points_sigma_workspace_bytes", prec, fd, 1 if ind_t is not None else 0, B) if fd is not None else 0
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need > 0 else None     # bf16 + NoF: per-point index bias
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_points_sigma_p(prec, nd, nb.data_ptr(), C.byref(ex), fd, L.ptr(fb),
-                                          C.byref(fx) if fx is not None else None,
-                                          C.byref(fi) if fi is not None else None, L.ptr(x), L.ptr(ind_t), ind_s, B,
-                                          L.ptr(sigma), L.ptr(canon), L.ptr(ws), need, L.current_stream(dev)), "mf_points_sigma")
+    L.launch(dev, "mf_points_sigma_p", prec, nd, nb.data_ptr(), C.byref(ex), fd, L.ptr(fb), C.byref(fx) if fx is not None else None,
+             C.byref(fi) if fi is not None else None, L.ptr(x), L.ptr(ind_t), ind_s, B, L.ptr(sigma), L.ptr(canon), L.ptr(ws), need)
     return (sigma, canon) if return_canonical else sigma
 
 
@@ -133,38 +130,30 @@ def query_sigma_lattice(axes, nerf, nerf_embedding_xyz, occupancy, world_of_axis
             raise RuntimeError(f"{who}: axes[{a}] must be 1-D, finite and ascending, got shape {x.shape}")
         host.append(x)
     n = [int(x.shape[0]) for x in host]
-    lib = L.lib()
-    need = int(lib.mf_lattice_select_scratch_bytes(*n))
-    if need < 0:                                     # bad shape: rejected before anything is allocated or copied
-        L.check(need, "mf_lattice_select_scratch_bytes")
+    scratch = L.scratch(dev, "mf_lattice_select_scratch_bytes", *n)      # a bad shape is rejected here, before anything is copied
     bricks = int(np.prod([(v + BRICK - 1) // BRICK for v in n], dtype=np.int64))
     ranges = [brick_cell_ranges(host[a], margin, occupancy.lo[woa[a]], occupancy.hi[woa[a]], occupancy.inv_cell[woa[a]],
                                 occupancy.dims[woa[a]]) for a in range(3)]
     woa_c = (C.c_int32 * 3)(*woa)
     with torch.no_grad(), torch.cuda.device(dev):
-        stream = L.current_stream(dev)
         tables = [torch.from_numpy(r).to(dev) for r in ranges]
         ax = [torch.from_numpy(x).to(dev) for x in host]
         slot = torch.empty(bricks, dtype=torch.int32, device=dev)
         ids = torch.empty(bricks, dtype=torch.int32, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.mf_lattice_select(occupancy.bits.data_ptr(), *occupancy.dims, *(t.data_ptr() for t in tables), *n, woa_c,
-                                      slot.data_ptr(), ids.data_ptr(), count.data_ptr(), scratch.data_ptr(), stream),
-                "mf_lattice_select")
+        L.enqueue(dev, "mf_lattice_select", occupancy.bits.data_ptr(), *occupancy.dims, *(t.data_ptr() for t in tables), *n, woa_c,
+                  slot.data_ptr(), ids.data_ptr(), count.data_ptr(), scratch.data_ptr())
         K = int(count.item())
         parts = []
         for k0 in range(0, K, LATTICE_CHUNK_BRICKS):
             kc = min(LATTICE_CHUNK_BRICKS, K - k0)
             pts = torch.empty((kc * BRICK ** 3, 3), dtype=torch.float32, device=dev)
-            L.check(lib.mf_lattice_points(ids.data_ptr() + 4 * k0, kc, *(t.data_ptr() for t in ax), *n, woa_c, pts.data_ptr(),
-                                          stream), "mf_lattice_points")
+            L.enqueue(dev, "mf_lattice_points", ids.data_ptr() + 4 * k0, kc, *(t.data_ptr() for t in ax), *n, woa_c, pts.data_ptr())
             parts.append(query_sigma(pts, nerf, nerf_embedding_xyz, bw_nof, nof_embeddings, ind, precision=precision))
             del pts
         sigma = None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts)
         volume = torch.empty(n, dtype=torch.float32, device=dev)
-        L.check(lib.mf_lattice_scatter(L.ptr(sigma), slot.data_ptr(), K, *n, float(fill), volume.data_ptr(), stream),
-                "mf_lattice_scatter")
+        L.enqueue(dev, "mf_lattice_scatter", L.ptr(sigma), slot.data_ptr(), K, *n, float(fill), volume.data_ptr())
     return (volume, (K, bricks)) if return_stats else volume
 
 
@@ -228,8 +217,6 @@ def query_radiance(xyz, nerf, nerf_embeddings, view_dirs=None, ind=None, bw_nof=
         fd, fb = bw_nof.packed(L.MF_PREC_F32)
         fx, fi = nof_embeddings[0].descriptor(), nof_embeddings[1].descriptor()
     ref = lambda d: C.byref(d) if d is not None else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_points_radiance(nd, nb.data_ptr(), C.byref(ex), ref(eext), fd, L.ptr(fb), ref(fx), ref(fi), L.ptr(x),
-                                           L.ptr(dirs), L.ptr(ind_t), ind_s, B, L.ptr(out), L.ptr(canon),
-                                           L.current_stream(dev)), "mf_points_radiance")
+    L.launch(dev, "mf_points_radiance", nd, nb.data_ptr(), C.byref(ex), ref(eext), fd, L.ptr(fb), ref(fx), ref(fi), L.ptr(x),
+             L.ptr(dirs), L.ptr(ind_t), ind_s, B, L.ptr(out), L.ptr(canon))
     return (out, canon) if return_canonical else out

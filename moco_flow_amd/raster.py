@@ -98,15 +98,9 @@ def project_vertices(verts, c2w, focal, center, znear=1e-3, return_xy=False):
     screen = torch.empty((V, 2), dtype=torch.int32, device=dev)
     inv_z = torch.empty(V, dtype=torch.float32, device=dev)
     xy = torch.empty((V, 2), dtype=torch.float32, device=dev) if return_xy else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_project_vertices(L.ptr(v) if V else None, V, mat, _f32(focal), _f32(center[0]), _f32(center[1]), _f32(znear),
-                                            L.ptr(screen) if V else None, L.ptr(inv_z) if V else None, L.ptr(xy) if V else None,
-                                            L.current_stream(dev)), "mf_project_vertices")
+    L.launch(dev, "mf_project_vertices", L.ptr0(v), V, mat, _f32(focal), _f32(center[0]), _f32(center[1]), _f32(znear),
+             L.ptr0(screen), L.ptr0(inv_z), L.ptr0(xy))
     return (screen, inv_z, xy) if return_xy else (screen, inv_z)
-
-
-def _p(t):
-    return t.data_ptr() if t is not None and t.numel() else None
 
 
 def _fill_keys(screen, inv_z, tris, H, W, pixel_offset, what):
@@ -122,11 +116,9 @@ def _fill_keys(screen, inv_z, tris, H, W, pixel_offset, what):
         raise RuntimeError(f"moco_flow_amd.raster.{what}: inv_z is on {inv_z.device}, screen on {dev}")
     inv_z = inv_z.detach().contiguous()
     tris = _tris(tris, what, dev)
-    lib = L.lib()
-    scratch = torch.empty(int(lib.mf_raster_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_rasterize(_p(screen), _p(inv_z), V, _p(tris), tris.shape[0], H, W, pixel_offset, scratch.data_ptr(),
-                                 L.current_stream(dev)), "mf_rasterize")
+    scratch = L.scratch(dev, "mf_raster_scratch_bytes", H, W)
+    L.launch(dev, "mf_rasterize", L.ptr0(screen), L.ptr0(inv_z), V, L.ptr0(tris), tris.shape[0], H, W, pixel_offset,
+             scratch.data_ptr())
     return screen, inv_z, tris, scratch
 
 
@@ -144,10 +136,8 @@ def rasterize(screen, inv_z, tris, H, W, pixel_offset=0.0, return_dropped=False)
     depth = torch.empty((H, W), dtype=torch.float32, device=dev)
     bary = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
     dropped = torch.empty(1, dtype=torch.int64, device=dev) if return_dropped else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_raster_resolve(scratch.data_ptr(), _p(screen), _p(inv_z), screen.shape[0], _p(tris), tris.shape[0], H, W, off,
-                                          face.data_ptr(), depth.data_ptr(), bary.data_ptr(), L.ptr(dropped), L.current_stream(dev)),
-                "mf_raster_resolve")
+    L.launch(dev, "mf_raster_resolve", scratch.data_ptr(), L.ptr0(screen), L.ptr0(inv_z), screen.shape[0], L.ptr0(tris),
+             tris.shape[0], H, W, off, face.data_ptr(), depth.data_ptr(), bary.data_ptr(), L.ptr(dropped))
     return (face, depth, bary, int(dropped.item())) if return_dropped else (face, depth, bary)
 
 
@@ -170,9 +160,8 @@ def interpolate(attrs, tris, face, bary):
             raise RuntimeError(f"moco_flow_amd.raster.interpolate: {name} is on {t.device}, attrs on {dev}")
     face, bary = face.contiguous(), bary.contiguous()
     out = torch.empty((H, W, Cn), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_raster_interpolate(_p(a), a.shape[0], Cn, _p(tris), tris.shape[0], _p(face), _p(bary), H * W, _p(out),
-                                              L.current_stream(dev)), "mf_raster_interpolate")
+    L.launch(dev, "mf_raster_interpolate", L.ptr0(a), a.shape[0], Cn, L.ptr0(tris), tris.shape[0], L.ptr0(face), L.ptr0(bary),
+             H * W, L.ptr0(out))
     return out
 
 
@@ -247,15 +236,14 @@ def render_mesh(verts, tris, colors, H, W, focal, center, c2w, background=None, 
             res[name] = torch.empty(shape(H, W), dtype=dtype, device=dev)
     if not res:
         raise RuntimeError("moco_flow_amd.raster.render_mesh: out names none of rgba, mask, depth, ray_t, face")
-    a.scratch, a.screen, a.inv_z, a.verts, a.colors, a.V = scratch.data_ptr(), _p(screen), _p(inv_z), _p(v), _p(col), V
-    a.tris, a.T, a.H, a.W = _p(tris), tris.shape[0], H, W
+    a.scratch, a.screen, a.inv_z, a.verts, a.colors, a.V = scratch.data_ptr(), L.ptr0(screen), L.ptr0(inv_z), L.ptr0(v), L.ptr0(col), V
+    a.tris, a.T, a.H, a.W = L.ptr0(tris), tris.shape[0], H, W
     a.focal, a.cx, a.cy, a.pixel_offset = _f32(focal), _f32(center[0]), _f32(center[1]), off
     a.c2w = mat
     a.shading, a.ambient = _SHADING[shading], _f32(ambient)
     for name in res:
         setattr(a, name, res[name].data_ptr())
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_raster_shade(C.byref(a), L.current_stream(dev)), "mf_raster_shade")
+    L.launch(dev, "mf_raster_shade", C.byref(a))
     return res
 
 

@@ -205,7 +205,7 @@ def _render_pass(rays, background, z_vals, z_steps, use_disp, noise, activation,
             else:
                 a.dump_nof_emb = alloc("nof_emb", (steps, N * S, 80))
             a.dump_nof_out = alloc("nof_out", (steps, N * S, 3))
-    need = int(L.lib().mf_render_workspace_bytes(C.byref(a)))      # bf16 + NoF: the per-ray bias table (ABI v12)
+    need = L.need("mf_render_workspace_bytes", C.byref(a))         # bf16 + NoF: the per-ray bias table (ABI v12)
     with torch.cuda.device(dev):
         if need > 0:
             shared = workspace if workspace is not None else [None]
@@ -215,8 +215,8 @@ def _render_pass(rays, background, z_vals, z_steps, use_disp, noise, activation,
             a.workspace, a.workspace_bytes = shared[0].data_ptr(), need
             keep.append(shared[0])
             if fresh:
-                L.check(L.lib().mf_render_prepare(C.byref(a), L.current_stream(dev)), "mf_render_prepare")
-        L.check(L.lib().mf_render_pass(C.byref(a), L.current_stream(dev)), "mf_render_pass")
+                L.enqueue(dev, "mf_render_prepare", C.byref(a))
+        L.enqueue(dev, "mf_render_pass", C.byref(a))
     del keep
     return out
 
@@ -224,7 +224,6 @@ def _render_pass(rays, background, z_vals, z_steps, use_disp, noise, activation,
 def _loss_partials_hip(c, f, target, N):
     """mf_loss_partials over the arrays the passes wrote: 12 float64 on the device, no host sync."""
     dev = target.device
-    lib = L.lib()
     tgt = target.detach().contiguous().float()
     if tgt.shape != (N, 3):
         raise RuntimeError(f"_loss_target must be (N, 3) = ({N}, 3), got {tuple(tgt.shape)}")
@@ -241,10 +240,9 @@ def _loss_partials_hip(c, f, target, N):
     dc = desc(c)
     df = desc(f) if f is not None else None
     out = torch.empty(12, dtype=torch.float64, device=dev)
-    scratch = torch.empty(int(lib.mf_loss_partials_scratch_bytes()), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_loss_partials(C.byref(dc), C.byref(df) if df is not None else None, tgt.data_ptr(), N,
-                                     out.data_ptr(), None, scratch.data_ptr(), L.current_stream(dev)), "mf_loss_partials")
+    scratch = L.scratch(dev, "mf_loss_partials_scratch_bytes")
+    L.launch(dev, "mf_loss_partials", C.byref(dc), C.byref(df) if df is not None else None, tgt.data_ptr(), N, out.data_ptr(),
+             None, scratch.data_ptr())
     return out
 
 
@@ -252,14 +250,12 @@ def _compact(alphas, vals_a, vals_b):
     """rendering.py:306-314: (vals[mask] for mask = alphas >= 0.01, all-true if empty)."""
     dev = alphas.device
     N, S = alphas.shape
-    lib = L.lib()
-    scratch = torch.empty(int(lib.mf_compact_scratch_bytes(N)), dtype=torch.uint8, device=dev)
+    scratch = L.scratch(dev, "mf_compact_scratch_bytes", N)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     oa = torch.empty(N * S, device=dev, dtype=torch.float32) if vals_a is not None else None
     ob = torch.empty(N * S, device=dev, dtype=torch.float32) if vals_b is not None else None
-    with torch.cuda.device(dev):
-        L.check(lib.mf_compact_mask(L.ptr(alphas), L.ptr(vals_a), L.ptr(vals_b), N, S, L.ptr(oa), L.ptr(ob),
-                                    count.data_ptr(), scratch.data_ptr(), L.current_stream(dev)), "mf_compact_mask")
+    L.launch(dev, "mf_compact_mask", L.ptr(alphas), L.ptr(vals_a), L.ptr(vals_b), N, S, L.ptr(oa), L.ptr(ob), count.data_ptr(),
+             scratch.data_ptr())
     n = int(count.item())   # data-dependent length, as in the reference's boolean indexing
     return (oa[:n] if oa is not None else None), (ob[:n] if ob is not None else None)
 
@@ -267,16 +263,13 @@ def _compact(alphas, vals_a, vals_b):
 def _pass_stats(p, N):
     """(sum, count) of the masked consensus distances of ONE pass as device scalars: mf_loss_partials on its planes."""
     dev = p["alphas"].device
-    lib = L.lib()
     d = L.mf_loss_pass()
     d.alphas, d.disp_local, d.disp_global = L.ptr(p["alphas"]), L.ptr(p.get("disp_local")), L.ptr(p.get("disp_global"))
     d.n_samples = p["alphas"].shape[1]
     out = torch.empty(12, dtype=torch.float64, device=dev)
     means = torch.empty(6, dtype=torch.float32, device=dev)
-    scratch = torch.empty(int(lib.mf_loss_partials_scratch_bytes()), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.mf_loss_partials(C.byref(d), None, None, N, out.data_ptr(), means.data_ptr(), scratch.data_ptr(),
-                                     L.current_stream(dev)), "mf_loss_partials")
+    scratch = L.scratch(dev, "mf_loss_partials_scratch_bytes")
+    L.launch(dev, "mf_loss_partials", C.byref(d), None, None, N, out.data_ptr(), means.data_ptr(), scratch.data_ptr())
     # (sum, count, mean): the mean is a view of the kernel's own fp32 output -- torch.mean(vector) launches nothing
     return {"local": (out[4], out[5], means[2]), "global": (out[8], out[9], means[4]), "out12": out}
 
@@ -313,9 +306,8 @@ def sample_pdf(bins, weights, N_importance, det=False, eps=1e-5):
     b = bins.detach().contiguous().float()
     w = weights.detach().contiguous().float()
     out = torch.empty((N, M), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_sample_pdf_eps(L.ptr(b), None, L.ptr(w), nb - 1, N, nb, M, L.ptr(u), u_stride, None,
-                                          L.ptr(out), None, None, float(eps), L.current_stream(dev)), "mf_sample_pdf")
+    L.launch(dev, "mf_sample_pdf_eps", L.ptr(b), None, L.ptr(w), nb - 1, N, nb, M, L.ptr(u), u_stride, None, L.ptr(out), None,
+             None, float(eps))
     return out
 
 
@@ -343,10 +335,8 @@ def resample_merge(z_vals, weights, N_importance, det=True, u=None, return_aux=F
     z_out = torch.empty((N, S + M), device=dev, dtype=torch.float32)
     inds = torch.empty((N, M), device=dev, dtype=torch.int32) if return_aux else None
     z_new = torch.empty((N, M), device=dev, dtype=torch.float32) if return_aux else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_sample_pdf(None, L.ptr(z), w.data_ptr() + 4, S, N, S - 1, M, L.ptr(u), u_stride,
-                                      L.ptr(cdf), L.ptr(z_new), L.ptr(inds), L.ptr(z_out),
-                                      L.current_stream(dev)), "mf_sample_pdf")
+    L.launch(dev, "mf_sample_pdf", None, L.ptr(z), w.data_ptr() + 4, S, N, S - 1, M, L.ptr(u), u_stride, L.ptr(cdf),
+             L.ptr(z_new), L.ptr(inds), L.ptr(z_out))
     if return_aux:
         return z_out, inds, z_new
     return z_out
@@ -422,9 +412,8 @@ def render_rays(rays,
             pr = _rng["perturb_rand"] if "perturb_rand" in _rng else torch.rand((N, S), device=dev)
             pr = pr.contiguous().float()
         z_vals = torch.empty((N, S), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_z_vals(L.ptr(rays), rays.stride(0), N, L.ptr(z_steps), S, 1 if use_disp else 0,
-                                      L.ptr(pr), float(perturb), L.ptr(z_vals), L.current_stream(dev)), "mf_z_vals")
+        L.launch(dev, "mf_z_vals", L.ptr(rays), rays.stride(0), N, L.ptr(z_steps), S, 1 if use_disp else 0, L.ptr(pr),
+                 float(perturb), L.ptr(z_vals))
 
     def draw_noise(shape, key=None):
         if key in _rng:
@@ -648,8 +637,8 @@ def _nof_embedded_inputs(p, plane, x_obs, rays, S, nof_embs):
         for k in range(steps):
             tab = ind_j if k in (2, 3) else ind_i
             pts = src[k].contiguous()
-            L.check(L.lib().mf_nof_embed_rows(ex, L.ptr(pts), L.ptr(tab), tab.shape[1], S, P, emb[plane[k]].data_ptr(),
-                                              L.current_stream(x_obs.device)), "mf_nof_embed_rows")
+            L.enqueue(x_obs.device, "mf_nof_embed_rows", ex, L.ptr(pts), L.ptr(tab), tab.shape[1], S, P,
+                      emb[plane[k]].data_ptr())
     emb._mf_natural = True
     return emb
 

@@ -105,11 +105,8 @@ class SMPL(nn.Module):
         desc = self._model(dev)
         verts = torch.empty((B, V, 3), device=dev, dtype=torch.float32) if want_verts else None
         T = torch.empty((B, V, 4, 4), device=dev, dtype=torch.float32) if want_T else None
-        lib = L.lib()
-        scratch = torch.empty((max(int(lib.mf_smpl_scratch_bytes(V, B)), 4),), device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_smpl_lbs(desc, L.ptr(p), is_rot, L.ptr(b), B, L.ptr(verts), L.ptr(T), L.ptr(scratch),
-                                    L.current_stream(dev)), "mf_smpl_lbs")
+        scratch = L.scratch(dev, "mf_smpl_scratch_bytes", V, B)
+        L.launch(dev, "mf_smpl_lbs", desc, L.ptr(p), is_rot, L.ptr(b), B, L.ptr(verts), L.ptr(T), L.ptr(scratch))
         return verts, T
 
     def forward(self, pose, beta):
@@ -132,9 +129,7 @@ def frame_transforms(T_src, T_tgt):
     if a.shape != b.shape or a.dim() != 3 or a.shape[1:] != (4, 4):
         raise RuntimeError(f"frame_transforms expects two (V,4,4) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        L.check(L.lib().mf_smpl_frame_transforms(L.ptr(a), L.ptr(b), a.shape[0], L.ptr(out), L.current_stream(a.device)),
-                "mf_smpl_frame_transforms")
+    L.launch(a.device, "mf_smpl_frame_transforms", L.ptr(a), L.ptr(b), a.shape[0], L.ptr(out))
     return out
 
 
@@ -147,9 +142,7 @@ def apply_vertex_transforms(trans, ind, query):
     if i.shape[0] != q.shape[0]:
         raise RuntimeError(f"apply_vertex_transforms: {i.shape[0]} indices for {q.shape[0]} points")
     out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        L.check(L.lib().mf_apply_vertex_transforms(L.ptr(t), L.ptr(i), t.shape[0], L.ptr(q), q.shape[0], L.ptr(out),
-                                                   L.current_stream(q.device)), "mf_apply_vertex_transforms")
+    L.launch(q.device, "mf_apply_vertex_transforms", L.ptr(t), L.ptr(i), t.shape[0], L.ptr(q), q.shape[0], L.ptr(out))
     return out
 
 

@@ -71,10 +71,8 @@ def point_correspond(verts, trans, queries, thickness, pick=None, noise=None, la
     inside = torch.empty((Q,), device=dev, dtype=torch.uint8)
     dist = torch.empty((Q,), device=dev, dtype=torch.float32)
     ind = torch.empty((Q,), device=dev, dtype=torch.int64)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_point_correspond(v.data_ptr(), t.data_ptr(), v.shape[0], L.ptr(q), q0, L.ptr(pick), L.ptr(noise), q1,
-                                            float(thickness), int(lanes_per_query), pairs.data_ptr(), inside.data_ptr(),
-                                            dist.data_ptr(), ind.data_ptr(), L.current_stream(dev)), "mf_point_correspond")
+    L.launch(dev, "mf_point_correspond", v.data_ptr(), t.data_ptr(), v.shape[0], L.ptr(q), q0, L.ptr(pick), L.ptr(noise), q1,
+             float(thickness), int(lanes_per_query), pairs.data_ptr(), inside.data_ptr(), dist.data_ptr(), ind.data_ptr())
     return Correspondence(pairs, inside, dist, ind)
 
 
@@ -130,14 +128,11 @@ class _PointLossMeans(torch.autograd.Function):
         pred_bw, pred_fw = c(pred_bw), c(pred_fw)
         ctx.sigma_shapes = [tuple(s.shape) for s in sigmas]
         sigmas = [c(s).reshape(-1) for s in sigmas]
-        lib = L.lib()
         out6 = torch.empty(6, device=dev, dtype=torch.float64)
         means = torch.empty(3, device=dev, dtype=torch.float32)
-        scratch = torch.empty(max(int(lib.mf_point_loss_partials_scratch_bytes(pairs.shape[0])), 8), device=dev, dtype=torch.uint8)
+        scratch = L.scratch(dev, "mf_point_loss_partials_scratch_bytes", pairs.shape[0])
         a = _loss_args(pairs, inside, use_all, pred_bw, pred_fw, sigmas, deltas)
-        with torch.cuda.device(dev):
-            L.check(lib.mf_point_loss_partials(C.byref(a), out6.data_ptr(), means.data_ptr(), scratch.data_ptr(),
-                                               L.current_stream(dev)), "mf_point_loss_partials")
+        L.launch(dev, "mf_point_loss_partials", C.byref(a), out6.data_ptr(), means.data_ptr(), scratch.data_ptr())
         ctx.use_all, ctx.deltas, ctx.has = use_all, deltas, (pred_bw is not None, pred_fw is not None)
         keep = [pairs, out6] + ([inside] if inside is not None else []) + [t for t in (pred_bw, pred_fw) if t is not None] + sigmas
         ctx.has_inside = inside is not None
@@ -166,11 +161,8 @@ class _PointLossMeans(torch.autograd.Function):
         g_fw = torch.empty((Q, 3), device=dev, dtype=torch.float32) if pred_fw is not None and need[5] else None
         g_sig = [torch.empty(ctx.sigma_shapes[i], device=dev, dtype=torch.float32) if need[6 + i] else None for i in range(len(sigmas))]
         a = _loss_args(pairs, inside, ctx.use_all, pred_bw, pred_fw, sigmas, ctx.deltas)
-        with torch.cuda.device(dev):
-            L.check(L.lib().mf_point_loss_partials_backward(C.byref(a), out6.data_ptr(), seeds.data_ptr(), L.ptr(g_bw), L.ptr(g_fw),
-                                                            L.ptr(g_sig[0]) if len(g_sig) > 0 else None,
-                                                            L.ptr(g_sig[1]) if len(g_sig) > 1 else None, L.current_stream(dev)),
-                    "mf_point_loss_partials_backward")
+        L.launch(dev, "mf_point_loss_partials_backward", C.byref(a), out6.data_ptr(), seeds.data_ptr(), L.ptr(g_bw), L.ptr(g_fw),
+                 L.ptr(g_sig[0]) if len(g_sig) > 0 else None, L.ptr(g_sig[1]) if len(g_sig) > 1 else None)
         return (None, None, None, None, g_bw, g_fw) + tuple(g_sig)
 
 

@@ -79,12 +79,9 @@ def _range_into(out2, plane, mi, ma):
             else:
                 slot.fill_(float(v))
         return float(ma)
-    lib = L.lib()
     n = plane.numel()
-    scratch = torch.empty(max(int(lib.mf_depth_range_scratch_bytes(n)), 8), dtype=torch.uint8, device=plane.device)
-    with torch.cuda.device(plane.device):
-        L.check(lib.mf_depth_range(plane.data_ptr(), n, 0.0, out2.data_ptr(), scratch.data_ptr(), L.current_stream(plane.device)),
-                "mf_depth_range")
+    scratch = L.scratch(plane.device, "mf_depth_range_scratch_bytes", n)
+    L.launch(plane.device, "mf_depth_range", plane.data_ptr(), n, 0.0, out2.data_ptr(), scratch.data_ptr())
     return 0.0
 
 
@@ -101,9 +98,7 @@ def visualize_depth(depth, mi=None, ma=None, cmap=COLORMAP_JET):
     range2 = torch.empty(2, dtype=torch.float32, device=dev)
     nan_value = _range_into(range2, plane, mi, ma)
     out = torch.empty((3,) + tuple(plane.shape), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_depth_colormap(plane.data_ptr(), plane.numel(), range2.data_ptr(), nan_value, lut.data_ptr(),
-                                          out.data_ptr(), L.current_stream(dev)), "mf_depth_colormap")
+    L.launch(dev, "mf_depth_colormap", plane.data_ptr(), plane.numel(), range2.data_ptr(), nan_value, lut.data_ptr(), out.data_ptr())
     return out
 
 
@@ -153,9 +148,7 @@ def frame_sheet(panels, H, W, planar=False, cmap=COLORMAP_JET):
     stack = torch.empty((3, H, k * W), dtype=torch.float32, device=dev) if planar else None
     if H * W == 0:                       # nothing to launch (and an empty tensor has no pointer to pass)
         return (sheet, stack) if planar else sheet
-    with torch.cuda.device(dev):
-        L.check(L.lib().mf_frame_sheet(items, k, H, W, range2s.data_ptr(), lut.data_ptr(), sheet.data_ptr(), L.ptr(stack),
-                                       L.current_stream(dev)), "mf_frame_sheet")
+    L.launch(dev, "mf_frame_sheet", items, k, H, W, range2s.data_ptr(), lut.data_ptr(), sheet.data_ptr(), L.ptr(stack))
     return (sheet, stack) if planar else sheet
 
 

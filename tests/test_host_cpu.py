@@ -1236,3 +1236,61 @@ def test_shares_header_under_the_sanitizers(tmp_path):
     assert build.returncode == 0, build.stderr
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "shares ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
+
+
+# ------------------------------------------------------------------ the binding helpers of _lib.py
+@pytest.mark.parametrize("name, dims", [("mf_mc_scratch_bytes", (4, 4, 4)), ("mf_mesh_label_scratch_bytes", (8, 4))])
+def test_need_is_the_size_query(name, dims):
+    import moco_flow_amd._lib as L
+    direct = int(getattr(L.lib(), name)(*dims))
+    assert direct > 0 and L.need(name, *dims) == direct
+
+
+@pytest.mark.parametrize("name, dims", [("mf_mc_scratch_bytes", (1, 4, 4)), ("mf_mesh_label_scratch_bytes", (2 ** 31, 1))])
+def test_need_raises_the_library_message_before_any_allocation(name, dims, monkeypatch):
+    import moco_flow_amd._lib as L
+
+    def no_allocation(*a, **k):
+        raise AssertionError("a refused size query reached torch.empty")
+
+    monkeypatch.setattr(torch, "empty", no_allocation)
+    rc = int(getattr(L.lib(), name)(*dims))
+    assert rc < 0
+    text = L.lib().mf_last_error().decode()
+    assert text
+    kind = NotImplementedError if rc == -3 else RuntimeError
+    for fn, args in ((L.need, (name,) + dims), (L.scratch, ("cuda", name) + dims)):
+        with pytest.raises(kind) as e:
+            fn(*args)
+        assert type(e.value) is kind and text in str(e.value) and name in str(e.value), str(e.value)
+
+
+def test_helper_names_are_declared_symbols():
+    """Every string literal given as ``name`` to L.launch / enqueue / call / need / scratch in the package is a key of
+    SYMBOLS: a typo fails here, not at the first call on a GPU."""
+    import ast
+    import glob
+    import moco_flow_amd._lib as L
+    name_at = {"launch": 1, "enqueue": 1, "scratch": 1, "call": 0, "need": 0}
+    seen = 0
+    for path in sorted(glob.glob(os.path.join(ROOT, "moco_flow_amd", "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in name_at
+                    and isinstance(node.func.value, ast.Name) and node.func.value.id == "L"):
+                continue
+            arg = node.args[name_at[node.func.attr]]
+            where = f"{os.path.basename(path)}:{node.lineno}"
+            literals = [arg.body, arg.orelse] if isinstance(arg, ast.IfExp) else [arg]      # "a" if x else "b"
+            for lit in literals:
+                assert isinstance(lit, ast.Constant) and isinstance(lit.value, str), f"{where}: the symbol's name is not a literal"
+                assert lit.value in L.SYMBOLS, f"{where}: {lit.value!r} is not in SYMBOLS"
+                seen += 1
+    assert seen >= 90, seen
+
+
+def test_ptr0_is_null_for_none_and_empty():
+    import moco_flow_amd._lib as L
+    assert L.ptr0(None) is None
+    assert L.ptr0(torch.empty((0, 3))) is None
+    t = torch.zeros((1, 3))
+    assert L.ptr0(t) == t.data_ptr() != 0
