@@ -54,7 +54,8 @@ extern "C" {
  *     mf_mask_label (+ mf_mask_label_scratch_bytes), mf_mask_select, mf_mask_fill_holes, mf_mask_table_count / mf_mask_table_emit;
  *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes); mf_rings_mesh_plan / mf_rings_mesh_emit
  *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes); mf_voxel_mesh, mf_voxel_fill
- *     (+ mf_voxel_fill_scratch_bytes), mf_voxel_dilate (+ mf_voxel_dilate_scratch_bytes) */
+ *     (+ mf_voxel_fill_scratch_bytes), mf_voxel_dilate (+ mf_voxel_dilate_scratch_bytes); mf_grid_edt
+ *     (+ mf_grid_edt_scratch_bytes) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -992,7 +993,10 @@ int32_t mf_ray_clip(const float* rays, int64_t ray_stride, int64_t n_rays, const
  * word 0 -- built from triangles instead of densities.  The reference labels a point "inside" iff it lies within `thickness` of a
  * vertex of the posed SMPL mesh (datasets/moco_flow_dataset.py:87-142), derives the frame's AABB from that mesh
  * (datasets/moco_flow_dataset.py:144-154) and renders every ray of that box's hull (trainer_moco_flow.py:226-268).  All three
- * entries decide in integers: their results are bit-identical from run to run and equal to tests/voxelize_oracle.py. ----
+ * entries decide in integers: their results are bit-identical from run to run and equal to tests/voxelize_oracle.py.
+ * mf_voxel_dilate thickens a grid by a box of cells, a superset of the Euclidean shell; mf_grid_edt (csrc/mf_distance.hip, below
+ * the three) thickens it by the shell itself and gives the grid's squared-distance field, in integers again
+ * (tests/distance_oracle.py). ----
  *
  * mf_voxel_mesh (serves datasets/moco_flow_dataset.py:87-142, datasets/moco_flow_dataset.py:144-154,
  * trainer_moco_flow.py:226-268): verts (V, 3) fp32 and tris (T, 3) int64 on the device -> the cells the triangles' surfaces meet.
@@ -1029,6 +1033,26 @@ int32_t mf_voxel_fill(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, 
 int64_t mf_voxel_dilate_scratch_bytes(int64_t gx, int64_t gy, int64_t gz);
 int32_t mf_voxel_dilate(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, int32_t rx, int32_t ry, int32_t rz,
                         uint32_t* bits_out, int64_t* count_out, void* scratch, void* stream);
+
+/* mf_grid_edt (serves datasets/moco_flow_dataset.py:87-142, trainer_moco_flow.py:226-268; csrc/mf_distance.hip): the exact
+ * weighted squared distance field of a bit grid, capped, and the Euclidean dilation it decides.  With w (host int32[3], each in
+ * [1, 65536]) and 0 <= R < 2^30:
+ *   d2(i, j, k) = min(R + 1, min over the set cells (a, b, c) of bits of w[0] (i-a)^2 + w[1] (j-b)^2 + w[2] (k-c)^2)      int32
+ * (an empty grid: R + 1 everywhere).  d2_out (optional): (gx, gy, gz) int32, dense, z fastest.  bits_out (optional): cell
+ * (i, j, k) is set iff d2 <= R, padding bits written 0; count_out (device int64[1], optional, needs bits_out): the number of set
+ * cells, through the fixed-order reduction.  At least one of d2_out / bits_out; bits_out must not be bits; the padding bits of
+ * bits are 0.  The caller turns world units into integers (OccupancyGrid.euclid_metric): with cmax the longest cell edge and t
+ * the world radius, w_a = floor(65536 (cell_a / cmax)^2) and R = ceil(65536 (t / cmax)^2) -- the floor and the ceil keep the
+ * result a superset of the real-valued ellipsoid; cubic cells give w = 65536 on every axis and the plain Euclidean test in cell
+ * units.  Three separable passes, exact because a pass drops only terms that exceed R on their own (r_a = isqrt(R / w_a) cells
+ * is the reach along axis a; windows are clipped to the grid, a reach beyond the side works): z by bit scans on the row's words,
+ * across word boundaries, then y, then x; a term w_a d^2 with |d| <= r_a is <= R and partial minima are capped at R + 1, so
+ * every intermediate fits an int32.  No atomics: every output word or int is written by one lane with a plain store;
+ * bit-identical from run to run.  scratch: mf_grid_edt_scratch_bytes bytes (6 per cell + 8 per workgroup), always needed.
+ * Nothing allocates or synchronises.  Each side 1 .. 1024, else MF_E_INVALID. */
+int64_t mf_grid_edt_scratch_bytes(int64_t gx, int64_t gy, int64_t gz);
+int32_t mf_grid_edt(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, const int32_t* w /* host */, int32_t R,
+                    int32_t* d2_out, uint32_t* bits_out, int64_t* count_out, void* scratch, void* stream);
 
 /* ---- sparse lattice queries: sigma only where a bit grid is occupied.  visualize_mesh (trainer_moco_flow.py:490-538,
  * trainer_nerf.py:200-259) evaluates every point of its lattice, and so does the lattice behind mf_occ_build; a body fills about a

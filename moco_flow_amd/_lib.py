@@ -258,6 +258,8 @@ SYMBOLS = {
     "mf_voxel_fill": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     "mf_voxel_dilate_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_voxel_dilate": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
+    "mf_grid_edt_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mf_grid_edt": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _fp, _fp, _fp, _fp, _fp]),
     "mf_lattice_select_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_lattice_select": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int64,
                                       C.POINTER(C.c_int32), _fp, _fp, _fp, _fp, _fp]),

@@ -4,7 +4,8 @@ The reference renders every ray inside the hull of the projected AABB (MoCoFlowT
 from the nearest to the farthest AABB corner (Camera.make_rays, utils/camera.py:134-148; rendering.py:239-249 spreads the
 coarse samples over that whole interval).  A body fills a fraction of the hull and of the interval.  An ``OccupancyGrid`` is
 one bit per cell of a lattice over the AABB, built from ONE ``query_sigma`` call at a frame's image index -- or, without any
-network, from the frame's posed SMPL mesh (``from_mesh`` / ``from_smpl``: mf_voxel_mesh, mf_voxel_fill, mf_voxel_dilate); ``clip_rays``
+network, from the frame's posed SMPL mesh (``from_mesh`` / ``from_smpl``: mf_voxel_mesh, mf_voxel_fill, mf_voxel_dilate,
+mf_grid_edt for the exact Euclidean shell and the grid's squared-distance field); ``clip_rays``
 marches rays through it, ``cull`` turns the result into a ray table, and ``image.render_image(..., occupancy=grid)`` renders
 only the rays that hit.  A grid belongs to one frame index: it serves that frame's overfit view, its novel view and every
 view of its orbit.  Opt-in: nothing changes for a caller that passes no grid."""
@@ -21,6 +22,8 @@ __all__ = ["OccupancyGrid"]
 
 _ACT = {"relu": L.MF_ACT_RELU, "softplus": L.MF_ACT_SOFTPLUS}
 _TIGHTEN = ("none", "near", "both")
+_SHELLS = ("box", "euclidean")
+_EDT_ONE = 65536                                  # the integer weight of the longest cell edge (mf_grid_edt)
 
 
 def _f3(v):
@@ -202,7 +205,7 @@ class OccupancyGrid:
     # ---- grids from a mesh (csrc/mf_voxelize.hip) -----------------------------------------------------------------------------
 
     @classmethod
-    def from_mesh(cls, verts, tris, aabb, dims=128, dilate=1, thickness=0.0, solid=True, return_dropped=False):
+    def from_mesh(cls, verts, tris, aabb, dims=128, dilate=1, thickness=0.0, solid=True, return_dropped=False, shell="box"):
         """The grid of a triangle mesh -- ``verts`` (V, 3) fp32 and ``tris`` (T, 3) int64 on a 'cuda' device -- over ``aabb``
         ((2, 3): min and max corner, as ``from_field`` takes it) in ``dims`` cells (an int or (Gx, Gy, Gz), each 1 .. 1024).
         Three steps, in this order, every one decided in integers and so bit-identical from run to run:
@@ -230,7 +233,20 @@ class OccupancyGrid:
         (b) The true surface lies within 1/128 cell of the snapped one along every axis, hence ``dilate >= 1`` covers it and
             meets the ``dilate >= 1`` premise of ``clip_rays``' guarantee.
         (c) What reaches beyond the SMPL shell by more than ``thickness`` is CULLED -- loose clothing and hair are the likely
-            cases.  Check a few frames against an unculled render; no thickness has been validated on a trained checkpoint."""
+            cases.  Check a few frames against an unculled render; no thickness has been validated on a trained checkpoint.
+
+        ``shell="euclidean"`` (the default "box" is step 3 above, unchanged; any other string raises) replaces step 3 by
+        ``dilated_euclidean(thickness)`` (mf_grid_edt: the cells within ``thickness`` of a set cell's index, in the integer
+        metric of ``euclid_metric``) followed by the box dilation ``dilated(dilate_a + 1)``.  Guarantee (a) holds as it does
+        for the box: with ``dilate >= 1``, every point of the box within ``thickness`` of a point of a cell set before the
+        dilation falls in a set cell.  Two cells k apart leave a gap of max(|k_a| - 1, 0) cell_a along axis a between their
+        points, so the cells that hold a point within t of a set cell are the ball of that gap metric, which is E(t) + box(1):
+        the ellipsoid of index offsets with sum (k_a cell_a)^2 <= t^2 -- ``euclid_metric`` rounds it outwards -- grown by one
+        cell per axis; ``dilate`` then absorbs the fp32 rounding of u and the 1/64 snapping as in (a).  (b) and ``clip_rays``'
+        premise hold as before, and (c) applies unchanged.  The Euclidean shell is NOT a subset of the box shell in general:
+        along axis a alone it reaches r_a + dilate_a + 1 cells against the box's dilate_a + ceil(thickness / cell_a), which is
+        one cell more when thickness / cell_a is a whole number; away from the axes it is thinner (a box shell is sqrt(3)
+        times too thick along its diagonal)."""
         L.require_gpu(verts, "OccupancyGrid.from_mesh")
         L.require_gpu(tris, "OccupancyGrid.from_mesh")
         if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
@@ -247,6 +263,8 @@ class OccupancyGrid:
         thickness = float(thickness)
         if not (0.0 <= thickness < math.inf):
             raise RuntimeError(f"OccupancyGrid.from_mesh: thickness={thickness} must be finite and >= 0")
+        if shell not in _SHELLS:
+            raise RuntimeError(f"OccupancyGrid.from_mesh: shell {shell!r} (box | euclidean)")
         dev = verts.device
         v, t = verts.detach().contiguous(), tris.detach().contiguous()
         bits = torch.empty((dims[0], dims[1], (dims[2] + 31) // 32), dtype=torch.int32, device=dev)
@@ -256,8 +274,11 @@ class OccupancyGrid:
         L.launch(dev, "mf_voxel_mesh", L.ptr0(v), V, L.ptr0(t), T, *dims, _f3(surface.lo), _f3(surface.hi), _f3(surface.inv_cell),
                  bits.data_ptr(), L.ptr(dropped))
         grid = surface.filled() if solid else surface
-        radii = tuple(dilate[a] + int(math.ceil(thickness / float(surface.cell[a]))) for a in range(3))
-        grid = grid.dilated(radii)
+        if shell == "euclidean":
+            grid = grid.dilated_euclidean(thickness).dilated(tuple(d + 1 for d in dilate))
+        else:
+            radii = tuple(dilate[a] + int(math.ceil(thickness / float(surface.cell[a]))) for a in range(3))
+            grid = grid.dilated(radii)
         return (grid, int(dropped.item())) if return_dropped else grid
 
     @classmethod
@@ -294,6 +315,62 @@ class OccupancyGrid:
         out = torch.empty_like(src)
         count = torch.empty(1, dtype=torch.int64, device=dev)
         L.launch(dev, "mf_voxel_dilate", src.data_ptr(), *self.dims, *radii, out.data_ptr(), count.data_ptr(), scratch.data_ptr())
+        return OccupancyGrid(out, self.dims, self.lo, self.hi, count)
+
+    # ---- the Euclidean shell and the distance field (csrc/mf_distance.hip) ------------------------------------------------------
+
+    @staticmethod
+    def euclid_metric(cell, radius):
+        """The integer metric of mf_grid_edt for float64 cell edges ``cell`` (3,) and a world ``radius`` >= 0 -> (w, R, r), all
+        Python ints from float64 arithmetic on the host: with cmax = cell.max(), w_a = floor(65536 (cell_a / cmax)^2) in
+        [1, 65536] (below 1 raises), R = ceil(65536 (radius / cmax)^2) (R >= 2^30, i.e. radius >= 128 cmax, raises) and
+        r_a = isqrt(R // w_a), the reach in cells along axis a.  The floor and the ceil keep {sum w_a k_a^2 <= R} a superset
+        of the real-valued ellipsoid {sum (k_a cell_a)^2 <= radius^2}; cubic cells give w = 65536 on every axis."""
+        c = np.asarray(cell, dtype=np.float64).reshape(-1)
+        radius = float(radius)
+        if c.shape != (3,) or not (np.isfinite(c).all() and (c > 0).all()):
+            raise RuntimeError(f"OccupancyGrid.euclid_metric: cell must be three finite edges > 0, got {cell!r}")
+        if not (0.0 <= radius < math.inf):
+            raise RuntimeError(f"OccupancyGrid.euclid_metric: radius={radius} must be finite and >= 0")
+        cmax = float(c.max())
+        ratios = [float(x) / cmax for x in c]
+        w = tuple(int(math.floor(_EDT_ONE * (q * q))) for q in ratios)
+        if min(w) < 1:
+            raise RuntimeError(f"OccupancyGrid.euclid_metric: cell edges {c.tolist()} differ by more than a factor of 256")
+        q = radius / cmax
+        big = _EDT_ONE * (q * q)
+        if not big < float(1 << 30) or int(math.ceil(big)) >= 1 << 30:
+            raise RuntimeError(f"OccupancyGrid.euclid_metric: radius={radius} is not below 128 times the longest cell edge {cmax}")
+        R = int(math.ceil(big))
+        return w, R, tuple(math.isqrt(R // x) for x in w)
+
+    def _edt(self, radius, want_d2, want_bits):
+        w, R, _ = self.euclid_metric(self.cell, radius)
+        dev = self.device
+        scratch = L.scratch(dev, "mf_grid_edt_scratch_bytes", *self.dims)
+        src = self.bits.contiguous()
+        d2 = torch.empty(self.dims, dtype=torch.int32, device=dev) if want_d2 else None
+        out = torch.empty_like(src) if want_bits else None
+        count = torch.empty(1, dtype=torch.int64, device=dev) if want_bits else None
+        L.launch(dev, "mf_grid_edt", src.data_ptr(), *self.dims, (C.c_int32 * 3)(*w), R, L.ptr(d2), L.ptr(out), L.ptr(count),
+                 scratch.data_ptr())
+        return d2, out, count, w, R
+
+    def squared_distance(self, radius):
+        """(d2, w, R): ``d2`` int32 (Gx, Gy, Gz) on the grid's device, the squared distance of every cell's index to the nearest
+        set cell's in the metric ``euclid_metric(self.cell, radius)`` = (w, R, r), capped: d2 = min(R + 1, min over set cells
+        of sum w_a k_a^2); an empty grid gives R + 1 everywhere.  The world distance between the two cells' centres is
+        cmax * sqrt(d2 / 65536) with cmax = ``cell.max()`` -- exactly Euclidean for cubic cells, rounded down by the floor of
+        w otherwise -- wherever d2 <= R; ``d2 <= R2`` for any R2 <= R re-thresholds at a smaller radius without voxelising
+        again.  Each side at most 1024 cells.  No synchronisation."""
+        d2, _, _, w, R = self._edt(radius, True, False)
+        return d2, w, R
+
+    def dilated_euclidean(self, radius):
+        """A new grid over the same box: the cells with ``squared_distance(radius)`` <= R, i.e. within ``radius`` (world units)
+        of a set cell, index to index, in the outward-rounded integer metric of ``euclid_metric`` (mf_grid_edt).  ``radius`` 0
+        returns the same cells.  Each side at most 1024 cells.  No synchronisation; the new grid carries its count."""
+        _, out, count, _, _ = self._edt(radius, False, True)
         return OccupancyGrid(out, self.dims, self.lo, self.hi, count)
 
     def _same_grid(self, other, what):
