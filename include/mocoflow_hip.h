@@ -55,7 +55,8 @@ extern "C" {
  *     mf_simplify_mesh_plan / mf_simplify_mesh_emit (+ mf_simplify_mesh_scratch_bytes); mf_rings_mesh_plan / mf_rings_mesh_emit
  *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes); mf_voxel_mesh, mf_voxel_fill
  *     (+ mf_voxel_fill_scratch_bytes), mf_voxel_dilate (+ mf_voxel_dilate_scratch_bytes); mf_grid_edt
- *     (+ mf_grid_edt_scratch_bytes) */
+ *     (+ mf_grid_edt_scratch_bytes); mf_surface_records, mf_surface_closest, mf_surface_weights, mf_surface_sample, mf_surface_stats
+ *     (+ mf_surface_stats_scratch_bytes) */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -1053,6 +1054,75 @@ int32_t mf_voxel_dilate(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz
 int64_t mf_grid_edt_scratch_bytes(int64_t gx, int64_t gy, int64_t gz);
 int32_t mf_grid_edt(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, const int32_t* w /* host */, int32_t R,
                     int32_t* d2_out, uint32_t* bits_out, int64_t* count_out, void* scratch, void* stream);
+
+/* ---- mesh-to-mesh distances: closest points on a triangle mesh, area-weighted surface samples and their statistics
+ * (csrc/mf_mesh_distance.hip).  The reference has no such measure: it validates a `thickness` around the SMPL surface
+ * by eye (datasets/moco_flow_dataset.py:101-132) and reports no geometry metric.  THE CONTRACT IS FIXED ARITHMETIC: every fp32
+ * operation is rounded once, in the order written, without FMA, and dot(x, y) = (x0 y0 + x1 y1) + x2 y2; max / min ignore a NaN
+ * operand (fmaxf / fminf).  tests/mesh_distance_oracle.py restates every output in np.float32.  No float atomics; every result
+ * is bit-identical from run to run and independent of every order and launch shape below.  Nothing allocates or synchronises.
+ *
+ * mf_surface_records: verts (V, 3) fp32, tris (T, 3) int64, order (T) int32 or NULL (identity): slot s holds triangle order[s].
+ * With a, b, c the triangle's vertices, ab = b - a, ac = c - a, bc = c - b, n = ab x ac (each component x y - z w: two rounded
+ * products, one difference):
+ *   records (Tp, 16)   a, ab, ac, r_ab = 1 / dot(ab, ab), r_ac = 1 / dot(ac, ac), r_bc = 1 / dot(bc, bc), d00 = dot(ab, ab),
+ *                      d01 = dot(ab, ac), d11 = dot(ac, ac), rden = 1 / (d00 d11 - d01 d01); Tp = T rounded up to 64
+ *   edges (Tp, 12)     b (the vertex as read), bc, and the triangle's exact min / max box lo, hi
+ *   slot_tri (Tp)      int32: the caller's index of the slot's triangle, -1 for a slot without one (these never win)
+ *   tile_box (Tp / 64, 8)   per tile of 64 slots: min lo, max hi over its kept slots (+inf / -inf for none), their number, 0
+ *   tri_slot (T) int32 the slot of triangle t or -1; area2 (T) = sqrtf(dot(n, n)); normal (T, 3) = n (1 / area2);
+ *   dropped (T) uint8; dropped_count (device int64[1])
+ * A triangle is DROPPED -- never a candidate, never sampled, area2 = normal = 0 -- when an index lies outside [0, V) (tested
+ * before an address is formed), when dot(n, n) is zero or not finite, when one of the 16 record fields is not finite, or when
+ * no slot holds it: an entry of order outside [0, T) leaves its slot empty, and of equal entries the lowest slot keeps the
+ * triangle (an integer atomic minimum), so a bad order cannot fault.  Every slot is written.
+ *
+ * mf_surface_closest: query (Q, 3).  The value of a kept triangle at q is max(m, lb(q, lo, hi)) (lb > m ? lb : m), m the least, in
+ * the order ab, ac, bc, face under strict < (the first minimum wins, a NaN never does), of dot(q - P, q - P) over
+ *   edge ab  P = a + ab t, t = min(max(dot(q - a, ab) r_ab, 0), 1);   edge ac  the same with ac, r_ac
+ *   edge bc  P = b + bc t, t = min(max(dot(q - b, bc) r_bc, 0), 1)
+ *   face     d20 = dot(q - a, ab), d21 = dot(q - a, ac), v = min(max((d11 d20 - d01 d21) rden, 0), 1),
+ *            w = min(max((d00 d21 - d01 d20) rden, 0), 1 - v), P = (a + ab v) + ac w
+ * and lb(q, lo, hi) = dot(g, g), g = max(max(lo - q, q - hi), 0) per axis.  Per query: the lexicographic minimum of (value,
+ * caller's index) over the kept triangles -> d2 (Q), tri (Q) int32, point (Q, 3) = the winning candidate's P, region (Q) uint8
+ * (0 ab, 1 ac, 2 bc, 3 face; optional).  No kept triangle, or no value below +inf and no kept triangle at +inf: d2 = +inf,
+ * tri = -1, point = 0, region = 0.  One query per lane; lane l of wave w takes row qorder[64 w + l] (int32 (Q) or NULL: identity;
+ * an entry outside [0, Q) is skipped, a repeated one leaves another row unwritten -- the caller passes a permutation).  Wave w
+ * visits the tiles start[w], +1, -1, +2, ... (int32 (ceil(Q / 64)) or NULL: 0; clamped).  mode: 0 = evaluate every tile,
+ * 1 = skip a tile when it holds no kept slot or when lb(q, tile box) > best fails to be <= on EVERY lane of the wave (one ballot:
+ * the wave-uniform decision).  Every operation of lb is monotone under rounding, so lb of a containing box <= lb of the
+ * triangle's own box <= the value, in fp32: the skip needs no slack and both modes give the same bits.  A tile's records are read at
+ * wave-uniform addresses (scalar loads).
+ * visited (ceil(Q / 64)) int32, optional: the tiles wave w evaluated.  Q = 0 launches nothing.
+ *
+ * mf_surface_weights: weights (T) int64 = 0 for a dropped triangle, else max(1, (int64) floorf(area2 (1048576.f / amax[0]))), capped
+ * at 2^22; amax: device fp32[1], the largest area2.  The caller takes their running sum `cum` (integers: exact in any order).
+ * mf_surface_sample: r (n) int64, masked to [0, 2^53); u (n, 2) fp32 in [0, 1).  total = cum[T - 1]; target = floor(r total / 2^53)
+ * by the 128-bit product; tri = the first t with cum[t] > target; s = sqrtf(u0), b0 = 1 - s, b1 = s (1 - u1), b2 = s u1;
+ * point = (a b0 + b b1) + c b2.  total = 0, or a triangle whose indices lie outside [0, V): tri = -1, point = 0.
+ *
+ * mf_surface_stats: d2 (n) and optionally tri_src, tri_dst (n) int32 with the normal tables (T_src, 3), (T_dst, 3).  A row with a
+ * negative tri_src or tri_dst is LEFT OUT; a row whose d2 is not in [0, +inf) is skipped; over the rest, d = sqrtf(d2):
+ *   out_f64 (device, 4)  = [sum d, sum d d, max d, sum |dot(n_src[tri_src], n_dst[tri_dst])|] (the last needs all four; |.| in fp32)
+ *   out_i64 (device, 10) = [rows with d <= thresholds[k], k < 8 (host fp32, n_thresholds <= 8; 0 beyond), finite rows, rows left out]
+ * Sums in float64 through the fixed-order reduction (csrc/mf_reduce.hpp): per-workgroup partials in scratch
+ * (mf_surface_stats_scratch_bytes(n) bytes), gathered by one workgroup.  n = 0 writes zeros.
+ *
+ * Every count (V, T, Q, n) in [0, 2^31 - 1), a NULL that is needed, a mode outside 0 .. 1 and an output that is an input are
+ * MF_E_INVALID with an mf_last_error text, settled before any launch. ---- */
+int32_t mf_surface_records(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int32_t* order, float* records,
+                        float* edges, int32_t* slot_tri, float* tile_box, int32_t* tri_slot, float* area2, float* normal,
+                        uint8_t* dropped, int64_t* dropped_count, void* stream);
+int32_t mf_surface_closest(const float* records, const float* edges, const int32_t* slot_tri, const float* tile_box, int64_t T,
+                        const float* query, int64_t Q, const int32_t* qorder, const int32_t* start, int32_t mode, float* d2,
+                        int32_t* tri, float* point, uint8_t* region, int32_t* visited, void* stream);
+int32_t mf_surface_weights(const float* area2, const uint8_t* dropped, int64_t T, const float* amax, int64_t* weights, void* stream);
+int32_t mf_surface_sample(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int64_t* cum, const int64_t* r,
+                       const float* u, int64_t n, float* points, int32_t* tri, void* stream);
+int64_t mf_surface_stats_scratch_bytes(int64_t n);
+int32_t mf_surface_stats(const float* d2, int64_t n, const int32_t* tri_src, const int32_t* tri_dst, const float* normal_src,
+                         int64_t T_src, const float* normal_dst, int64_t T_dst, const float* thresholds /* host */,
+                         int32_t n_thresholds, double* out_f64, int64_t* out_i64, void* scratch, void* stream);
 
 /* ---- sparse lattice queries: sigma only where a bit grid is occupied.  visualize_mesh (trainer_moco_flow.py:490-538,
  * trainer_nerf.py:200-259) evaluates every point of its lattice, and so does the lattice behind mf_occ_build; a body fills about a

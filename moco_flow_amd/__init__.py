@@ -21,7 +21,8 @@ from .nerf import NeRF
 from .nof import NoF
 from .points import query_radiance, query_sigma, query_sigma_lattice
 from .mesh import (export_obj, export_ply, extract_colored_mesh, extract_mesh, filter_components, marching_cubes, mesh_components,
-                   simplify_mesh, smooth_mesh, vertex_normals, vertex_rings)
+                   simplify_mesh, smooth_mesh, vertex_normals, vertex_rings, MeshIndex, closest_point, sample_surface,
+                   surface_distance, surface_stats)
 from . import metrics
 from .metrics import image_metrics
 from . import vis
@@ -46,4 +47,5 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "supervision", "Correspondence", "correspondence", "point_correspond", "point_losses",
            "occupancy", "OccupancyGrid", "query_sigma_lattice",
            "raster", "project_vertices", "rasterize", "interpolate", "render_mesh", "smpl_views",
-           "frames", "resize", "composite", "to_rows", "background_plate", "clean_mask", "mask_regions", "Regions"]
+           "frames", "resize", "composite", "to_rows", "background_plate", "clean_mask", "mask_regions", "Regions",
+           "MeshIndex", "closest_point", "sample_surface", "surface_distance", "surface_stats"]

@@ -5,6 +5,7 @@
 //   mf_occupancy.hip  occ_build_kernel / occ_count_finish_kernel               1 slot (count_finish)
 //   mf_voxelize.hip   voxel_dilate_rows_kernel / voxel_count_finish_kernel     1 slot (count_finish)
 //   mf_distance.hip   edt_x_kernel / edt_count_finish_kernel                   1 slot (count_finish)
+//   mf_mesh_distance.hip  md_stats_kernel / md_stats_finish_kernel            13 slots
 // THE CONTRACT IS THE ORDER OF THE ADDITIONS; "two runs are bit-identical, no atomics"  rests on it:
 //   a thread      adds its own elements (or, in a finish, the partial rows t, t + THREADS, t + 2 THREADS, ...) in ascending order
 //   wave_sum_d    adds the 64 lanes of a wave in the fixed tree below

@@ -1,7 +1,7 @@
 // mf_shares.hpp -- how a launch divides its input and its scratch buffer, written once.  Plain C++: no HIP include, a host
 // compiler alone builds it (tests/test_host_cpu.py does, under the sanitizers).  Users: mf_batch.hip (mf_mask_compact),
 // mf_regions.hip, mf_mesh_simplify.hip, mf_mesh_smooth.hip (share_of, Carver), mf_mesh_components.hip, mf_mesh.hip,
-// mf_voxelize.hip, mf_distance.hip (Carver); mf_host.hpp (kIndexLimit, align_up).  The device side of a share is mf_scan.hpp's share_range.
+// mf_voxelize.hip, mf_distance.hip, mf_mesh_distance.hip (Carver); mf_host.hpp (kIndexLimit, align_up).  The device side of a share is mf_scan.hpp's share_range.
 #pragma once
 #include <cstdint>
 

@@ -5,7 +5,8 @@ without the volume leaving the device -- and what a coloured mesh adds: vertex n
 clean-up that follows an isosurface at a fixed threshold: connected components (mf_mesh_label, mf_mesh_table_*) and the
 filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device; the
 reduction of the triangle count by vertex clustering (simplify_mesh: mf_simplify_mesh_*); and vertex adjacency with the
-smoothing built on it (vertex_rings: mf_rings_mesh_*, smooth_mesh: mf_smooth_mesh)."""
+smoothing built on it (vertex_rings: mf_rings_mesh_*, smooth_mesh: mf_smooth_mesh); and how far two meshes are apart
+(MeshIndex, closest_point, sample_surface, surface_distance: mf_surface_*)."""
 import ctypes as C
 import math
 
@@ -628,3 +629,215 @@ def export_obj(path, verts, tris):
             fh.write("\n".join("v %.9g %.9g %.9g" % tuple(r) for r in v) + "\n")
         if len(f):
             fh.write("\n".join("f %d %d %d" % tuple(r) for r in (f.astype(np.int64) + 1)) + "\n")
+
+
+# ---- mesh-to-mesh distances (csrc/mf_mesh_distance.hip; include/mocoflow_hip.h "mesh-to-mesh distances") ----
+_MD_TILE = 64
+_MD_MODES = {"sweep": 0, "cull": 1}
+
+
+def _morton(points, lo, hi):
+    """30-bit Morton codes (int64) of (N, 3) points, 10 bits per axis over the box [lo, hi], clamped into it.  Plumbing: the
+    codes order the slots and the queries and pick a wave's first tile; no result depends on them."""
+    ext = (hi - lo).clamp_min(torch.finfo(torch.float32).tiny)
+    c = ((points - lo) / ext * 1024.0).nan_to_num(0.0, 0.0, 0.0).clamp(0.0, 1023.0).to(torch.int64)
+
+    def spread(x):
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        return (x | (x << 2)) & 0x09249249
+    return (spread(c[:, 0]) << 2) | (spread(c[:, 1]) << 1) | spread(c[:, 2])
+
+
+class MeshIndex:
+    """What closest_point, sample_surface and surface_distance need of a mesh, built once: verts (V, 3) float32 and tris (T, 3)
+    int64 on a 'cuda' device.  ``order``: which triangle each slot of the search holds -- "morton" (triangle centroids quantised
+    to 10 bits per axis over the mesh box, bits interleaved, a stable sort), "identity", or an int32 (T,) tensor.  The order is
+    plumbing: no result depends on it (an entry outside [0, T) or a repeated one only drops triangles, and is counted).
+
+    records (Tp, 16), edges (Tp, 12), slot_tri (Tp,), tile_box (Tp / 64, 8), tri_slot (T,), area2 (T,), normal (T, 3),
+    dropped (T,) uint8, ``dropped_count`` (device int64 scalar), weights / cum (T,) int64: as include/mocoflow_hip.h defines them.
+    A dropped triangle (an index outside [0, V), no area, a record field that is not finite) is never returned and never sampled.
+    Nothing is read back from the device."""
+
+    def __init__(self, verts, tris, order="morton"):
+        _check_tris(tris, "MeshIndex")
+        if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+            raise RuntimeError(f"MeshIndex: verts must be (V, 3) float32, got {tuple(verts.shape)} {verts.dtype}")
+        L.require_gpu(verts, "MeshIndex")
+        L.require_gpu(tris, "MeshIndex")
+        dev = verts.device
+        self.verts, self.tris = verts.detach().contiguous(), tris.detach().contiguous()
+        V, T = self.verts.shape[0], self.tris.shape[0]
+        Tp = (T + _MD_TILE - 1) // _MD_TILE * _MD_TILE
+        self.V, self.T, self.n_tiles, self.device = V, T, Tp // _MD_TILE, dev
+        if T and V:
+            cen = self.verts[self.tris.clamp(0, V - 1)].mean(1).nan_to_num(0.0, 0.0, 0.0)
+            self.lo, self.hi = cen.amin(0), cen.amax(0)
+            codes = _morton(cen, self.lo, self.hi)
+        else:
+            self.lo, self.hi = torch.zeros(3, device=dev), torch.ones(3, device=dev)
+            codes = torch.zeros(T, dtype=torch.int64, device=dev)
+        if isinstance(order, str):
+            if order not in ("morton", "identity"):
+                raise ValueError(f"MeshIndex: order is 'morton', 'identity' or an int32 tensor, got {order!r}")
+            self.order = torch.sort(codes, stable=True)[1].to(torch.int32) if order == "morton" and T else None
+        else:
+            L.require_gpu(order, "MeshIndex")
+            if order.dtype != torch.int32 or order.shape != (T,):
+                raise RuntimeError(f"MeshIndex: order must be int32 ({T},), got {order.dtype} {tuple(order.shape)}")
+            self.order = order.contiguous()
+        slot_codes = codes if self.order is None else codes[self.order.long().clamp(0, max(T - 1, 0))]
+        self.tile_codes = slot_codes[::_MD_TILE].contiguous()                # ascending under "morton"
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.records, self.edges = torch.empty((Tp, 16), **f32), torch.empty((Tp, 12), **f32)
+        self.slot_tri = torch.empty(Tp, dtype=torch.int32, device=dev)
+        self.tile_box = torch.empty((self.n_tiles, 8), **f32)
+        self.tri_slot = torch.empty(T, dtype=torch.int32, device=dev)
+        self.area2, self.normal = torch.empty(T, **f32), torch.empty((T, 3), **f32)
+        self.dropped = torch.empty(T, dtype=torch.uint8, device=dev)
+        self.dropped_count = torch.empty((), dtype=torch.int64, device=dev)
+        self.weights = torch.empty(T, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            L.enqueue(dev, "mf_surface_records", L.ptr0(self.verts), V, L.ptr0(self.tris), T, L.ptr0(self.order), L.ptr0(self.records),
+                      L.ptr0(self.edges), L.ptr0(self.slot_tri), L.ptr0(self.tile_box), L.ptr0(self.tri_slot), L.ptr0(self.area2),
+                      L.ptr0(self.normal), L.ptr0(self.dropped), self.dropped_count.data_ptr())
+            if T:
+                self.amax = self.area2.amax().reshape(1)
+                L.enqueue(dev, "mf_surface_weights", self.area2.data_ptr(), self.dropped.data_ptr(), T, self.amax.data_ptr(),
+                          self.weights.data_ptr())
+        self.cum = torch.cumsum(self.weights, 0)                            # integers: exact in any order
+
+
+def _as_index(mesh, what):
+    if isinstance(mesh, MeshIndex):
+        return mesh
+    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        return MeshIndex(mesh[0], mesh[1])
+    raise RuntimeError(f"{what}: a mesh is a MeshIndex or a (verts, tris) pair")
+
+
+def closest_point(points, index, mode="cull", return_region=False, return_visited=False):
+    """The closest point of a mesh to each of ``points`` (Q, 3) float32 on the index's device -> (d2 (Q,) float32, tri (Q,)
+    int32 in the caller's numbering, point (Q, 3) float32[, region (Q,) uint8: 0 edge ab, 1 edge ac, 2 edge bc, 3 the face]
+    [, visited (ceil(Q / 64),) int32: the 64-triangle tiles each wave of 64 queries evaluated]).
+
+    Exact in the sense of include/mocoflow_hip.h: the lexicographic minimum of (value, triangle index) over the kept triangles,
+    the value of a triangle being the least of four clamped candidates raised to the distance to its box, every operation
+    rounded once.  ``mode="cull"`` skips tiles by their boxes, ``"sweep"`` evaluates every one; both give the same bits, as do
+    every ``order`` of the index and every order of the queries.  The queries are visited in Morton order and each wave starts
+    at the tile whose code is nearest its first query's.  No triangle kept: d2 = +inf, tri = -1, point = 0.  No host read."""
+    if not isinstance(index, MeshIndex):
+        raise RuntimeError("closest_point: index must be a MeshIndex")
+    if mode not in _MD_MODES:
+        raise ValueError(f"closest_point: mode is 'cull' or 'sweep', got {mode!r}")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise RuntimeError(f"closest_point: points must be (Q, 3) float32, got {tuple(points.shape)} {points.dtype}")
+    L.require_gpu(points, "closest_point")
+    dev = index.device
+    if points.device != dev:
+        raise RuntimeError(f"closest_point: points on {points.device}, the index on {dev}")
+    q = points.detach().contiguous()
+    Q = q.shape[0]
+    n_waves = (Q + 63) // 64
+    d2 = torch.empty(Q, dtype=torch.float32, device=dev)
+    tri = torch.empty(Q, dtype=torch.int32, device=dev)
+    point = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+    region = torch.empty(Q, dtype=torch.uint8, device=dev) if return_region else None
+    visited = torch.empty(n_waves, dtype=torch.int32, device=dev) if return_visited else None
+    if Q:
+        codes, qorder = torch.sort(_morton(q, index.lo, index.hi), stable=True)
+        qorder = qorder.to(torch.int32)
+        start = None
+        if index.n_tiles:
+            start = (torch.searchsorted(index.tile_codes, codes[::64].contiguous(), right=True) - 1).clamp(0, index.n_tiles - 1).to(torch.int32)
+        L.launch(dev, "mf_surface_closest", L.ptr0(index.records), L.ptr0(index.edges), L.ptr0(index.slot_tri), L.ptr0(index.tile_box),
+                 index.T, q.data_ptr(), Q, qorder.data_ptr(), L.ptr0(start), _MD_MODES[mode], d2.data_ptr(),
+                 tri.data_ptr(), point.data_ptr(), L.ptr0(region), L.ptr0(visited))
+    out = (d2, tri, point)
+    if return_region:
+        out += (region,)
+    if return_visited:
+        out += (visited,)
+    return out
+
+
+def sample_surface(index, n, generator=None, draws=None):
+    """``n`` points on the surface of the index's mesh, area-weighted: (points (n, 3) float32, tri (n,) int32).  A kept triangle
+    has the integer weight max(1, floor(2^20 area / the largest area)), a dropped one 0; a draw r (int64 in [0, 2^53)) picks the
+    first triangle whose running weight exceeds floor(r total / 2^53), and u (2 floats in [0, 1)) the point
+    (a (1 - s) + b s (1 - u1)) + c s u1 with s = sqrt(u0).  ``draws=(r (n,), u (n, 2))`` injects them; otherwise torch draws them
+    on the device (``generator``: a generator of that device).  No triangle kept: tri = -1, points = 0.  No host read."""
+    if not isinstance(index, MeshIndex):
+        raise RuntimeError("sample_surface: index must be a MeshIndex")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"sample_surface: n={n}")
+    dev = index.device
+    if draws is None:
+        r = torch.randint(0, 1 << 53, (n,), dtype=torch.int64, device=dev, generator=generator)
+        u = torch.rand((n, 2), dtype=torch.float32, device=dev, generator=generator)
+    else:
+        r, u = draws
+        L.require_gpu(r, "sample_surface")
+        L.require_gpu(u, "sample_surface")
+        if r.dtype != torch.int64 or r.shape != (n,) or u.dtype != torch.float32 or u.shape != (n, 2):
+            raise RuntimeError(f"sample_surface: draws are (r int64 ({n},), u float32 ({n}, 2))")
+        r, u = r.contiguous(), u.contiguous()
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    tri = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        L.launch(dev, "mf_surface_sample", L.ptr0(index.verts), index.V, L.ptr0(index.tris), index.T, L.ptr0(index.cum), r.data_ptr(),
+                 u.data_ptr(), n, points.data_ptr(), tri.data_ptr())
+    return points, tri
+
+
+def surface_stats(d2, thresholds=(), tri_src=None, tri_dst=None, normal_src=None, normal_dst=None):
+    """The fused statistics of one direction: d2 (n,) float32 -> (f64 (4,) = [sum d, sum d^2, max d, sum |n_src . n_dst|],
+    i64 (10,) = [rows with d <= thresholds[k] (k < 8), finite rows, rows left out]) on the device; d = sqrt(d2) in float32, sums
+    in float64 in a fixed order (identical from run to run).  A row with a negative tri_src / tri_dst is left out and counted."""
+    L.require_gpu(d2, "surface_stats")
+    thresholds = tuple(float(t) for t in thresholds)
+    if len(thresholds) > 8:
+        raise ValueError(f"surface_stats: at most 8 thresholds, got {len(thresholds)}")
+    dev, n = d2.device, d2.shape[0]
+    d2 = d2.detach().contiguous()
+    f64 = torch.empty(4, dtype=torch.float64, device=dev)
+    i64 = torch.empty(10, dtype=torch.int64, device=dev)
+    scratch = L.scratch(dev, "mf_surface_stats_scratch_bytes", n)
+    tau = (C.c_float * 8)(*thresholds)
+    L.launch(dev, "mf_surface_stats", L.ptr0(d2), n, L.ptr0(tri_src), L.ptr0(tri_dst), L.ptr0(normal_src),
+             0 if normal_src is None else normal_src.shape[0], L.ptr0(normal_dst), 0 if normal_dst is None else normal_dst.shape[0],
+             tau, len(thresholds), f64.data_ptr(), i64.data_ptr(), scratch.data_ptr())
+    return f64, i64
+
+
+def _direction(src, dst, n, thresholds, generator, draws):
+    points, ts = sample_surface(src, n, generator, draws)
+    d2, td, _ = closest_point(points, dst)
+    f64, i64 = surface_stats(d2, thresholds, ts, td, src.normal, dst.normal)
+    k = len(thresholds)
+    finite = i64[8].to(torch.float64)
+    return dict(mean=f64[0] / finite, rms=torch.sqrt(f64[1] / finite), max=f64[2], within=i64[:k], normal_consistency=f64[3] / finite,
+                finite=i64[8], left_out=i64[9], d=torch.sqrt(d2), sums=f64)
+
+
+def surface_distance(mesh_a, mesh_b, n=100_000, thresholds=(), generator=None, draws=None):
+    """How far two surfaces are apart: ``n`` area-weighted samples of each mesh against the other.  A mesh is a MeshIndex or a
+    (verts, tris) pair; ``draws=((r, u), (r, u))`` injects the samples of a and of b (sample_surface).  -> a dict of device
+    tensors: ``a2b`` and ``b2a``, each a dict of mean, rms, max (of the distances of the finite rows), within[k] (rows with
+    d <= thresholds[k], int64), normal_consistency (the mean |n_src . n_dst| of the two face normals), finite, left_out (int64),
+    d (n,) the distances and sums (the raw float64 sums); ``chamfer`` = (mean_a2b + mean_b2a) / 2; ``fscore[k]`` = 2 P R / (P + R)
+    with P = within_a2b[k] / finite_a2b and R = within_b2a[k] / finite_b2a (0 where P + R = 0).  Means of no finite row are NaN.
+    No host read."""
+    a, b = _as_index(mesh_a, "surface_distance"), _as_index(mesh_b, "surface_distance")
+    if a.device != b.device:
+        raise RuntimeError(f"surface_distance: meshes on {a.device} and {b.device}")
+    thresholds = tuple(float(t) for t in thresholds)
+    da, db = (None, None) if draws is None else draws
+    ab = _direction(a, b, n, thresholds, generator, da)
+    ba = _direction(b, a, n, thresholds, generator, db)
+    P, R = ab["within"].to(torch.float64) / ab["finite"], ba["within"].to(torch.float64) / ba["finite"]
+    fscore = torch.where(P + R > 0, 2 * P * R / (P + R), torch.zeros_like(P))
+    return dict(a2b=ab, b2a=ba, chamfer=(ab["mean"] + ba["mean"]) / 2, fscore=fscore)
