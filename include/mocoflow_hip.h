@@ -56,7 +56,7 @@ extern "C" {
  *     (+ mf_rings_mesh_scratch_bytes), mf_smooth_mesh (+ mf_smooth_mesh_scratch_bytes); mf_voxel_mesh, mf_voxel_fill
  *     (+ mf_voxel_fill_scratch_bytes), mf_voxel_dilate (+ mf_voxel_dilate_scratch_bytes); mf_grid_edt
  *     (+ mf_grid_edt_scratch_bytes); mf_surface_records, mf_surface_closest, mf_surface_weights, mf_surface_sample, mf_surface_stats
- *     (+ mf_surface_stats_scratch_bytes) */
+ *     (+ mf_surface_stats_scratch_bytes); mf_surface_corners, mf_surface_cast */
 #define MF_ABI_VERSION 16
 
 enum {
@@ -1123,6 +1123,71 @@ int64_t mf_surface_stats_scratch_bytes(int64_t n);
 int32_t mf_surface_stats(const float* d2, int64_t n, const int32_t* tri_src, const int32_t* tri_dst, const float* normal_src,
                          int64_t T_src, const float* normal_dst, int64_t T_dst, const float* thresholds /* host */,
                          int32_t n_thresholds, double* out_f64, int64_t* out_i64, void* scratch, void* stream);
+
+/* ---- ray casts against a mesh: the first hit of a ray on the triangles of an mf_surface_records index, or whether it has one
+ * (csrc/mf_mesh_rays.hip).  The reference has no ray-mesh code.  THE CONTRACT IS FIXED ARITHMETIC, as in the section
+ * above: every fp32 operation is rounded once, in the order written, without FMA; min / max are fminf / fmaxf (a NaN operand is
+ * ignored); a / b is the correctly rounded quotient.  tests/mesh_rays_oracle.py restates every output in np.float32.  No atomics;
+ * every result is bit-identical from run to run.  Nothing allocates or synchronises.
+ *
+ * mf_surface_corners: verts, tris as given to mf_surface_records and the slot_tri (Tp) it wrote -> corners (Tp, 16), 16-byte
+ * aligned: per slot the three vertices a, b, c AS READ (9 floats), the triangle's box lo, hi (6 floats, the values of
+ * edges[6 .. 11]) and a zero.  A slot with slot_tri outside [0, T), or whose triangle has an index outside [0, V) (both tested
+ * before an address is formed), gets 16 zeros.
+ *
+ * mf_surface_cast: ray i is origins + i ray_stride, dirs + i ray_stride (3 floats each; ray_stride >= 3, in floats) with the range
+ * t_min[i bound_stride] .. t_max[i bound_stride] (bound_stride >= 0; 0: one pair for every ray).  The package's (Q, 8) ray rows
+ * (o, d, near, far) are origins = rows, dirs = rows + 3, t_min = rows + 6, t_max = rows + 7 and both strides 8.
+ * Per ray (o, d, t_min, t_max): the ray is DEAD -- it hits nothing -- if a component of o or d is not finite, if d is all zero,
+ * or if !(t_min <= t_max).  Otherwise kz = the first axis of the largest |d|, kx = (kz + 1) % 3, ky = (kx + 1) % 3, kx and ky
+ * swapped if d[kz] < 0; Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ * Per vertex p of a triangle, exactly as read from verts: q = p - o; x = q[kx] - Sx q[kz], y = q[ky] - Sy q[kz], z = Sz q[kz].
+ * (A vertex shared by two triangles gets the same three numbers in both.)
+ * Per triangle with the sheared corners A, B, C:
+ *   U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax (each two rounded products and one difference);  det = (U + V) + W
+ *   t_raw = ((U Az + V Bz) + W Cz) (1 / det);  t = min(max(t_raw, zmin), zmax), zmin / zmax = min / max((Az, Bz), Cz)
+ * The triangle is ACCEPTED iff (U, V, W all >= 0, or all <= 0) and det != 0 and min((Ax, Bx), Cx) <= 0 <= max((Ax, Bx), Cx) and
+ * the same in y and t_min <= t <= t_max.  Both faces count.
+ *   mode 0 (first): the lexicographic minimum of (t, caller's index) over the accepted kept triangles -> t (Q) fp32, tri (Q)
+ *     int32, bary (Q, 3) = (U, V, W) (1 / det) of the winner, recomputed from its slot: the hit is bary0 a + bary1 b + bary2 c.
+ *     A miss: t = +inf, tri = -1, bary = 0.  hit may be NULL.
+ *   mode 1 (any): hit (Q) uint8 = 1 iff some kept triangle is accepted.  t, tri, bary may be NULL.
+ * One ray per lane; lane l of wave w takes row qorder[64 w + l] (int32 (Q) or NULL: identity; an entry outside [0, Q) is
+ * skipped, a repeated one leaves another row unwritten -- the caller passes a permutation).  Wave w visits the tiles start[w],
+ * +1, -1, +2, ... (int32 (ceil(Q / 64)) or NULL: 0; clamped), as mf_surface_closest does.  cull: 0 = evaluate every tile;
+ * 1 = with the tile box translated by o (l = lo - o, h = hi - o) and
+ *   x0 = l[kx] - max(Sx l[kz], Sx h[kz]), x1 = h[kx] - min(Sx l[kz], Sx h[kz]); y0, y1 the same with ky, Sy;
+ *   z0 = min(Sz l[kz], Sz h[kz]), z1 = max(Sz l[kz], Sz h[kz])
+ * a lane WANTS the tile unless its ray is dead, or (mode 1) it has a hit already, or !(x0 <= 0 <= x1), or !(y0 <= 0 <= y1), or
+ * z1 < t_min, or z0 > t_max, or !(z0 <= best) (best: the lane's least t so far, +inf before); a tile is skipped when it holds no
+ * kept slot or no lane of the wave wants it (one ballot: the wave-uniform decision), and the wave leaves the tile loop when
+ * every lane is dead or (mode 1) has its hit.
+ *   P1  Cull equals sweep, bit for bit.  Subtracting a fixed o, multiplying by a fixed S and min / max are monotone under
+ *       rounding, so the intervals of a box that contains a vertex contain the vertex's computed x, y, z.  An accepted triangle
+ *       has 0 inside its own computed x and y ranges (a condition of acceptance) and t >= zmin >= z0, t <= zmax <= z1 (the
+ *       clamp), so its tile is wanted by every lane it could still serve.
+ *   P2  Watertight.  Neighbours see the same sheared end points of a shared edge, so its edge function in one is exactly the
+ *       negation of that in the other; and a rounded difference of two rounded products never has the sign opposite to the
+ *       exact one (rounding is monotone: a b >= c d gives fl(a b) >= fl(c d)).  So on the closed planar mesh of sheared
+ *       points, computed acceptance of the sign test contains exact acceptance; the own-range conditions hold trivially for a
+ *       triangle that exactly contains the origin.  det = 0 needs U = V = W = 0 (numbers of one sign do not cancel): a triangle
+ *       sheared to a segment or a point -- its neighbours across the edges through the origin contain the origin too -- or
+ *       one so small that all six fp32 products round to the same values; the argument does not cover the latter.
+ *   P3  Order independence: the result is a minimum over a set, so the order of the index, of the rays, the start tiles and
+ *       the launch shape cannot change it.
+ *   P4  No atomics; a dropped triangle, or a slot without one (slot_tri < 0), never wins.
+ * The corner rows and slot_tri of a tile are read at wave-uniform addresses (scalar loads); every store is a vector store.
+ * visited (ceil(Q / 64)) int32, optional: the tiles wave w evaluated.  Q = 0 launches nothing.
+ *
+ * Every count (V, T, Q) in [0, 2^31 - 1), a NULL that is needed, a mode or cull outside 0 .. 1, ray_stride < 3, bound_stride < 0,
+ * corners not 16-byte aligned and an output that is an input are MF_E_INVALID with an mf_last_error text, settled before any
+ * launch. ---- */
+int32_t mf_surface_corners(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int32_t* slot_tri, float* corners,
+                           void* stream);
+int32_t mf_surface_cast(const float* corners, const int32_t* slot_tri, const float* tile_box, int64_t T, const float* origins,
+                        const float* dirs, int64_t ray_stride, const float* t_min, const float* t_max, int64_t bound_stride,
+                        int64_t Q, const int32_t* qorder, const int32_t* start, int32_t mode, int32_t cull, float* t, int32_t* tri,
+                        float* bary, uint8_t* hit, int32_t* visited, void* stream);
 
 /* ---- sparse lattice queries: sigma only where a bit grid is occupied.  visualize_mesh (trainer_moco_flow.py:490-538,
  * trainer_nerf.py:200-259) evaluates every point of its lattice, and so does the lattice behind mf_occ_build; a body fills about a

@@ -22,7 +22,7 @@ from .nof import NoF
 from .points import query_radiance, query_sigma, query_sigma_lattice
 from .mesh import (export_obj, export_ply, extract_colored_mesh, extract_mesh, filter_components, marching_cubes, mesh_components,
                    simplify_mesh, smooth_mesh, vertex_normals, vertex_rings, MeshIndex, closest_point, sample_surface,
-                   surface_distance, surface_stats)
+                   surface_distance, surface_stats, cast_rays, visible_from)
 from . import metrics
 from .metrics import image_metrics
 from . import vis
@@ -48,4 +48,4 @@ __all__ = ["Embedding", "NeRF", "NoF", "get_model", "get_loss", "render_rays", "
            "occupancy", "OccupancyGrid", "query_sigma_lattice",
            "raster", "project_vertices", "rasterize", "interpolate", "render_mesh", "smpl_views",
            "frames", "resize", "composite", "to_rows", "background_plate", "clean_mask", "mask_regions", "Regions",
-           "MeshIndex", "closest_point", "sample_surface", "surface_distance", "surface_stats"]
+           "MeshIndex", "closest_point", "sample_surface", "surface_distance", "surface_stats", "cast_rays", "visible_from"]

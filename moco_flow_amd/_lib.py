@@ -267,6 +267,9 @@ SYMBOLS = {
     "mf_surface_stats_scratch_bytes": (C.c_int64, [C.c_int64]),
     "mf_surface_stats": (C.c_int32, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, _fp, C.c_int64, C.POINTER(C.c_float), C.c_int32,
                                      _fp, _fp, _fp, _fp]),
+    "mf_surface_corners": (C.c_int32, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp]),
+    "mf_surface_cast": (C.c_int32, [_fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp,
+                                    C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "mf_lattice_select_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mf_lattice_select": (C.c_int32, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int64,
                                       C.POINTER(C.c_int32), _fp, _fp, _fp, _fp, _fp]),

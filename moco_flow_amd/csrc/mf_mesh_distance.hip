@@ -20,6 +20,7 @@
 #pragma clang fp contract(off)
 #include <cmath>
 
+#include "mf_f3.hpp"
 #include "mf_host.hpp"
 #include "mf_reduce.hpp"
 #include "mf_scan.hpp"
@@ -38,15 +39,8 @@ constexpr int kMdStatSlots = 5 + kMdMaxThresholds;   // sum d, sum d^2, sum |n.n
 constexpr int kMdWeightOne = 1 << 20;            // the weight of the largest triangle
 constexpr int kMdNoSlot = 0x7fffffff;
 
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 f3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ F3 sub3(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 add3(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ F3 mul3(F3 a, float t) { return {a.x * t, a.y * t, a.z * t}; }
 __device__ __forceinline__ F3 along(F3 a, F3 d, float t) { return add3(a, mul3(d, t)); }                 // a + d t
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }                  // a NaN gives 0
-__device__ __forceinline__ bool finite3(F3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
 struct Rec { F3 a, ab, ac; float r_ab, r_ac, r_bc, d00, d01, d11, rden; };
 struct Edge { F3 b, bc, lo, hi; };

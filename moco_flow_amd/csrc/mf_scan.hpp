@@ -1,5 +1,5 @@
 // mf_scan.hpp -- the ordered integer prefix of the library, written once.  Users: mf_sample.hip (compact_*_kernel: mf_compact_mask),
-// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (in_range, wave_add), mf_mesh_distance.hip (the same two),
+// mf_batch.hip (mask_*_kernel: mf_mask_compact), mf_mesh.hip (mc_scan_kernel; mc::block_scan: lanes_below), mf_mesh_components.hip (in_range, wave_add), mf_mesh_distance.hip (the same two), mf_mesh_rays.hip (in_range),
 // mf_regions.hip (reg_best_kernel, reg_table_*_kernel), mf_mesh_simplify.hip (the survivors' and the used cells' ranks), mf_mesh_smooth.hip
 // (the raw and the compact ring offsets), mf_lattice.hip (lat_*_kernel).  The four units that walk contiguous shares (mf_shares.hpp:
 // share_of) take their range from share_range.

@@ -6,7 +6,8 @@ clean-up that follows an isosurface at a fixed threshold: connected components (
 filter on them (mf_mesh_filter_*, mf_gather_rows) -- the body kept, the detached specks dropped, on the device; the
 reduction of the triangle count by vertex clustering (simplify_mesh: mf_simplify_mesh_*); and vertex adjacency with the
 smoothing built on it (vertex_rings: mf_rings_mesh_*, smooth_mesh: mf_smooth_mesh); and how far two meshes are apart
-(MeshIndex, closest_point, sample_surface, surface_distance: mf_surface_*)."""
+(MeshIndex, closest_point, sample_surface, surface_distance: mf_surface_*); and rays against a mesh -- the first hit, any hit,
+what a camera sees of it (cast_rays, visible_from: mf_surface_corners, mf_surface_cast)."""
 import ctypes as C
 import math
 
@@ -659,7 +660,18 @@ class MeshIndex:
     records (Tp, 16), edges (Tp, 12), slot_tri (Tp,), tile_box (Tp / 64, 8), tri_slot (T,), area2 (T,), normal (T, 3),
     dropped (T,) uint8, ``dropped_count`` (device int64 scalar), weights / cum (T,) int64: as include/mocoflow_hip.h defines them.
     A dropped triangle (an index outside [0, V), no area, a record field that is not finite) is never returned and never sampled.
-    Nothing is read back from the device."""
+    ``corners`` (Tp, 16): what cast_rays reads per slot -- the three vertices as read, the triangle's box, a zero -- built by
+    mf_surface_corners on first use and kept.  Nothing is read back from the device."""
+    _corners = None
+
+    @property
+    def corners(self):
+        if self._corners is None:
+            corners = torch.empty((self.n_tiles * _MD_TILE, 16), dtype=torch.float32, device=self.device)
+            L.launch(self.device, "mf_surface_corners", L.ptr0(self.verts), self.V, L.ptr0(self.tris), self.T, L.ptr0(self.slot_tri),
+                     L.ptr0(corners))
+            self._corners = corners
+        return self._corners
 
     def __init__(self, verts, tris, order="morton"):
         _check_tris(tris, "MeshIndex")
@@ -841,3 +853,111 @@ def surface_distance(mesh_a, mesh_b, n=100_000, thresholds=(), generator=None, d
     P, R = ab["within"].to(torch.float64) / ab["finite"], ba["within"].to(torch.float64) / ba["finite"]
     fscore = torch.where(P + R > 0, 2 * P * R / (P + R), torch.zeros_like(P))
     return dict(a2b=ab, b2a=ba, chamfer=(ab["mean"] + ba["mean"]) / 2, fscore=fscore)
+
+
+# ---- ray casts against a mesh (csrc/mf_mesh_rays.hip; include/mocoflow_hip.h "ray casts against a mesh") ----
+_MR_MODES = {"first": 0, "any": 1}
+
+
+def _ray_bounds(bound, Q, dev, what):
+    if not isinstance(bound, torch.Tensor):
+        return None
+    L.require_gpu(bound, "cast_rays")
+    if bound.device != dev or bound.dtype != torch.float32 or bound.shape not in ((), (Q,)):
+        raise RuntimeError(f"cast_rays: {what} is a float or a float32 tensor () or ({Q},) on {dev}, got {bound.dtype} {tuple(bound.shape)}")
+    return bound.detach().expand(Q).contiguous()
+
+
+def cast_rays(index, origins=None, dirs=None, rays=None, t_min=0.0, t_max=math.inf, mode="first", cull=True, return_visited=False):
+    """Rays against the index's mesh.  Either ``origins`` and ``dirs`` (Q, 3) float32 with ``t_min`` / ``t_max`` as floats or
+    float32 (Q,) tensors, or ``rays`` (Q, >= 8) float32 rows in the package's layout (o, d, near, far: the bounds are the rows').
+    A hit at parameter t lies at o + t d (d is not normalised by anyone).  ``mode="first"`` -> (t (Q,) float32, tri (Q,) int32
+    in the caller's numbering, bary (Q, 3) float32: the weights of the triangle's three vertices); a miss is t = +inf, tri = -1,
+    bary = 0.  ``mode="any"`` -> hit (Q,) uint8.  [, visited (ceil(Q / 64),) int32: the 64-triangle tiles each wave of 64 rays
+    evaluated].  Both faces count.
+
+    Exact in the sense of include/mocoflow_hip.h: a triangle is accepted by sign tests on edge functions of vertices sheared along
+    the ray, every operation rounded once, so a ray through a shared edge or vertex of a closed mesh is never lost between two
+    triangles; ``first`` is the lexicographic minimum of (t, triangle index) over the accepted kept triangles.  ``cull=True`` skips
+    tiles by their boxes, ``False`` evaluates every one; both give the same bits, as do every ``order`` of the index and every
+    order of the rays.  A ray with a component that is not finite, a zero direction or t_min > t_max hits nothing.  The rays are
+    visited in the Morton order of the point each reaches at the distance of the mesh's centre, and a wave starts at the tile
+    whose code is nearest its first ray's: plumbing that no result depends on.  No host read."""
+    if not isinstance(index, MeshIndex):
+        raise RuntimeError("cast_rays: index must be a MeshIndex")
+    if mode not in _MR_MODES:
+        raise ValueError(f"cast_rays: mode is 'first' or 'any', got {mode!r}")
+    dev = index.device
+    if rays is not None:
+        if origins is not None or dirs is not None:
+            raise ValueError("cast_rays: give origins and dirs, or rays, not both")
+        if rays.dim() != 2 or rays.shape[1] < 8 or rays.dtype != torch.float32:
+            raise RuntimeError(f"cast_rays: rays must be (Q, >= 8) float32, got {tuple(rays.shape)} {rays.dtype}")
+        L.require_gpu(rays, "cast_rays")
+        rays = rays.detach()
+        if rays.shape[0] and (rays.stride(1) != 1 or rays.stride(0) < rays.shape[1]):
+            rays = rays.contiguous()                                         # (a column slice or a row subset is read in place)
+        Q, stride = rays.shape[0], rays.stride(0) if rays.shape[0] else 8
+        o, d = rays[:, 0:3], rays[:, 3:6]
+        o_ptr, bound_stride = rays.data_ptr(), stride
+        d_ptr, lo_ptr, hi_ptr = o_ptr + 12, o_ptr + 24, o_ptr + 28
+    else:
+        if origins is None or dirs is None:
+            raise ValueError("cast_rays: give origins and dirs, or rays")
+        for name, x in (("origins", origins), ("dirs", dirs)):
+            if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
+                raise RuntimeError(f"cast_rays: {name} must be (Q, 3) float32, got {tuple(x.shape)} {x.dtype}")
+            L.require_gpu(x, "cast_rays")
+        if origins.shape != dirs.shape:
+            raise RuntimeError(f"cast_rays: origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)}")
+        o, d = origins.detach().contiguous(), dirs.detach().contiguous()
+        Q, stride = o.shape[0], 3
+        lo, hi = _ray_bounds(t_min, Q, dev, "t_min"), _ray_bounds(t_max, Q, dev, "t_max")
+        if lo is None and hi is None:                                        # one pair of bounds for every ray
+            held, bound_stride = torch.tensor([float(t_min), float(t_max)], dtype=torch.float32, device=dev), 0
+            lo_ptr, hi_ptr = held.data_ptr(), held.data_ptr() + 4      # (held until the launch is enqueued)
+        else:
+            lo = torch.full((Q,), float(t_min), dtype=torch.float32, device=dev) if lo is None else lo
+            hi = torch.full((Q,), float(t_max), dtype=torch.float32, device=dev) if hi is None else hi
+            bound_stride, lo_ptr, hi_ptr = 1, lo.data_ptr(), hi.data_ptr()
+        o_ptr, d_ptr = o.data_ptr(), d.data_ptr()
+    if o.device != dev:
+        raise RuntimeError(f"cast_rays: rays on {o.device}, the index on {dev}")
+    n_waves = (Q + 63) // 64
+    first = mode == "first"
+    t = torch.empty(Q, dtype=torch.float32, device=dev) if first else None
+    tri = torch.empty(Q, dtype=torch.int32, device=dev) if first else None
+    bary = torch.empty((Q, 3), dtype=torch.float32, device=dev) if first else None
+    hit = None if first else torch.empty(Q, dtype=torch.uint8, device=dev)
+    visited = torch.empty(n_waves, dtype=torch.int32, device=dev) if return_visited else None
+    if Q:
+        centre = (index.lo + index.hi) * 0.5
+        reach = (centre - o).norm(dim=1, keepdim=True) / d.norm(dim=1, keepdim=True)
+        codes, qorder = torch.sort(_morton(o + d * reach, index.lo, index.hi), stable=True)
+        qorder = qorder.to(torch.int32)
+        start = None
+        if index.n_tiles:
+            start = (torch.searchsorted(index.tile_codes, codes[::64].contiguous(), right=True) - 1).clamp(0, index.n_tiles - 1).to(torch.int32)
+        L.launch(dev, "mf_surface_cast", L.ptr0(index.corners), L.ptr0(index.slot_tri), L.ptr0(index.tile_box), index.T, o_ptr, d_ptr, stride,
+                 lo_ptr, hi_ptr, bound_stride, Q, qorder.data_ptr(), L.ptr0(start), _MR_MODES[mode], 1 if cull else 0, L.ptr0(t), L.ptr0(tri),
+                 L.ptr0(bary), L.ptr0(hit), L.ptr0(visited))
+    out = (t, tri, bary) if first else (hit,)
+    if return_visited:
+        out += (visited,)
+    return out if len(out) > 1 else out[0]
+
+
+def visible_from(index, points, eye, bias):
+    """Which of ``points`` (Q, 3) float32 the point ``eye`` sees past the index's mesh -> (Q,) uint8, 1 where the segment from
+    points[i] to eye is free.  ``eye``: (3,) or (Q, 3) float32 on the index's device.  An any-hit cast_rays with o = points,
+    d = eye - points and t in [bias, 1].  ``bias``: a float in units of the segment, chosen by the caller: it excludes the surface
+    the point itself sits on (a vertex or a surface sample of this mesh is hit at t = 0, give or take rounding); too large a
+    bias also excludes an occluder that close to the point.  A point that is not finite, or that is the eye, counts as seen."""
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise RuntimeError(f"visible_from: points must be (Q, 3) float32, got {tuple(points.shape)} {points.dtype}")
+    if not isinstance(eye, torch.Tensor) or eye.dtype != torch.float32 or eye.shape not in ((3,), tuple(points.shape)):
+        raise RuntimeError(f"visible_from: eye must be a float32 tensor (3,) or {tuple(points.shape)}")
+    L.require_gpu(points, "visible_from")
+    L.require_gpu(eye, "visible_from")
+    points = points.detach()
+    return cast_rays(index, points, (eye.detach() - points).contiguous(), t_min=float(bias), t_max=1.0, mode="any") ^ 1
