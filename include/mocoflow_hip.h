@@ -1077,6 +1077,15 @@ int32_t mf_grid_edt(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, co
  * no slot holds it: an entry of order outside [0, T) leaves its slot empty, and of equal entries the lowest slot keeps the
  * triangle (an integer atomic minimum), so a bad order cannot fault.  Every slot is written.
  *
+ * The tile walk of a MeshIndex search (mf_surface_closest, mf_surface_cast): one row (a query, a ray) per lane.  Lane l of wave w
+ * takes row qorder[64 w + l] (int32 (Q) or NULL: identity; an entry outside [0, Q) is skipped, a repeated one leaves another row
+ * unwritten -- the caller passes a permutation).  Wave w visits the tiles start[w], +1, -1, +2, ... (int32 (ceil(Q / 64)) or NULL:
+ * 0; clamped into the tiles).  Evaluating every tile is the sweep.  Under the cull the wave leaves the walk when no lane wants
+ * anything more, and takes ONE decision per tile (one ballot, wave-uniform): the tile is skipped when it holds no kept slot or no
+ * lane wants it -- by the search's own test of the tile's box, below.  Any other tile is evaluated whole, its 64 slots in order on
+ * every lane, a slot's rows read at wave-uniform addresses (scalar loads).
+ * visited (ceil(Q / 64)) int32, optional: the tiles wave w evaluated.  Q = 0 launches nothing.
+ *
  * mf_surface_closest: query (Q, 3).  The value of a kept triangle at q is max(m, lb(q, lo, hi)) (lb > m ? lb : m), m the least, in
  * the order ab, ac, bc, face under strict < (the first minimum wins, a NaN never does), of dot(q - P, q - P) over
  *   edge ab  P = a + ab t, t = min(max(dot(q - a, ab) r_ab, 0), 1);   edge ac  the same with ac, r_ac
@@ -1086,14 +1095,10 @@ int32_t mf_grid_edt(const uint32_t* bits, int32_t gx, int32_t gy, int32_t gz, co
  * and lb(q, lo, hi) = dot(g, g), g = max(max(lo - q, q - hi), 0) per axis.  Per query: the lexicographic minimum of (value,
  * caller's index) over the kept triangles -> d2 (Q), tri (Q) int32, point (Q, 3) = the winning candidate's P, region (Q) uint8
  * (0 ab, 1 ac, 2 bc, 3 face; optional).  No kept triangle, or no value below +inf and no kept triangle at +inf: d2 = +inf,
- * tri = -1, point = 0, region = 0.  One query per lane; lane l of wave w takes row qorder[64 w + l] (int32 (Q) or NULL: identity;
- * an entry outside [0, Q) is skipped, a repeated one leaves another row unwritten -- the caller passes a permutation).  Wave w
- * visits the tiles start[w], +1, -1, +2, ... (int32 (ceil(Q / 64)) or NULL: 0; clamped).  mode: 0 = evaluate every tile,
- * 1 = skip a tile when it holds no kept slot or when lb(q, tile box) > best fails to be <= on EVERY lane of the wave (one ballot:
- * the wave-uniform decision).  Every operation of lb is monotone under rounding, so lb of a containing box <= lb of the
- * triangle's own box <= the value, in fp32: the skip needs no slack and both modes give the same bits.  A tile's records are read at
- * wave-uniform addresses (scalar loads).
- * visited (ceil(Q / 64)) int32, optional: the tiles wave w evaluated.  Q = 0 launches nothing.
+ * tri = -1, point = 0, region = 0.  The rows are the queries of the tile walk above (qorder, start, visited).  mode: 0 = the sweep,
+ * 1 = the cull: a lane wants a tile iff its row is a query and lb(q, tile box) <= best (best: the lane's least value so far, +inf
+ * before).  Every operation of lb is monotone under rounding, so lb of a containing box <= lb of the triangle's own box <= the
+ * value, in fp32: the skip needs no slack and both modes give the same bits.
  *
  * mf_surface_weights: weights (T) int64 = 0 for a dropped triangle, else max(1, (int64) floorf(area2 (1048576.f / amax[0]))), capped
  * at 2^22; amax: device fp32[1], the largest area2.  The caller takes their running sum `cum` (integers: exact in any order).
@@ -1152,16 +1157,13 @@ int32_t mf_surface_stats(const float* d2, int64_t n, const int32_t* tri_src, con
  *     int32, bary (Q, 3) = (U, V, W) (1 / det) of the winner, recomputed from its slot: the hit is bary0 a + bary1 b + bary2 c.
  *     A miss: t = +inf, tri = -1, bary = 0.  hit may be NULL.
  *   mode 1 (any): hit (Q) uint8 = 1 iff some kept triangle is accepted.  t, tri, bary may be NULL.
- * One ray per lane; lane l of wave w takes row qorder[64 w + l] (int32 (Q) or NULL: identity; an entry outside [0, Q) is
- * skipped, a repeated one leaves another row unwritten -- the caller passes a permutation).  Wave w visits the tiles start[w],
- * +1, -1, +2, ... (int32 (ceil(Q / 64)) or NULL: 0; clamped), as mf_surface_closest does.  cull: 0 = evaluate every tile;
- * 1 = with the tile box translated by o (l = lo - o, h = hi - o) and
+ * The rows are the rays of the tile walk of a MeshIndex search (the section above: qorder, start, visited).  cull: 0 = the sweep;
+ * 1 = the cull: with the tile box translated by o (l = lo - o, h = hi - o) and
  *   x0 = l[kx] - max(Sx l[kz], Sx h[kz]), x1 = h[kx] - min(Sx l[kz], Sx h[kz]); y0, y1 the same with ky, Sy;
  *   z0 = min(Sz l[kz], Sz h[kz]), z1 = max(Sz l[kz], Sz h[kz])
  * a lane WANTS the tile unless its ray is dead, or (mode 1) it has a hit already, or !(x0 <= 0 <= x1), or !(y0 <= 0 <= y1), or
- * z1 < t_min, or z0 > t_max, or !(z0 <= best) (best: the lane's least t so far, +inf before); a tile is skipped when it holds no
- * kept slot or no lane of the wave wants it (one ballot: the wave-uniform decision), and the wave leaves the tile loop when
- * every lane is dead or (mode 1) has its hit.
+ * z1 < t_min, or z0 > t_max, or !(z0 <= best) (best: the lane's least t so far, +inf before); a lane wants nothing more when
+ * its ray is dead or (mode 1) has its hit.
  *   P1  Cull equals sweep, bit for bit.  Subtracting a fixed o, multiplying by a fixed S and min / max are monotone under
  *       rounding, so the intervals of a box that contains a vertex contain the vertex's computed x, y, z.  An accepted triangle
  *       has 0 inside its own computed x and y ranges (a condition of acceptance) and t >= zmin >= z0, t <= zmax <= z1 (the
@@ -1176,8 +1178,7 @@ int32_t mf_surface_stats(const float* d2, int64_t n, const int32_t* tri_src, con
  *   P3  Order independence: the result is a minimum over a set, so the order of the index, of the rays, the start tiles and
  *       the launch shape cannot change it.
  *   P4  No atomics; a dropped triangle, or a slot without one (slot_tri < 0), never wins.
- * The corner rows and slot_tri of a tile are read at wave-uniform addresses (scalar loads); every store is a vector store.
- * visited (ceil(Q / 64)) int32, optional: the tiles wave w evaluated.  Q = 0 launches nothing.
+ * Every store is a vector store.
  *
  * Every count (V, T, Q) in [0, 2^31 - 1), a NULL that is needed, a mode or cull outside 0 .. 1, ray_stride < 3, bound_stride < 0,
  * corners not 16-byte aligned and an output that is an input are MF_E_INVALID with an mf_last_error text, settled before any

@@ -4,8 +4,7 @@
 // restates every output in np.float32 bit for bit; dot(x, y) = (x0 y0 + x1 y1) + x2 y2 everywhere.
 //   md_fill / md_claim / md_build / md_unplaced   mf_surface_records: a slot per triangle in the caller's `order`, a 16-float record
 //                                                 + a 12-float edge row (b, bc, the triangle's box) per slot, a box per 64-slot tile
-//   md_closest_kernel                             mf_surface_closest: a query per lane; per tile ONE wave-uniform decision (the ballot
-//                                                 of the lanes' strict box tests), then the tile's 64 records on every lane
+//   md_closest_kernel                             mf_surface_closest: a query per lane, on the tile walk of include/mocoflow_hip.h
 //   md_weights / md_sample                        integer area weights; a triangle by binary search of their running sum, a point
 //   md_stats / md_stats_finish                    float64 sums through mf_reduce.hpp, a maximum, integer counts
 // The distance to a triangle is the least of FOUR clamped candidates (edges ab, ac, bc, the face), branch-free: a wave never
@@ -20,19 +19,16 @@
 #pragma clang fp contract(off)
 #include <cmath>
 
-#include "mf_f3.hpp"
-#include "mf_host.hpp"
 #include "mf_reduce.hpp"
-#include "mf_scan.hpp"
+#include "mf_surface.hpp"
 
 namespace mf {
 
-constexpr int kMdThreads = 256;
-constexpr int kMdWaves = kMdThreads / 64;
-constexpr int kMdTile = 64;                      // slots per tile: one record per lane of a wave
+constexpr int kMdThreads = 256;                  // (tests/ reads these two from this file: the literals stay here)
+constexpr int kMdTile = 64;
+static_assert(kMdThreads == kSurfThreads && kMdTile == kSurfTile, "one tile geometry: mf_surface.hpp");
 constexpr int kMdRecord = 16;                    // floats per record
 constexpr int kMdEdge = 12;                      // floats per edge row
-constexpr int kMdBox = 8;                        // floats per tile box: lo, hi, the number of kept slots, 0
 constexpr int kMdStatBlocks = 1024;              // md_stats: workgroups of its grid-stride loop
 constexpr int kMdMaxThresholds = 8;
 constexpr int kMdStatSlots = 5 + kMdMaxThresholds;   // sum d, sum d^2, sum |n.n|, finite rows, rows left out, within[8]
@@ -121,11 +117,9 @@ __global__ __launch_bounds__(kMdThreads) void md_build_kernel(const RecordParams
   e.hi = {-INFINITY, -INFINITY, -INFINITY};
   bool ok = false;
   if (o >= 0) {
-    const long long i0 = p.tris[3ll * o], i1 = p.tris[3ll * o + 1], i2 = p.tris[3ll * o + 2];
     float area2 = 0.f;
-    F3 nrm = {0.f, 0.f, 0.f};
-    if (in_range(i0, p.V) && in_range(i1, p.V) && in_range(i2, p.V)) {           // before any address is formed
-      const F3 a = f3(p.verts + 3 * i0), b = f3(p.verts + 3 * i1), c = f3(p.verts + 3 * i2);
+    F3 nrm = {0.f, 0.f, 0.f}, a, b, c;
+    if (load_corners(p.verts, p.tris, p.V, o, a, b, c)) {                        // else: a dropped triangle
       Rec k;
       k.a = a; k.ab = sub3(b, a); k.ac = sub3(c, a);
       const F3 bc = sub3(c, b);
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(kMdThreads) void md_build_kernel(const RecordParams
   }
   const int kept = __popcll(__ballot(ok));
   if (slot && (threadIdx.x & 63) == 0) {
-    float* box = p.tile_box + (s / kMdTile) * kMdBox;
+    float* box = p.tile_box + (s / kMdTile) * kSurfBox;
     reinterpret_cast<float4*>(box)[0] = {lo.x, lo.y, lo.z, hi.x};
     reinterpret_cast<float4*>(box)[1] = {hi.y, hi.z, (float)kept, 0.f};
   }
@@ -208,7 +202,7 @@ __device__ __forceinline__ Edge md_edge(const float* f) {
 // The 28 floats of a slot are read at a wave-uniform address: scalar loads (the loop stores nothing, so they are unclobbered).
 __global__ __launch_bounds__(kMdThreads) void md_closest_kernel(const ClosestParams p) {
   const int lane = threadIdx.x & 63;
-  const long long wave = (long long)blockIdx.x * kMdWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long wave = (long long)blockIdx.x * kSurfWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (wave * 64 >= p.Q) return;                                                  // uniform over the wave
   const long long i = wave * 64 + lane;
   long long row = -1;
@@ -229,10 +223,10 @@ __global__ __launch_bounds__(kMdThreads) void md_closest_kernel(const ClosestPar
     const int d = (k + 1) >> 1, t = (k & 1) ? s + d : s - d;
     if (t < 0 || t >= n) continue;
     if (p.cull) {
-      const float* box = p.tile_box + (long long)t * kMdBox;
+      const float* box = p.tile_box + (long long)t * kSurfBox;
       const float lb = box_lb(q, f3(box), f3(box + 3));
       const bool skip = !live || !(lb <= best);
-      if (box[6] == 0.f || __all(skip)) continue;                                // the one decision of the wave
+      if (box[kSurfBoxKept] == 0.f || __all(skip)) continue;                     // the one decision of the wave
     }
     ++evaluated;
     const long long s0 = (long long)t * kMdTile;
@@ -287,9 +281,8 @@ __global__ __launch_bounds__(kMdThreads) void md_sample_kernel(const SampleParam
       const long long mid = (lo + hi) >> 1;
       if ((unsigned long long)p.cum[mid] > target) hi = mid; else lo = mid + 1;
     }
-    const long long i0 = p.tris[3 * lo], i1 = p.tris[3 * lo + 1], i2 = p.tris[3 * lo + 2];
-    if (in_range(i0, p.V) && in_range(i1, p.V) && in_range(i2, p.V)) {           // a `cum` that is not the index's own may point anywhere
-      const F3 a = f3(p.verts + 3 * i0), b = f3(p.verts + 3 * i1), c = f3(p.verts + 3 * i2);
+    F3 a, b, c;
+    if (load_corners(p.verts, p.tris, p.V, lo, a, b, c)) {                       // (a foreign `cum` may point anywhere) else: tri = -1
       const float u0 = p.u[2 * i], u1 = p.u[2 * i + 1];
       const float s = sqrtf(u0), b0 = 1.f - s, b1 = s * (1.f - u1), b2 = s * u1;
       pt = add3(add3(mul3(a, b0), mul3(b, b1)), mul3(c, b2));
@@ -365,7 +358,6 @@ __global__ __launch_bounds__(kMdThreads) void md_stats_finish_kernel(const doubl
   }
 }
 
-inline long long md_blocks(long long n) { return (n + kMdThreads - 1) / kMdThreads; }
 inline long long md_stat_blocks(long long n) { return capped_blocks(n, kMdThreads, kMdStatBlocks); }
 // scratch of mf_surface_stats: the sums' partials float64 [workgroups][13] | the maxima float64 [workgroups].  Returns its size.
 inline long long md_stat_scratch(void* scratch, long long blocks, double*& parts, double*& parts_max) {
@@ -374,7 +366,6 @@ inline long long md_stat_scratch(void* scratch, long long blocks, double*& parts
   parts_max = c.take<double>(blocks);
   return c.bytes();
 }
-inline bool md_count_ok(int64_t n) { return n >= 0 && n < kIndexLimit - 1; }
 
 }  // namespace mf
 
@@ -383,19 +374,13 @@ using namespace mf;
 extern "C" int32_t mf_surface_records(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int32_t* order, float* records,
                                    float* edges, int32_t* slot_tri, float* tile_box, int32_t* tri_slot, float* area2, float* normal,
                                    uint8_t* dropped, int64_t* dropped_count, void* stream) {
-  if (!md_count_ok(V) || !md_count_ok(T))
+  if (!surf_count_ok(V) || !surf_count_ok(T))
     return fail(MF_E_INVALID, "mf_surface_records: V=%lld T=%lld (both in [0, 2^31 - 1))", (long long)V, (long long)T);
   if (!dropped_count) return fail(MF_E_INVALID, "mf_surface_records: null dropped_count");
   if (T > 0 && (!tris || !records || !edges || !slot_tri || !tile_box || !tri_slot || !area2 || !normal || !dropped))
     return fail(MF_E_INVALID, "mf_surface_records: null tris or output with T=%lld", (long long)T);
   if (T > 0 && V > 0 && !verts) return fail(MF_E_INVALID, "mf_surface_records: null verts with V=%lld", (long long)V);
-  if (T > 0) {
-    const void* in[3] = {verts, tris, order};
-    const void* out[9] = {records, edges, slot_tri, tile_box, tri_slot, area2, normal, dropped, dropped_count};
-    for (const void* o : out)
-      for (const void* i : in)
-        if (i && o == i) return fail(MF_E_INVALID, "mf_surface_records: an output aliases an input");
-  }
+  if (T > 0 && surf_alias("mf_surface_records", {records, edges, slot_tri, tile_box, tri_slot, area2, normal, dropped, dropped_count}, {verts, tris, order})) return MF_E_INVALID;
   RecordParams p{};
   p.verts = verts; p.tris = reinterpret_cast<const long long*>(tris); p.order = order;
   p.records = records; p.edges = edges; p.slot_tri = slot_tri; p.tile_box = tile_box;
@@ -403,7 +388,7 @@ extern "C" int32_t mf_surface_records(const float* verts, int64_t V, const int64
   p.dropped_count = reinterpret_cast<long long*>(dropped_count);
   p.V = V; p.T = T; p.Tpad = align_up(T, kMdTile);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 block(kMdThreads), grid((unsigned)(T > 0 ? md_blocks(p.Tpad) : 1));
+  const dim3 block(kMdThreads), grid((unsigned)(T > 0 ? surf_blocks(p.Tpad) : 1));
   hipLaunchKernelGGL(md_fill_kernel, grid, block, 0, s, p);
   if (T > 0) {
     hipLaunchKernelGGL(md_claim_kernel, grid, block, 0, s, p);
@@ -416,58 +401,52 @@ extern "C" int32_t mf_surface_records(const float* verts, int64_t V, const int64
 extern "C" int32_t mf_surface_closest(const float* records, const float* edges, const int32_t* slot_tri, const float* tile_box, int64_t T,
                                    const float* query, int64_t Q, const int32_t* qorder, const int32_t* start, int32_t mode, float* d2,
                                    int32_t* tri, float* point, uint8_t* region, int32_t* visited, void* stream) {
-  if (!md_count_ok(T) || !md_count_ok(Q))
+  if (!surf_count_ok(T) || !surf_count_ok(Q))
     return fail(MF_E_INVALID, "mf_surface_closest: T=%lld Q=%lld (both in [0, 2^31 - 1))", (long long)T, (long long)Q);
   if (mode < 0 || mode > 1) return fail(MF_E_INVALID, "mf_surface_closest: mode=%d (0 sweep, 1 cull)", mode);
   if (Q == 0) return MF_OK;
   if (T > 0 && (!records || !edges || !slot_tri || !tile_box)) return fail(MF_E_INVALID, "mf_surface_closest: null records, edges, slot_tri or tile_box");
   if (!query || !d2 || !tri || !point) return fail(MF_E_INVALID, "mf_surface_closest: null query, d2, tri or point");
-  const void* in[7] = {records, edges, slot_tri, tile_box, query, qorder, start};
-  const void* out[5] = {d2, tri, point, region, visited};
-  for (const void* o : out)
-    for (const void* i : in)
-      if (o && o == i) return fail(MF_E_INVALID, "mf_surface_closest: an output aliases an input");
+  if (surf_alias("mf_surface_closest", {d2, tri, point, region, visited}, {records, edges, slot_tri, tile_box, query, qorder, start})) return MF_E_INVALID;
   ClosestParams p{};
   p.records = records; p.edges = edges; p.slot_tri = slot_tri; p.tile_box = tile_box; p.query = query; p.qorder = qorder; p.start = start;
   p.d2 = d2; p.tri = tri; p.point = point; p.region = region; p.visited = visited;
-  p.Q = Q; p.n_tiles = (int)(align_up(T, kMdTile) / kMdTile); p.cull = mode;
-  const dim3 block(kMdThreads), grid((unsigned)md_blocks(Q));
+  p.Q = Q; p.n_tiles = surf_tiles(T); p.cull = mode;
+  const dim3 block(kMdThreads), grid((unsigned)surf_blocks(Q));
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(md_closest_kernel, grid, block, 0, s, p);
   return check_launch("mf_surface_closest");
 }
 
 extern "C" int32_t mf_surface_weights(const float* area2, const uint8_t* dropped, int64_t T, const float* amax, int64_t* weights, void* stream) {
-  if (!md_count_ok(T)) return fail(MF_E_INVALID, "mf_surface_weights: T=%lld (in [0, 2^31 - 1))", (long long)T);
+  if (!surf_count_ok(T)) return fail(MF_E_INVALID, "mf_surface_weights: T=%lld (in [0, 2^31 - 1))", (long long)T);
   if (T == 0) return MF_OK;
   if (!area2 || !dropped || !amax || !weights) return fail(MF_E_INVALID, "mf_surface_weights: null area2, dropped, amax or weights");
   if ((const void*)weights == area2 || (const void*)weights == dropped || (const void*)weights == amax)
     return fail(MF_E_INVALID, "mf_surface_weights: weights aliases an input");
-  hipLaunchKernelGGL(md_weights_kernel, dim3((unsigned)md_blocks(T)), dim3(kMdThreads), 0, static_cast<hipStream_t>(stream), area2, dropped,
+  hipLaunchKernelGGL(md_weights_kernel, dim3((unsigned)surf_blocks(T)), dim3(kMdThreads), 0, static_cast<hipStream_t>(stream), area2, dropped,
                      (long long)T, amax, reinterpret_cast<long long*>(weights));
   return check_launch("mf_surface_weights");
 }
 
 extern "C" int32_t mf_surface_sample(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int64_t* cum, const int64_t* r,
                                   const float* u, int64_t n, float* points, int32_t* tri, void* stream) {
-  if (!md_count_ok(V) || !md_count_ok(T) || !md_count_ok(n))
+  if (!surf_count_ok(V) || !surf_count_ok(T) || !surf_count_ok(n))
     return fail(MF_E_INVALID, "mf_surface_sample: V=%lld T=%lld n=%lld (each in [0, 2^31 - 1))", (long long)V, (long long)T, (long long)n);
   if (n == 0) return MF_OK;
   if (!points || !tri) return fail(MF_E_INVALID, "mf_surface_sample: null points or tri");
   if (T > 0 && (!tris || !cum || !r || !u || (V > 0 && !verts))) return fail(MF_E_INVALID, "mf_surface_sample: null verts, tris, cum, r or u");
-  const void* in[5] = {verts, tris, cum, r, u};
-  for (const void* i : in)
-    if (i && (i == (const void*)points || i == (const void*)tri)) return fail(MF_E_INVALID, "mf_surface_sample: an output aliases an input");
+  if (surf_alias("mf_surface_sample", {points, tri}, {verts, tris, cum, r, u})) return MF_E_INVALID;
   SampleParams p{};
   p.verts = verts; p.tris = reinterpret_cast<const long long*>(tris); p.cum = reinterpret_cast<const long long*>(cum);
   p.r = reinterpret_cast<const long long*>(r); p.u = u; p.points = points; p.tri = tri;
   p.V = V; p.T = T; p.n = n;
-  hipLaunchKernelGGL(md_sample_kernel, dim3((unsigned)md_blocks(n)), dim3(kMdThreads), 0, static_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(md_sample_kernel, dim3((unsigned)surf_blocks(n)), dim3(kMdThreads), 0, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_surface_sample");
 }
 
 extern "C" int64_t mf_surface_stats_scratch_bytes(int64_t n) {
-  if (!md_count_ok(n)) return fail(MF_E_INVALID, "mf_surface_stats_scratch_bytes: n=%lld (in [0, 2^31 - 1))", (long long)n);
+  if (!surf_count_ok(n)) return fail(MF_E_INVALID, "mf_surface_stats_scratch_bytes: n=%lld (in [0, 2^31 - 1))", (long long)n);
   double *parts, *parts_max;
   return md_stat_scratch(nullptr, md_stat_blocks(n), parts, parts_max);
 }
@@ -475,7 +454,7 @@ extern "C" int64_t mf_surface_stats_scratch_bytes(int64_t n) {
 extern "C" int32_t mf_surface_stats(const float* d2, int64_t n, const int32_t* tri_src, const int32_t* tri_dst, const float* normal_src,
                                     int64_t T_src, const float* normal_dst, int64_t T_dst, const float* thresholds, int32_t n_thresholds,
                                     double* out_f64, int64_t* out_i64, void* scratch, void* stream) {
-  if (!md_count_ok(n) || !md_count_ok(T_src) || !md_count_ok(T_dst))
+  if (!surf_count_ok(n) || !surf_count_ok(T_src) || !surf_count_ok(T_dst))
     return fail(MF_E_INVALID, "mf_surface_stats: n=%lld T_src=%lld T_dst=%lld (each in [0, 2^31 - 1))", (long long)n, (long long)T_src, (long long)T_dst);
   if (n_thresholds < 0 || n_thresholds > kMdMaxThresholds || (n_thresholds > 0 && !thresholds))
     return fail(MF_E_INVALID, "mf_surface_stats: n_thresholds=%d (0 .. %d, with a host array)", n_thresholds, kMdMaxThresholds);

@@ -3,8 +3,8 @@
 // operation below is rounded once, in the order written, with no FMA, so that tests/mesh_rays_oracle.py restates every output in
 // np.float32 bit for bit.
 //   mr_corners_kernel      mf_surface_corners: per slot of the index a 16-float row -- the three vertices as read, the triangle's box
-//   mr_cast_kernel<MODE>   mf_surface_cast: a ray per lane; per tile ONE wave-uniform decision (the ballot of the lanes' tests of the
-//                          tile's sheared box), then the tile's 64 rows on every lane.  MODE 0 first hit, 1 any hit.
+//   mr_cast_kernel<MODE>   mf_surface_cast: a ray per lane, on the tile walk of include/mocoflow_hip.h (a lane tests the tile's sheared
+//                          box).  MODE 0 first hit, 1 any hit.
 // A ray picks its dominant axis kz and shears the mesh along itself: a vertex p becomes x = q[kx] - Sx q[kz], y = q[ky] - Sy q[kz],
 // z = Sz q[kz] with q = p - o.  These three numbers depend on the vertex and the ray alone, so two triangles that share an edge
 // see the same sheared end points, the edge function of one is exactly the negated edge function of the other, and a rounded
@@ -17,17 +17,11 @@
 #pragma clang fp contract(off)
 #include <cmath>
 
-#include "mf_f3.hpp"
-#include "mf_host.hpp"
-#include "mf_scan.hpp"
+#include "mf_surface.hpp"
 
 namespace mf {
 
-constexpr int kMrThreads = 256;
-constexpr int kMrWaves = kMrThreads / 64;
-constexpr int kMrTile = 64;                      // slots per tile, as mf_mesh_distance.hip's kMdTile
 constexpr int kMrCorner = 16;                    // floats per corner row: a, b, c, lo, hi, 0
-constexpr int kMrBox = 8;                        // floats per tile box, as mf_surface_records writes them
 
 // ---------------------------------------------------------------- corner rows ------------------------------------------------
 struct CornerParams {
@@ -38,18 +32,14 @@ struct CornerParams {
   long long V, T, Tpad;
 };
 
-__global__ __launch_bounds__(kMrThreads) void mr_corners_kernel(const CornerParams p) {
-  const long long s = (long long)blockIdx.x * kMrThreads + threadIdx.x;
+__global__ __launch_bounds__(kSurfThreads) void mr_corners_kernel(const CornerParams p) {
+  const long long s = (long long)blockIdx.x * kSurfThreads + threadIdx.x;
   if (s >= p.Tpad) return;
   F3 a = {0.f, 0.f, 0.f}, b = a, c = a, lo = a, hi = a;
   const long long t = p.slot_tri[s];
-  if (in_range(t, p.T)) {
-    const long long i0 = p.tris[3 * t], i1 = p.tris[3 * t + 1], i2 = p.tris[3 * t + 2];
-    if (in_range(i0, p.V) && in_range(i1, p.V) && in_range(i2, p.V)) {           // before any address is formed
-      a = f3(p.verts + 3 * i0); b = f3(p.verts + 3 * i1); c = f3(p.verts + 3 * i2);
-      lo = min3(min3(a, b), c);
-      hi = max3(max3(a, b), c);
-    }
+  if (in_range(t, p.T) && load_corners(p.verts, p.tris, p.V, t, a, b, c)) {      // else: a row of zeros
+    lo = min3(min3(a, b), c);
+    hi = max3(max3(a, b), c);
   }
   float* row = p.corners + s * kMrCorner;
   reinterpret_cast<float4*>(row)[0] = {a.x, a.y, a.z, b.x};
@@ -118,9 +108,9 @@ __device__ __forceinline__ bool wants_tile(const float* box, const Ray& r, float
 
 // The 16 floats of a slot are read at a wave-uniform address: scalar loads (the loop stores nothing, so they are unclobbered).
 template <int MODE>
-__global__ __launch_bounds__(kMrThreads) void mr_cast_kernel(const CastParams p) {
+__global__ __launch_bounds__(kSurfThreads) void mr_cast_kernel(const CastParams p) {
   const int lane = threadIdx.x & 63;
-  const long long wave = (long long)blockIdx.x * kMrWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long wave = (long long)blockIdx.x * kSurfWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (wave * 64 >= p.Q) return;                                                  // uniform over the wave
   const long long i = wave * 64 + lane;
   long long row = -1;
@@ -161,14 +151,14 @@ __global__ __launch_bounds__(kMrThreads) void mr_cast_kernel(const CastParams p)
     if (p.cull) {
       const bool done = !live || (MODE == 1 && found);
       if (__all(done)) break;                                                    // no lane wants anything any more
-      const float* box = p.tile_box + (long long)t * kMrBox;
+      const float* box = p.tile_box + (long long)t * kSurfBox;
       const bool want = !done && wants_tile(box, r, best);
-      if (box[6] == 0.f || !__any(want)) continue;                               // the one decision of the wave
+      if (box[kSurfBoxKept] == 0.f || !__any(want)) continue;                              // the one decision of the wave
     }
     ++evaluated;
-    const long long s0 = (long long)t * kMrTile;
+    const long long s0 = (long long)t * kSurfTile;
 #pragma unroll 2
-    for (int j = 0; j < kMrTile; ++j) {
+    for (int j = 0; j < kSurfTile; ++j) {
       const int tri = p.slot_tri[s0 + j];
       float th;
       const bool ok = tri_hit(p.corners + (s0 + j) * kMrCorner, r, th) && live && tri >= 0;
@@ -197,16 +187,13 @@ __global__ __launch_bounds__(kMrThreads) void mr_cast_kernel(const CastParams p)
   p.bary[3 * row] = bary.x; p.bary[3 * row + 1] = bary.y; p.bary[3 * row + 2] = bary.z;
 }
 
-inline long long mr_blocks(long long n) { return (n + kMrThreads - 1) / kMrThreads; }
-inline bool mr_count_ok(int64_t n) { return n >= 0 && n < kIndexLimit - 1; }
-
 }  // namespace mf
 
 using namespace mf;
 
 extern "C" int32_t mf_surface_corners(const float* verts, int64_t V, const int64_t* tris, int64_t T, const int32_t* slot_tri, float* corners,
                                       void* stream) {
-  if (!mr_count_ok(V) || !mr_count_ok(T))
+  if (!surf_count_ok(V) || !surf_count_ok(T))
     return fail(MF_E_INVALID, "mf_surface_corners: V=%lld T=%lld (both in [0, 2^31 - 1))", (long long)V, (long long)T);
   if (T == 0) return MF_OK;
   if (!tris || !slot_tri || !corners) return fail(MF_E_INVALID, "mf_surface_corners: null tris, slot_tri or corners with T=%lld", (long long)T);
@@ -216,8 +203,8 @@ extern "C" int32_t mf_surface_corners(const float* verts, int64_t V, const int64
     return fail(MF_E_INVALID, "mf_surface_corners: corners aliases an input");
   CornerParams p{};
   p.verts = verts; p.tris = reinterpret_cast<const long long*>(tris); p.slot_tri = slot_tri; p.corners = corners;
-  p.V = V; p.T = T; p.Tpad = align_up(T, kMrTile);
-  hipLaunchKernelGGL(mr_corners_kernel, dim3((unsigned)mr_blocks(p.Tpad)), dim3(kMrThreads), 0, static_cast<hipStream_t>(stream), p);
+  p.V = V; p.T = T; p.Tpad = align_up(T, kSurfTile);
+  hipLaunchKernelGGL(mr_corners_kernel, dim3((unsigned)surf_blocks(p.Tpad)), dim3(kSurfThreads), 0, static_cast<hipStream_t>(stream), p);
   return check_launch("mf_surface_corners");
 }
 
@@ -225,7 +212,7 @@ extern "C" int32_t mf_surface_cast(const float* corners, const int32_t* slot_tri
                                    const float* dirs, int64_t ray_stride, const float* t_min, const float* t_max, int64_t bound_stride,
                                    int64_t Q, const int32_t* qorder, const int32_t* start, int32_t mode, int32_t cull, float* t, int32_t* tri,
                                    float* bary, uint8_t* hit, int32_t* visited, void* stream) {
-  if (!mr_count_ok(T) || !mr_count_ok(Q))
+  if (!surf_count_ok(T) || !surf_count_ok(Q))
     return fail(MF_E_INVALID, "mf_surface_cast: T=%lld Q=%lld (both in [0, 2^31 - 1))", (long long)T, (long long)Q);
   if (mode < 0 || mode > 1) return fail(MF_E_INVALID, "mf_surface_cast: mode=%d (0 first, 1 any)", mode);
   if (cull < 0 || cull > 1) return fail(MF_E_INVALID, "mf_surface_cast: cull=%d (0 sweep, 1 cull)", cull);
@@ -237,18 +224,14 @@ extern "C" int32_t mf_surface_cast(const float* corners, const int32_t* slot_tri
   if (!origins || !dirs || !t_min || !t_max) return fail(MF_E_INVALID, "mf_surface_cast: null origins, dirs, t_min or t_max");
   if (mode == 0 && (!t || !tri || !bary)) return fail(MF_E_INVALID, "mf_surface_cast: mode 0 with null t, tri or bary");
   if (mode == 1 && !hit) return fail(MF_E_INVALID, "mf_surface_cast: mode 1 with null hit");
-  const void* in[9] = {corners, slot_tri, tile_box, origins, dirs, t_min, t_max, qorder, start};
-  const void* out[5] = {t, tri, bary, hit, visited};
-  for (const void* o : out)
-    for (const void* i : in)
-      if (o && o == i) return fail(MF_E_INVALID, "mf_surface_cast: an output aliases an input");
+  if (surf_alias("mf_surface_cast", {t, tri, bary, hit, visited}, {corners, slot_tri, tile_box, origins, dirs, t_min, t_max, qorder, start})) return MF_E_INVALID;
   CastParams p{};
   p.corners = corners; p.slot_tri = slot_tri; p.tile_box = tile_box;
   p.origins = origins; p.dirs = dirs; p.t_min = t_min; p.t_max = t_max; p.qorder = qorder; p.start = start;
   p.t = t; p.tri = tri; p.bary = bary; p.hit = hit; p.visited = visited;
   p.Q = Q; p.ray_stride = ray_stride; p.bound_stride = bound_stride;
-  p.n_tiles = (int)(align_up(T, kMrTile) / kMrTile); p.cull = cull;
-  const dim3 block(kMrThreads), grid((unsigned)mr_blocks(Q));
+  p.n_tiles = surf_tiles(T); p.cull = cull;
+  const dim3 block(kSurfThreads), grid((unsigned)surf_blocks(Q));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (mode == 0) hipLaunchKernelGGL(mr_cast_kernel<0>, grid, block, 0, s, p);
   else hipLaunchKernelGGL(mr_cast_kernel<1>, grid, block, 0, s, p);

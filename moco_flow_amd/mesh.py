@@ -633,7 +633,7 @@ def export_obj(path, verts, tris):
 
 
 # ---- mesh-to-mesh distances (csrc/mf_mesh_distance.hip; include/mocoflow_hip.h "mesh-to-mesh distances") ----
-_MD_TILE = 64
+_TILE = 64                               # slots per tile and rows per wave (csrc/mf_surface.hpp kSurfTile)
 _MD_MODES = {"sweep": 0, "cull": 1}
 
 
@@ -667,7 +667,7 @@ class MeshIndex:
     @property
     def corners(self):
         if self._corners is None:
-            corners = torch.empty((self.n_tiles * _MD_TILE, 16), dtype=torch.float32, device=self.device)
+            corners = torch.empty((self.n_tiles * _TILE, 16), dtype=torch.float32, device=self.device)
             L.launch(self.device, "mf_surface_corners", L.ptr0(self.verts), self.V, L.ptr0(self.tris), self.T, L.ptr0(self.slot_tri),
                      L.ptr0(corners))
             self._corners = corners
@@ -682,8 +682,8 @@ class MeshIndex:
         dev = verts.device
         self.verts, self.tris = verts.detach().contiguous(), tris.detach().contiguous()
         V, T = self.verts.shape[0], self.tris.shape[0]
-        Tp = (T + _MD_TILE - 1) // _MD_TILE * _MD_TILE
-        self.V, self.T, self.n_tiles, self.device = V, T, Tp // _MD_TILE, dev
+        Tp = (T + _TILE - 1) // _TILE * _TILE
+        self.V, self.T, self.n_tiles, self.device = V, T, Tp // _TILE, dev
         if T and V:
             cen = self.verts[self.tris.clamp(0, V - 1)].mean(1).nan_to_num(0.0, 0.0, 0.0)
             self.lo, self.hi = cen.amin(0), cen.amax(0)
@@ -701,7 +701,7 @@ class MeshIndex:
                 raise RuntimeError(f"MeshIndex: order must be int32 ({T},), got {order.dtype} {tuple(order.shape)}")
             self.order = order.contiguous()
         slot_codes = codes if self.order is None else codes[self.order.long().clamp(0, max(T - 1, 0))]
-        self.tile_codes = slot_codes[::_MD_TILE].contiguous()                # ascending under "morton"
+        self.tile_codes = slot_codes[::_TILE].contiguous()                   # ascending under "morton"
         f32 = dict(dtype=torch.float32, device=dev)
         self.records, self.edges = torch.empty((Tp, 16), **f32), torch.empty((Tp, 12), **f32)
         self.slot_tri = torch.empty(Tp, dtype=torch.int32, device=dev)
@@ -730,6 +730,15 @@ def _as_index(mesh, what):
     raise RuntimeError(f"{what}: a mesh is a MeshIndex or a (verts, tris) pair")
 
 
+def _schedule(index, anchors):
+    """The schedule of a search: the rows in the Morton order of ``anchors`` (Q >= 1, 3), and per wave of 64 the tile whose code is
+    nearest its first row's -> (qorder (Q,) int32, start (waves,) int32 or None without tiles).  No result depends on it."""
+    codes, qorder = torch.sort(_morton(anchors, index.lo, index.hi), stable=True)
+    first = codes[::_TILE].contiguous()                                      # the code of each wave's first row
+    start = (torch.searchsorted(index.tile_codes, first, right=True) - 1).clamp(0, index.n_tiles - 1).to(torch.int32) if index.n_tiles else None
+    return qorder.to(torch.int32), start
+
+
 def closest_point(points, index, mode="cull", return_region=False, return_visited=False):
     """The closest point of a mesh to each of ``points`` (Q, 3) float32 on the index's device -> (d2 (Q,) float32, tri (Q,)
     int32 in the caller's numbering, point (Q, 3) float32[, region (Q,) uint8: 0 edge ab, 1 edge ac, 2 edge bc, 3 the face]
@@ -752,18 +761,13 @@ def closest_point(points, index, mode="cull", return_region=False, return_visite
         raise RuntimeError(f"closest_point: points on {points.device}, the index on {dev}")
     q = points.detach().contiguous()
     Q = q.shape[0]
-    n_waves = (Q + 63) // 64
     d2 = torch.empty(Q, dtype=torch.float32, device=dev)
     tri = torch.empty(Q, dtype=torch.int32, device=dev)
     point = torch.empty((Q, 3), dtype=torch.float32, device=dev)
     region = torch.empty(Q, dtype=torch.uint8, device=dev) if return_region else None
-    visited = torch.empty(n_waves, dtype=torch.int32, device=dev) if return_visited else None
+    visited = torch.empty((Q + _TILE - 1) // _TILE, dtype=torch.int32, device=dev) if return_visited else None
     if Q:
-        codes, qorder = torch.sort(_morton(q, index.lo, index.hi), stable=True)
-        qorder = qorder.to(torch.int32)
-        start = None
-        if index.n_tiles:
-            start = (torch.searchsorted(index.tile_codes, codes[::64].contiguous(), right=True) - 1).clamp(0, index.n_tiles - 1).to(torch.int32)
+        qorder, start = _schedule(index, q)
         L.launch(dev, "mf_surface_closest", L.ptr0(index.records), L.ptr0(index.edges), L.ptr0(index.slot_tri), L.ptr0(index.tile_box),
                  index.T, q.data_ptr(), Q, qorder.data_ptr(), L.ptr0(start), _MD_MODES[mode], d2.data_ptr(),
                  tri.data_ptr(), point.data_ptr(), L.ptr0(region), L.ptr0(visited))
@@ -923,21 +927,16 @@ def cast_rays(index, origins=None, dirs=None, rays=None, t_min=0.0, t_max=math.i
         o_ptr, d_ptr = o.data_ptr(), d.data_ptr()
     if o.device != dev:
         raise RuntimeError(f"cast_rays: rays on {o.device}, the index on {dev}")
-    n_waves = (Q + 63) // 64
     first = mode == "first"
     t = torch.empty(Q, dtype=torch.float32, device=dev) if first else None
     tri = torch.empty(Q, dtype=torch.int32, device=dev) if first else None
     bary = torch.empty((Q, 3), dtype=torch.float32, device=dev) if first else None
     hit = None if first else torch.empty(Q, dtype=torch.uint8, device=dev)
-    visited = torch.empty(n_waves, dtype=torch.int32, device=dev) if return_visited else None
+    visited = torch.empty((Q + _TILE - 1) // _TILE, dtype=torch.int32, device=dev) if return_visited else None
     if Q:
         centre = (index.lo + index.hi) * 0.5
         reach = (centre - o).norm(dim=1, keepdim=True) / d.norm(dim=1, keepdim=True)
-        codes, qorder = torch.sort(_morton(o + d * reach, index.lo, index.hi), stable=True)
-        qorder = qorder.to(torch.int32)
-        start = None
-        if index.n_tiles:
-            start = (torch.searchsorted(index.tile_codes, codes[::64].contiguous(), right=True) - 1).clamp(0, index.n_tiles - 1).to(torch.int32)
+        qorder, start = _schedule(index, o + d * reach)
         L.launch(dev, "mf_surface_cast", L.ptr0(index.corners), L.ptr0(index.slot_tri), L.ptr0(index.tile_box), index.T, o_ptr, d_ptr, stride,
                  lo_ptr, hi_ptr, bound_stride, Q, qorder.data_ptr(), L.ptr0(start), _MR_MODES[mode], 1 if cull else 0, L.ptr0(t), L.ptr0(tri),
                  L.ptr0(bary), L.ptr0(hit), L.ptr0(visited))

@@ -211,8 +211,18 @@ def better(d, tri, best, btri):
     return (np.asarray(tri) >= 0) & ((d < best) | ((d == best) & (u(tri) < u(btri))))
 
 
+def tile_walk(start, n):
+    """The tiles a wave visits, in its order: s, s + 1, s - 1, s + 2, ... inside [0, n), s = `start` clamped into it."""
+    s = min(max(int(start), 0), n - 1)
+    for k in range(2 * max(s, n - 1 - s) + 1):
+        d = (k + 1) >> 1
+        t = s + d if k & 1 else s - d
+        if 0 <= t < n:
+            yield t
+
+
 def closest_culled(R, query, qorder=None, start=None, cull=True):
-    """The search as a wave performs it: 64 queries in the visiting order, tiles s, s + 1, s - 1, ..., one decision per tile.
+    """The search as a wave performs it: 64 queries in the visiting order, the tiles of tile_walk, one decision per tile.
     -> d2, tri, slot per query, and the number of tiles each wave evaluated."""
     q = np.ascontiguousarray(query, dtype=F).reshape(-1, 3)
     Q, n = len(q), len(R["tile_box"])
@@ -224,13 +234,8 @@ def closest_culled(R, query, qorder=None, start=None, cull=True):
         rows = qorder[w * TILE:(w + 1) * TILE]
         qq = q[rows]
         best, btri, bslot = np.full(len(rows), np.inf, F), np.full(len(rows), -1, np.int32), np.full(len(rows), -1, np.int64)
-        s = min(max(int(start[w]) if start is not None else 0, 0), n - 1)
         count = 0
-        for k in range(2 * max(s, n - 1 - s) + 1):
-            d = (k + 1) >> 1
-            t = s + d if k & 1 else s - d
-            if t < 0 or t >= n:
-                continue
+        for t in tile_walk(start[w] if start is not None else 0, n):
             if cull:
                 lb = box_lb(qq, R["tile_box"][t, 0:3], R["tile_box"][t, 3:6])
                 with np.errstate(invalid="ignore"):

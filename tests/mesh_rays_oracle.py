@@ -3,7 +3,7 @@ in np.float32, rounded once, in the header's order, with max / min that ignore a
 Brute force, vectorised over triangles and chunked over rays: the ray set-up, the sheared vertices (sheared once per VERTEX, so
 that two triangles sharing one see the same three numbers -- the kernel recomputes them per corner from the same operands), the
 edge functions, the clamped t, the four acceptance conditions, the (t, index) minimum and the winner's barycentrics; the corner
-rows of mf_surface_corners; the tile predicate of the culled search.  Beside it a plain Moeller-Trumbore, in float64 as the
+rows of mf_surface_corners; the tile predicate of the culled search, and that search as a wave performs it.  Beside it a plain Moeller-Trumbore, in float64 as the
 judge and in float32 as the thing the contract replaces, the blob mesh and the ray families of the watertightness tests.  The
 index (slots, tiles, the drop rule) is mesh_distance_oracle.records' -- the cast reads the same one.  As there, the only float
 comparison that is not bit for bit is the sign of a zero, so callers compare with == (np.array_equal)."""
@@ -215,6 +215,52 @@ def tile_wanted(R, ray, best=np.inf):
     with np.errstate(all="ignore"):
         geo = (x0 <= 0) & (0 <= x1) & (y0 <= 0) & (0 <= y1) & ~(z1 < ray["t_min"][:, None]) & ~(z0 > ray["t_max"][:, None]) & (z0 <= best)
     return geo & (R["tile_box"][None, :, 6] != 0) & ~ray["dead"][:, None]
+
+
+def cast_culled(R, o, d, t_min, t_max, mode, qorder=None, start=None, cull=True):
+    """The cast as a wave performs it: 64 rays in the visiting order, the tiles of mesh_distance_oracle.tile_walk, one decision
+    per tile.  A lane is done if its ray is dead or, in mode 1 (any), has found a hit; under `cull` the wave stops once every
+    lane is done and skips a tile that holds no kept slot or that no lane still at work wants at its current best.  A tile that
+    is not skipped is evaluated slot by slot, as the lanes do.  -> t, tri, bary (mode 0; else None), hit (mode 1; else None) and
+    the number of tiles each wave evaluated."""
+    ray = setup(o, d, t_min, t_max)
+    Q, n = ray["Q"], len(R["tile_box"])
+    qorder = np.arange(Q) if qorder is None else np.asarray(qorder)
+    t_out, tri, bary, hit = np.full(Q, np.inf, F), np.full(Q, -1, np.int32), np.zeros((Q, 3), F), np.zeros(Q, np.uint8)
+    rows_of, slot_tri = corners(R).reshape(n, TILE, 16), R["slot_tri"].reshape(n, TILE)
+    visited = []
+    for w in range(-(-Q // TILE)):
+        rows = qorder[w * TILE:(w + 1) * TILE]
+        r = dict(_rows(ray, rows), Q=len(rows))
+        best, btri, found = np.full(len(rows), np.inf, F), np.full(len(rows), -1, np.int32), np.zeros(len(rows), bool)
+        buvw = np.zeros((len(rows), 4), F)                                  # the winner's U, V, W, det
+        count = 0
+        for t in D.tile_walk(start[w] if start is not None else 0, n):
+            if cull:
+                done = r["dead"] | found if mode == 1 else r["dead"]
+                if done.all():
+                    break
+                if not (~done & tile_wanted(dict(tile_box=R["tile_box"][t:t + 1]), r, best)[:, 0]).any():
+                    continue
+            count += 1
+            A, B, C = (shear(rows_of[t, :, k:k + 3], r) for k in (0, 3, 6))
+            U, V, W, det, th, acc = tri_terms(A, B, C, r["t_min"][:, None], r["t_max"][:, None])
+            acc &= ~r["dead"][:, None] & (slot_tri[t] >= 0)[None, :]
+            for j in range(TILE):                                           # slot by slot, as the lanes do
+                if mode == 1:                                               # best stays +inf: any hit will do
+                    found |= acc[:, j]
+                    continue
+                win = acc[:, j] & D.better(th[:, j], slot_tri[t, j], best, btri)
+                best = np.where(win, th[:, j], best)
+                btri = np.where(win, slot_tri[t, j], btri).astype(np.int32)
+                buvw = np.where(win[:, None], np.stack([U[:, j], V[:, j], W[:, j], det[:, j]], -1), buvw)
+        with np.errstate(all="ignore"):
+            rdet = F(1) / buvw[:, 3:4]
+            t_out[rows], tri[rows], bary[rows] = best, btri, np.where(btri[:, None] >= 0, buvw[:, 0:3] * rdet, F(0))
+        hit[rows] = found
+        visited.append(count)
+    first = mode == 0
+    return (t_out if first else None, tri if first else None, bary if first else None, None if first else hit, np.array(visited))
 
 
 # ---------------------------------------------------------------- Moeller-Trumbore --------------------------------------------

@@ -52,10 +52,12 @@ def _index(M, verts, tris, order="morton"):
 
 
 def _raw(M, index, q, mode, qorder=None, start=None):
-    """mf_surface_closest alone, on outputs filled with a sentinel beforehand, so that an unwritten row shows."""
+    """mf_surface_closest alone, on outputs filled with a sentinel beforehand, so that an unwritten row shows -> (d2, tri, point,
+    region, visited)."""
     L = M._lib
     q = _dev(q)
     Q = q.shape[0]
+    visited = torch.full(((Q + 63) // 64,), -5, dtype=torch.int32, device="cuda")
     d2 = torch.full((Q,), -7.0, dtype=torch.float32, device="cuda")
     tri = torch.full((Q,), -9, dtype=torch.int32, device="cuda")
     point = torch.full((Q, 3), -7.0, dtype=torch.float32, device="cuda")
@@ -63,8 +65,8 @@ def _raw(M, index, q, mode, qorder=None, start=None):
     qo = None if qorder is None else _dev(np.asarray(qorder, dtype=np.int32))
     st = None if start is None else _dev(np.asarray(start, dtype=np.int32))
     L.launch(q.device, "mf_surface_closest", L.ptr0(index.records), L.ptr0(index.edges), L.ptr0(index.slot_tri), L.ptr0(index.tile_box), index.T,
-             L.ptr0(q), Q, L.ptr0(qo), L.ptr0(st), mode, L.ptr0(d2), L.ptr0(tri), L.ptr0(point), L.ptr0(region), None)
-    return tuple(_np(t) for t in (d2, tri, point, region))
+             L.ptr0(q), Q, L.ptr0(qo), L.ptr0(st), mode, L.ptr0(d2), L.ptr0(tri), L.ptr0(point), L.ptr0(region), L.ptr0(visited))
+    return tuple(_np(t) for t in (d2, tri, point, region, visited))
 
 
 def _same(got, want, what=""):
@@ -171,6 +173,41 @@ def test_order_independence(M, soup_case):
     Rb = O.records(verts, tris, bad)
     _records_match(index, Rb)
     _same(M.closest_point(_dev(q), index, return_region=True), O.closest(Rb, q))
+
+
+def _schedules(M, index, anchors):
+    """The four query schedules the walk is pinned under, as (qorder, start) in numpy: as the package derives them; none
+    (identity, tile 0); the package's order with every wave starting at the last tile; starts out of range on both sides."""
+    qorder, start = (_np(x) for x in M.mesh._schedule(index, anchors))
+    n_waves, n = len(start), index.n_tiles
+    return ((qorder, start), (None, None), (qorder, np.full(n_waves, n - 1)), (qorder, np.where(np.arange(n_waves) % 2, n + 5, -3)))
+
+
+@pytest.mark.parametrize("T", [65, 130, 1000])
+def test_the_walk_is_the_oracles(M, sphere, T):
+    """The tiles each wave evaluates under the cull are closest_culled's, exactly, in four schedules: the visiting order, the
+    clamped start and the one decision per wave and tile are the oracle's.  (2, 3 and 16 tiles; two full waves and one of 2.)"""
+    verts, tris = sphere
+    tris = tris[:T]
+    index = _index(M, verts, tris)
+    R = O.records(verts, tris, _np(index.order))
+    q = _near(verts, tris, 130, np.random.default_rng(T), 0.02)
+    want = O.closest(R, q)
+    n, counts = index.n_tiles, []
+    assert n == -(-T // 64)
+    for k, (qorder, start) in enumerate(_schedules(M, index, _dev(q))):
+        d2, tri, slot, visited = O.closest_culled(R, q, qorder, start)
+        assert np.array_equal(d2, want[0]) and np.array_equal(tri, want[1])
+        if k == 3:                                                                     # out of range behaves as clamped
+            assert np.array_equal(visited, O.closest_culled(R, q, qorder, np.clip(start, 0, n - 1))[3])
+        print(f"T={T} schedule {k}: tiles evaluated per wave {visited} of {n}")
+        counts.append(visited)
+        got = _raw(M, index, q, 1, qorder, start)
+        _same(got, want, (T, k))
+        assert got[4].dtype == np.int32 and np.array_equal(got[4], visited), (T, k, got[4], visited)
+        assert (_raw(M, index, q, 0, qorder, start)[4] == n).all()
+    counts = np.concatenate(counts)
+    assert ((counts > 0) & (counts < n)).any()                                         # not vacuous: the oracle itself culls here
 
 
 def test_cull_equals_sweep_at_size(M):

@@ -4,7 +4,7 @@ comparison is equality, with no tolerance and nothing left out (np.array_equal: 
 thing it does not see, mesh_distance_oracle.py says why); where no oracle is run (the mesh at size) the culled search is
 held to the full sweep, byte for byte.
 
-Launch shape: the cast has no grid-stride loop -- a wave per 64 rays, a workgroup per kMrThreads -- so there is no second trip to
+Launch shape: the cast has no grid-stride loop -- a wave per 64 rays, a workgroup per kSurfThreads -- so there is no second trip to
 reach; Q = 300 and the 10 700-ray case run several workgroups."""
 import numpy as np
 import pytest
@@ -172,6 +172,68 @@ def test_ties_resolve_to_the_lowest_index(M, blob, inside):
             got = M.cast_rays(_index(M, v, t, order), _dev(o1), _dev(d1))
             _same(got, O.cast(R, o1, d1))
             assert _np(got[1]).tolist() == [0] and _np(got[0]).tolist() == [0.5]
+
+
+def _schedules(M, index, o, d):
+    """The four ray schedules the walk is pinned under, as (qorder, start) in numpy: as cast_rays derives them (the Morton order
+    of the point each ray reaches at the distance of the mesh's centre); none (identity, tile 0); that order with every wave
+    starting at the last tile; starts out of range on both sides."""
+    o, d = _dev(o), _dev(d)
+    reach = ((index.lo + index.hi) * 0.5 - o).norm(dim=1, keepdim=True) / d.norm(dim=1, keepdim=True)
+    qorder, start = (_np(x) for x in M.mesh._schedule(index, o + d * reach))
+    n_waves, n = len(start), index.n_tiles
+    return ((qorder, start), (None, None), (qorder, np.full(n_waves, n - 1)), (qorder, np.where(np.arange(n_waves) % 2, n + 5, -3)))
+
+
+@pytest.mark.parametrize("T", [65, 130, 1280])
+def test_the_walk_is_the_oracles(M, blob, inside, outside, T):
+    """The tiles each wave evaluates, and every output, are cast_culled's, exactly: both modes, cull on and off, four schedules.
+    The visiting order, the clamped start, the early exit and the one decision per wave and tile are the oracle's.  (2, 3 and 20
+    tiles; two full waves and one of 2 rays.)"""
+    verts, tris = blob
+    tris = tris[:T]
+    index = _index(M, verts, tris)
+    R = _records(index, verts, tris)
+    n = index.n_tiles
+    rng = np.random.default_rng(T)
+    pick_in, pick_out = rng.choice(len(inside[0]), 100, replace=False), rng.choice(len(outside[0]), 30, replace=False)
+    perm = rng.permutation(130)
+    o = np.concatenate([inside[0][pick_in], outside[0][pick_out]])[perm]
+    d = np.concatenate([inside[1][pick_in], outside[1][pick_out]])[perm]
+    want = O.cast(R, o, d)
+    culled, fewer_any = [], False
+    for k, (qorder, start) in enumerate(_schedules(M, index, o, d)):
+        per_mode = {}
+        for mode in (0, 1):
+            for cull in (1, 0):
+                ref = O.cast_culled(R, o, d, 0.0, np.inf, mode, qorder, start, bool(cull))
+                if mode == 0:
+                    _same(ref, want, ("oracle", T, k, cull))
+                else:
+                    _same_hit(ref[3], want, ("oracle", T, k, cull))
+                got = _raw(M, index, o, d, mode=mode, cull=cull, qorder=qorder, start=start)
+                _same(got, want, (T, k, cull)) if mode == 0 else _same_hit(got[3], want, (T, k, cull))
+                assert got[4].dtype == np.int32 and np.array_equal(got[4], ref[4]), (T, k, mode, cull, got[4], ref[4])
+                if not cull:
+                    assert (ref[4] == n).all()
+                    continue
+                per_mode[mode] = ref[4]
+                if k == 3:                                                   # out of range behaves as clamped
+                    assert np.array_equal(ref[4], O.cast_culled(R, o, d, 0.0, np.inf, mode, qorder, np.clip(start, 0, n - 1))[4])
+        print(f"T={T} schedule {k}: tiles evaluated per wave of {n}: first {per_mode[0]}, any {per_mode[1]}")
+        culled += [per_mode[0], per_mode[1]]
+        fewer_any = fewer_any or bool((per_mode[1] < per_mode[0]).any())
+    culled = np.concatenate(culled)
+    assert ((culled > 0) & (culled < n)).any()                               # not vacuous: the oracle itself culls here,
+    assert fewer_any == (T > 65)                                             # any hit more (of 65 triangles, never a whole wave's rays)
+    # a wave of dead rays (zero directions) evaluates nothing under the cull, and every tile under the sweep
+    dead = np.zeros((64, 3), F)
+    for mode in (0, 1):
+        for cull in (1, 0):
+            ref = O.cast_culled(R, o[:64], dead, 0.0, np.inf, mode, cull=bool(cull))
+            got = _raw(M, index, o[:64], dead, mode=mode, cull=cull)
+            assert ref[4].tolist() == got[4].tolist() == [0 if cull else n]
+            assert (got[1] == -1).all() and np.isinf(got[0]).all() if mode == 0 else not got[3].any()
 
 
 def test_cull_equals_sweep_at_size(M):

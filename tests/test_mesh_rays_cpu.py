@@ -60,6 +60,44 @@ def test_tile_predicate_passes_every_accepted_triangle(case):
     assert wanted.sum(1).mean() < len(R["tile_box"]) / 2                    # and it does reject
 
 
+def test_the_culled_cast_equals_the_brute_force():
+    """cast_culled -- the walk of a wave, tile by tile -- returns what cast does: cull on and off, both modes, the rays in
+    identity order from tile 0, and sorted as the slots are from the tile in the middle."""
+    verts, tris = O.blob()
+    lo, hi = verts.min(0), verts.max(0)
+
+    def cell(p):                                                            # a 6-bit Morton code: 4 cells per axis over the mesh's box
+        g = np.clip((p - lo) / (hi - lo) * 4, 0, 3).astype(np.int64)
+        return sum(((g[:, a] >> b) & 1) << (3 * b + 2 - a) for a in range(3) for b in range(2))
+    R = O.records(verts, tris, np.argsort(cell(verts[tris].mean(1)), kind="stable"))      # compact tiles
+    n = len(R["tile_box"])
+    assert n == 20
+    rng = np.random.default_rng(61)
+    d = rng.normal(size=(150, 3)).astype(F)
+    o = np.tile(O.blob_interior(), (150, 1))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o[128:] += d[128:] * F(4)                                               # the last wave: from outside, looking back or past
+    d[128:] = -d[128:] + rng.normal(size=(22, 3)).astype(F) * F(0.3)
+    d[7] = 0                                                                # a dead ray
+    want = O.cast(R, o, d, 0.0, np.inf)
+    assert 128 < want[3].sum() < 149
+    n_waves = 3
+    by_cell = np.concatenate([np.argsort(cell(o[:128] + d[:128]), kind="stable"), np.arange(128, 150)])
+    for qorder, start in ((None, None), (by_cell, np.full(n_waves, n // 2))):
+        counts = {}
+        for cull in (True, False):
+            for mode in (0, 1):
+                got = O.cast_culled(R, o, d, 0.0, np.inf, mode, qorder, start, cull)
+                counts[cull, mode] = got[4]
+                if mode == 0:
+                    assert all(g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got[:3], want[:3])), (cull, mode)
+                else:
+                    assert np.array_equal(got[3], want[3])
+            assert cull or all((counts[cull, mode] == n).all() for mode in (0, 1))
+    print("tiles evaluated per wave, rays sorted: first", counts[True, 0], "any", counts[True, 1])
+    assert counts[True, 1].sum() < counts[True, 0].sum() < n * n_waves      # sorted rays: the cull does cull, any hit more so
+
+
 def test_against_float64(case):
     n = len(case["families"]["random"])
     sl = slice(len(case["d"]) - n - 18, len(case["d"]) - 18)                # the 3 000 random rays
